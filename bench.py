@@ -3,6 +3,7 @@
 (BASELINE.json config #2/#3), bf16 normal equations, data-parallel over N MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--rows R] [--features D] [--dtype bf16]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -12,6 +13,15 @@ column: fused MFMA Gram pass over the rank's shard -> RCCL all-reduce of the f64
 xGMI -> f64 normal-equation solve -> model.  Rows are sharded across ranks (strong scaling: the
 global dataset is fixed at --rows).  Synthetic data, random-init coefficients; nothing is cached
 between steps.  Rank 0 prints one JSON line.
+
+A plain run does only what the headline figure needs: set up, warm up, time the K steps, print
+the line.  ``--dump-outputs DIR`` also writes what the last timed fit returned (the model a
+caller of ``fit`` receives) as ``DIR/coefficients.npy`` and ``DIR/intercept.npy`` (float64); the
+synthetic data is seeded, so the same arguments give the same inputs on every run and two builds
+can be compared output for output.  ``--full`` is the switch for every measurement beyond the
+headline; this benchmark has none of its own (the CPU baselines, other configurations and
+per-kernel figures are separate programs under ``benchmarks/`` and ``scripts/``), so today it
+changes nothing.
 """
 from __future__ import annotations
 
@@ -46,8 +56,17 @@ def _args(argv=None):
                     help="synchronous fits (host WLS solve after a D2H of the statistics, every step)")
     ap.add_argument("--async", dest="use_async", action="store_true",
                     help="asynchronous fits (device WLS solve, no host wait per step; the default)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the model of the last timed fit as DIR/<name>.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beyond the headline figure (none today)")
     ap.set_defaults(use_async=True)
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return a
 
 
 def _self_launch(a, argv) -> int:
@@ -151,6 +170,13 @@ def main(argv=None):
     value = global_rows * a.steps / elapsed
     coef = model.coefficients.toArray()
     err = float(abs(coef - beta.double().cpu().numpy()).max())
+    if rank == 0 and a.dump_outputs:
+        import numpy as np
+
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        np.save(os.path.join(a.dump_outputs, "coefficients.npy"), np.asarray(coef, dtype=np.float64))
+        np.save(os.path.join(a.dump_outputs, "intercept.npy"),
+                np.asarray([float(model.intercept)], dtype=np.float64))
     if rank == 0:
         line = {
             "metric": "rows/sec LinearRegression.fit, 1e8x32 synthetic, at 1/2/4/8 MI355X",

@@ -50,6 +50,37 @@ def test_bench_py_json_contract():
     assert line["config"]["coef_max_abs_err"] < 0.05
 
 
+def test_bench_py_dumps_the_last_models_arrays(tmp_path):
+    """``--dump-outputs DIR`` writes the model of the last timed fit (float64 ``coefficients.npy``
+    and ``intercept.npy``); seeded inputs, so a second run with the same arguments writes the same
+    arrays.  ``--full`` is accepted and keeps the result line's contract."""
+    import numpy as np
+
+    got = []
+    for name, extra in (("a", []), ("b", ["--full"])):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1",
+                              "--rows", "50000", "--dump-outputs", str(tmp_path / name), *extra],
+                             capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        line = json.loads(out.stdout.strip().splitlines()[-1])
+        assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["dtype"] == "bf16"
+        assert sorted(os.listdir(tmp_path / name)) == ["coefficients.npy", "intercept.npy"]
+        coef = np.load(tmp_path / name / "coefficients.npy")
+        icpt = np.load(tmp_path / name / "intercept.npy")
+        assert coef.dtype == np.float64 and coef.shape == (32,) and icpt.dtype == np.float64 and icpt.shape == (1,)
+        # the generating model: beta = linspace(-2, 2, 32), intercept 0.5
+        assert abs(coef - np.linspace(-2.0, 2.0, 32)).max() == pytest.approx(line["config"]["coef_max_abs_err"], abs=1e-6)
+        assert abs(coef - np.linspace(-2.0, 2.0, 32)).max() < 0.05 and abs(icpt[0] - 0.5) < 0.05
+        got.append((coef, icpt))
+    assert np.array_equal(got[0][0], got[1][0]) and np.array_equal(got[0][1], got[1][1])
+
+
+def test_bench_py_rejects_zero_steps():
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"],
+                         capture_output=True, text=True, timeout=300)
+    assert out.returncode == 2 and "--steps" in out.stderr
+
+
 def test_bench_py_self_launches_ranks():
     """``bench.py --gpus 2`` with no launcher spawns its own two ranks (gloo on this CPU box) and
     reports the two-rank run: n_gpus 2, dp2, one device per rank."""
