@@ -12,6 +12,8 @@ from .models.linalg import Vectors, DenseVector, SparseVector, Vector
 from .models.feature import VectorAssembler
 from .models.regression import (LinearRegression, LinearRegressionModel,
                                 LinearRegressionTrainingSummary)
+from .models.tuning import (ParamGridBuilder, CrossValidator, CrossValidatorModel, TrainValidationSplit,
+                            TrainValidationSplitModel)
 from .dq.rules import MinimumPriceDataQualityUdf, PriceCorrelationDataQualityUdf
 
 __version__ = "0.1.0"
@@ -21,4 +23,6 @@ __all__ = [
     "expr", "coalesce", "DataTypes", "StructType", "StructField", "Vectors", "DenseVector",
     "SparseVector", "Vector", "VectorAssembler", "LinearRegression", "LinearRegressionModel",
     "LinearRegressionTrainingSummary", "MinimumPriceDataQualityUdf", "PriceCorrelationDataQualityUdf",
+    "ParamGridBuilder", "CrossValidator", "CrossValidatorModel", "TrainValidationSplit",
+    "TrainValidationSplitModel",
 ]

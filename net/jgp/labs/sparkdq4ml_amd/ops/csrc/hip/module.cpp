@@ -13,6 +13,7 @@
 #include "csv_scan.h"
 #include "dqvm.h"
 #include "gram.h"
+#include "gram_folds.h"
 #include "gram_wide.h"
 #include "gram_syrk.h"
 #include "wls_small.h"
@@ -179,6 +180,35 @@ PYBIND11_MODULE(_dq4ml_hip, m) {
         });
   m.def("gram_reduce", [](int mode, uintptr_t partials, int blocks, int d, uintptr_t out, uintptr_t stream) {
     gram_reduce(mode, P<const double>(partials), blocks, d, P<double>(out), as_stream(stream));
+  });
+  // ---- fold-partitioned Gram (one-pass k-fold statistics) ----------------------------------
+  auto fold_rule = [](const std::vector<uint32_t>& thr, uint64_t seed) {
+    if (thr.size() + 1 > (size_t)kMaxFolds) throw std::invalid_argument("fold rule: at most 16 folds");
+    FoldRule fr{};
+    fr.seed = seed;
+    fr.k = (int)thr.size() + 1;
+    for (size_t j = 0; j < thr.size(); ++j) fr.thr[j] = thr[j];
+    return fr;
+  };
+  m.def("gram_folds_blocks", &gram_folds_blocks);
+  m.def("gram_folds", [fold_rule](uintptr_t X, int64_t ld, int d, int64_t n, int xdt, uintptr_t y, int ydt,
+                                  uintptr_t sel, const std::vector<uint32_t>& thr, uint64_t seed,
+                                  uintptr_t partials, int blocks, uintptr_t out, uintptr_t stream) {
+    GramArgs a{};
+    a.X = P<const void>(X);
+    a.ld = ld;
+    a.d = d;
+    a.n = n;
+    a.xdt = xdt;
+    a.y = P<const void>(y);
+    a.ydt = ydt;
+    a.sel = P<const uint8_t>(sel);
+    a.partials = P<double>(partials);
+    gram_folds(a, fold_rule(thr, seed), blocks, P<double>(out), as_stream(stream));
+  });
+  m.def("fold_ids", [fold_rule](int64_t n, int64_t granule, const std::vector<uint32_t>& thr, uint64_t seed,
+                                uintptr_t out, uintptr_t stream) {
+    fold_ids(n, granule, fold_rule(thr, seed), P<uint8_t>(out), as_stream(stream));
   });
   m.def("gram_window_fold", [](uintptr_t part, int64_t rows, int gw, uintptr_t flat, uintptr_t stream) {
     gram_window_fold(P<const double>(part), rows, gw, P<double>(flat), as_stream(stream));

@@ -279,6 +279,86 @@ def gram_stats(X, y, w, sel, compute: str = "fp64", x_zero_dead: bool = False, b
     return _unshift(h, out, shift, d)
 
 
+# One-pass fold kernel (gram_folds.hip) vs k masked gram_stats passes: the feature range where the
+# one-pass kernel measured faster (profiles/cv_onepass.md: d = 8, 16, 32, 64 at k = 3, 5, 10, by
+# 1.1x at d = 8, k = 3 up to 4.5x at d = 64, k = 10).  d < 8 was not measured and keeps the masked
+# route: its passes are the lane-per-row skinny kernel, the MFMA tile idles most lanes there.
+ONEPASS_MIN_D, ONEPASS_MAX_D = 8, 64
+FOLD_GRANULE = 64  # rows per granule of the one-pass kernel (= one superstep)
+
+
+def fold_ids(n: int, thr: np.ndarray, seed64: int, granule: int, dev) -> torch.Tensor:
+    """uint8 fold of physical rows 0..n-1 (``fold_ids_kernel``); ``seed64``: the rank-mixed seed."""
+    h = native.hip()
+    out = torch.empty(int(n), dtype=torch.uint8, device=dev)
+    if n > 0:
+        h.fold_ids(int(n), int(granule), [int(t) for t in thr], int(seed64), out.data_ptr(), _stream())
+    return out
+
+
+def onepass_ok(X, granule: int, compute: str) -> bool:
+    """The one-pass route's domain: 64-row granules, fp64 statistics of dense f32 / f64 features
+    with d in the measured range."""
+    return (torch.is_tensor(X) and X.dim() == 2 and int(granule) == FOLD_GRANULE and compute == "fp64"
+            and X.dtype in (torch.float32, torch.float64) and ONEPASS_MIN_D <= X.shape[0] <= ONEPASS_MAX_D)
+
+
+def gram_stats_folds(X, y, sel, k_or_weights, seed: int, granule: int, compute: str = "fp64", route: str = "auto",
+                     blocks: Optional[int] = None) -> torch.Tensor:
+    """Per-fold WLS statistics ``[k, P]`` (unit weights).  ``route``: "auto" (one-pass where
+    :func:`onepass_ok`, else masked), or "onepass" / "masked" to force one (tests, benchmarks;
+    a forced "onepass" accepts any d <= 64)."""
+    from . import kernels
+
+    thr = kernels.fold_thresholds(k_or_weights)
+    k = int(thr.size) + 1
+    seed64 = kernels.fold_seed(seed)
+    n = int(y.shape[0])
+    if route not in ("auto", "onepass", "masked"):
+        raise ValueError(f"gram_stats_folds: unknown route {route!r}")
+    if route == "auto":
+        route = "onepass" if onepass_ok(X, granule, compute) and n > 0 else "masked"
+    if route == "masked":
+        ids = fold_ids(n, thr, seed64, granule, y.device)
+        outs = []
+        for f in range(k):
+            m = ids == f
+            if sel is not None:
+                m &= sel.to(torch.bool)
+            outs.append(gram_stats(X, y, None, m, compute))
+        return torch.stack(outs)
+    h = native.hip()
+    if not (torch.is_tensor(X) and X.dim() == 2 and X.dtype in (torch.float32, torch.float64)):
+        raise ValueError("gram_stats_folds(onepass): dense f32 / f64 feature-major features only")
+    _check_dev(X, y, sel)
+    d = int(X.shape[0])
+    if int(X.shape[1]) != n or (sel is not None and sel.numel() != n):
+        raise ValueError("gram_stats_folds: row-count mismatch")
+    if int(granule) != FOLD_GRANULE or compute != "fp64" or not 1 <= d <= 64 or n < 1:
+        raise ValueError("gram_stats_folds(onepass): needs granule 64, fp64 statistics, 1 <= d <= 64, n >= 1")
+    Xv, ld = _feature_view(X, 16 // X.element_size())
+    y = y.contiguous()
+    if y.dtype not in (torch.float64, torch.float32):
+        y = y.to(torch.float64)
+    if sel is not None:
+        sel = sel.contiguous()
+        if sel.dtype != torch.bool:
+            sel = sel.to(torch.bool)
+    nb = blocks
+    if not nb:
+        key = (torch.cuda.current_device(), "folds", d, n, dtype_code(Xv))
+        nb = _plan_cache.get(key)
+        if nb is None:
+            nb = _plan_cache[key] = int(h.gram_folds_blocks(d, n, dtype_code(Xv)))
+    nb = int(nb)
+    P = int(h.gram_partial_stride(0, d))
+    partials = torch.empty(k * nb * P, dtype=torch.float64, device=X.device)
+    out = torch.empty(k, 5 + 2 * d + d * (d + 1) // 2, dtype=torch.float64, device=X.device)
+    h.gram_folds(Xv.data_ptr(), int(ld), d, n, dtype_code(Xv), y.data_ptr(), dtype_code(y), _ptr(sel),
+                 [int(t) for t in thr], int(seed64), partials.data_ptr(), nb, out.data_ptr(), _stream())
+    return out
+
+
 def gram_skinny_cols(parts: List[torch.Tensor], y, w, sel, blocks: Optional[int] = None):
     """f64 WLS statistics of a narrow (d <= 8) VectorAssembler output straight from its SOURCE
     columns (any of f64/f32/bf16/int32/int64/bool, mixed): the assembled [d, n] f64 matrix is

@@ -21,7 +21,7 @@ import torch
 from . import native
 
 __all__ = ["selected_indices", "pack_columns", "gram_stats", "predict", "regression_metrics",
-           "gram_layout_size"]
+           "gram_layout_size", "gram_stats_folds", "fold_ids", "fold_thresholds", "fold_seed"]
 
 
 def _on_gpu(t: torch.Tensor) -> bool:
@@ -150,6 +150,114 @@ def gram_stats(X: torch.Tensor, y: torch.Tensor, w: Optional[torch.Tensor], sel:
     out[5:5 + d] = Xw.sum(1)
     out[5 + d:5 + 2 * d] = Xw @ yd
     out[5 + 2 * d:] = packed_upper(aa)
+    return out
+
+
+# ------------------------------------------------------------------------------------------
+# K5f — fold-partitioned statistics (k-fold cross-validation in one pass)
+# ------------------------------------------------------------------------------------------
+MAX_FOLDS = 16
+_M64 = (1 << 64) - 1
+_RANK_SALT = 0xD1B54A32D192ED03
+
+
+def fold_seed(seed: int, rank: Optional[int] = None) -> int:
+    """Spark's ``long`` seed as the 64-bit hash seed of this rank: ``seed mod 2^64`` XOR
+    ``rank * 0xD1B54A32D192ED03 mod 2^64`` (rank 0 / world 1: the seed itself), so the shards of
+    a data-parallel table draw different granule hashes."""
+    if rank is None:
+        from ..parallel import comm
+
+        rank = comm.rank()
+    return (int(seed) & _M64) ^ ((int(rank) * _RANK_SALT) & _M64)
+
+
+def fold_thresholds(k_or_weights) -> np.ndarray:
+    """The k - 1 uint32 thresholds of the fold rule: ``(j << 32) // k`` for k equal folds, else
+    ``floor(c_j * 2^32)`` with c_j the normalised cumulative weight (f64)."""
+    if isinstance(k_or_weights, (int, np.integer)):
+        k = int(k_or_weights)
+        if not 1 <= k <= MAX_FOLDS:
+            raise ValueError(f"number of folds must be in [1, {MAX_FOLDS}], got {k}")
+        return np.array([(j << 32) // k for j in range(1, k)], dtype=np.uint32)
+    w = np.asarray(list(k_or_weights), dtype=np.float64)
+    if not 1 <= w.size <= MAX_FOLDS:
+        raise ValueError(f"number of split weights must be in [1, {MAX_FOLDS}], got {w.size}")
+    if not np.all(np.isfinite(w)) or np.any(w < 0) or not w.sum() > 0:
+        raise ValueError(f"Weights must be nonnegative and their sum positive, but got {w.tolist()}")
+    c = np.cumsum(w / w.sum())[:-1]
+    return np.minimum(np.floor(c * 4294967296.0), 4294967295.0).astype(np.uint32)
+
+
+def fold_hash(seed64: int, g: np.ndarray) -> np.ndarray:
+    """uint32 hash of granule indices ``g`` (uint64) under the 64-bit seed (splitmix64 finaliser,
+    high word); all arithmetic mod 2^64.  The device kernels compute the same bits."""
+    with np.errstate(over="ignore"):
+        z = np.uint64(seed64) + (g.astype(np.uint64) + np.uint64(1)) * np.uint64(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        z = z ^ (z >> np.uint64(31))
+    return (z >> np.uint64(32)).astype(np.uint32)
+
+
+def fold_ids_host(n: int, k_or_weights, seed64: int, granule: int) -> np.ndarray:
+    """uint8 fold of physical rows 0..n-1 under an already rank-mixed 64-bit seed."""
+    thr = fold_thresholds(k_or_weights)
+    granule = int(granule)
+    if granule < 1:
+        raise ValueError("fold granule must be >= 1")
+    ng = (int(n) + granule - 1) // granule
+    u = fold_hash(seed64, np.arange(ng, dtype=np.uint64))
+    f = np.searchsorted(thr, u, side="right").astype(np.uint8)  # = #{j : u >= t_j}
+    return np.repeat(f, granule)[:int(n)] if granule > 1 else f
+
+
+def fold_ids(n: int, k_or_weights, seed: int, granule: int, device=None) -> torch.Tensor:
+    """uint8 fold id of every physical row (row r belongs to granule r // granule) under Spark
+    seed ``seed`` on this rank; computed on ``device`` when it is a GPU, bit-equal to the host."""
+    dev = torch.device(device) if device is not None else torch.device("cpu")
+    if dev.type == "cuda":
+        from . import device as _device
+
+        return _device.fold_ids(int(n), fold_thresholds(k_or_weights), fold_seed(seed), int(granule), dev)
+    return torch.from_numpy(fold_ids_host(n, k_or_weights, fold_seed(seed), granule))
+
+
+def folds_route(X, granule: int, compute: str = "fp64") -> str:
+    """The route ``gram_stats_folds`` takes for these operands: "onepass" (the ``gram_folds``
+    kernel) or "masked" (k masked ``gram_stats`` passes; always on the host)."""
+    Xt = X if torch.is_tensor(X) else X.buf
+    if not _on_gpu(Xt):
+        return "masked"
+    from . import device
+
+    return "onepass" if device.onepass_ok(X, granule, compute) and int(X.shape[1]) > 0 else "masked"
+
+
+def gram_stats_folds(X: torch.Tensor, y: torch.Tensor, sel: Optional[torch.Tensor], k_or_weights, seed: int,
+                     granule: int, compute: str = "fp64") -> torch.Tensor:
+    """``[k, P]`` f64: row f is the ``gram_stats`` vector (unit weights) of the live rows whose
+    fold is f.  Device tensors: the one-pass ``gram_folds`` kernel or k masked ``gram_stats``
+    passes (``device.gram_stats_folds``); host tensors: fp64 torch (the oracle and CPU engine)."""
+    Xt = X if torch.is_tensor(X) else X.buf
+    if _on_gpu(Xt):
+        from . import device
+
+        return device.gram_stats_folds(X, y, sel, k_or_weights, seed, granule, compute)
+    d, n = X.shape
+    if int(y.shape[0]) != n or (sel is not None and sel.shape[0] != n):
+        raise ValueError("gram_stats_folds: row-count mismatch between features, label and selection")
+    thr = fold_thresholds(k_or_weights)
+    k = int(thr.size) + 1
+    ids = fold_ids(n, k_or_weights, seed, granule)
+    live = torch.ones(n, dtype=torch.bool) if sel is None else sel.to(torch.bool)
+    Xd = (X.to_dense() if hasattr(X, "to_dense") else X).to(torch.float64)
+    Xd = torch.where(live.unsqueeze(0), Xd, torch.zeros_like(Xd))  # dead rows: exact zeros, no NaN
+    yd = torch.where(live, y.to(torch.float64), torch.zeros(n, dtype=torch.float64))
+    out = torch.empty(k, gram_layout_size(d), dtype=torch.float64)
+    for f in range(k):
+        m = live & (ids == f)
+        out[f] = gram_stats(Xd, yd, None, m, "fp64")
     return out
 
 

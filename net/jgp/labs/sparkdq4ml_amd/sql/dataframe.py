@@ -369,6 +369,32 @@ class DataFrame:
 
     localCheckpoint = checkpoint
 
+    def _narrowed(self, t: Table, mask: torch.Tensor) -> "DataFrame":
+        """A frame over the columns of the executed table ``t`` whose selection vector is
+        ``t.sel & mask``: no row is copied (random splits, cross-validation folds)."""
+        sel = mask if t.sel is None else (t.sel & mask)
+        rel = LocalRelation(Table(t.schema, t.columns, t.nrows, sel, t.device), sharded=is_sharded(self._plan))
+        return DataFrame(rel, self.sparkSession)
+
+    def randomSplit(self, weights, seed=None) -> List["DataFrame"]:
+        """Randomly split the rows by the normalised ``weights``.  The plan executes once (like
+        ``checkpoint``); every returned frame shares its columns and narrows the selection vector
+        by the per-row fold ids (``ops.kernels.fold_ids``, granule 1)."""
+        from ..ops import kernels
+
+        weights = [float(w) for w in weights]
+        if any(w < 0 for w in weights):
+            raise ValueError(f"Weights must be nonnegative, but got {weights}")
+        if not sum(weights) > 0:
+            raise ValueError(f"Sum of weights must be positive, but got {weights}")
+        if seed is None:
+            import random
+
+            seed = random.getrandbits(63)
+        t = self._table()
+        ids = kernels.fold_ids(t.nrows, weights, int(seed), 1, t.device)
+        return [self._narrowed(t, ids == f) for f in range(len(weights))]
+
     # ---- actions ---------------------------------------------------------------------------
     def _table(self) -> Table:
         return execute(self._plan, self.sparkSession)
