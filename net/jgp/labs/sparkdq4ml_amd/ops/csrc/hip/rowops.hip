@@ -35,7 +35,9 @@ __device__ __forceinline__ void st_from_f64(void* p, int dt, int64_t i, double v
   switch (dt) {
     case DT_F64: reinterpret_cast<double*>(p)[i] = v; break;
     case DT_F32: reinterpret_cast<float*>(p)[i] = (float)v; break;
-    case DT_BF16: reinterpret_cast<__bf16*>(p)[i] = (__bf16)(float)v; break;
+    // one rounding, f64 -> bf16 (what the compiler made of a cast through float as well: an f64
+    // source is NOT rounded to f32 first, so 1 value in ~2^17 differs from torch's .to(bfloat16))
+    case DT_BF16: reinterpret_cast<__bf16*>(p)[i] = (__bf16)v; break;
     case DT_I32: reinterpret_cast<int32_t*>(p)[i] = (int32_t)v; break;
     case DT_I64: reinterpret_cast<int64_t*>(p)[i] = (int64_t)v; break;
     default: break;
@@ -744,7 +746,8 @@ void launch_huber(const void* X, int xdt, int64_t ld, int d, int64_t n, int tile
   } else {
     hipLaunchKernelGGL(huber_rows_kernel<0>, dim3(g), dim3(256), 0, st, X, xdt, ld, d, n, tiled, y, ydt, w, wdt, sel,
                        ceff, icpt, sigma, eps, mult, partials, act);
-    hipLaunchKernelGGL(sum_slabs_kernel, dim3(1), dim3(256), 0, st, partials, g, 4, out);
+    // (sum_cols, not sum_slabs: the same sums, and gated on `act` like every other kernel of the pass)
+    hipLaunchKernelGGL(sum_cols_kernel, dim3(4), dim3(256), 0, st, partials, g, 4, out, act);
     const int64_t c = xt_chunks(n, d), chunk = (n + c - 1) / c;
     double* part = partials + (int64_t)g * 4;
     hipLaunchKernelGGL(xt_part_kernel, dim3((unsigned)c, (unsigned)d), dim3(256), 0, st, X, xdt, ld, d, n, tiled,
