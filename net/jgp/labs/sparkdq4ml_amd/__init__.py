@@ -9,12 +9,12 @@ from .sql.column import Column
 from .sql.functions import callUDF, call_udf, col, lit, udf, when, expr, coalesce
 from .sql.types import DataTypes, StructType, StructField
 from .models.linalg import Vectors, DenseVector, SparseVector, Vector
-from .models.feature import VectorAssembler
+from .models.feature import VectorAssembler, Imputer, ImputerModel
 from .models.regression import (LinearRegression, LinearRegressionModel,
                                 LinearRegressionTrainingSummary)
 from .models.tuning import (ParamGridBuilder, CrossValidator, CrossValidatorModel, TrainValidationSplit,
                             TrainValidationSplitModel)
-from .dq.rules import MinimumPriceDataQualityUdf, PriceCorrelationDataQualityUdf
+from .dq.rules import MinimumPriceDataQualityUdf, PriceCorrelationDataQualityUdf, IqrRule
 
 __version__ = "0.1.0"
 
@@ -24,5 +24,5 @@ __all__ = [
     "SparseVector", "Vector", "VectorAssembler", "LinearRegression", "LinearRegressionModel",
     "LinearRegressionTrainingSummary", "MinimumPriceDataQualityUdf", "PriceCorrelationDataQualityUdf",
     "ParamGridBuilder", "CrossValidator", "CrossValidatorModel", "TrainValidationSplit",
-    "TrainValidationSplitModel",
+    "TrainValidationSplitModel", "Imputer", "ImputerModel", "IqrRule",
 ]

@@ -10,7 +10,8 @@ Each rule is a UDF object with both contracts of :mod:`..sql.udf`:
   and compiles into the fused DQ VM kernel together with the clean-up filters.
 
 ``RangeRule`` / ``NotNullRule`` / ``ThresholdRule`` generalize them for user pipelines (the
-"null/range UDF filters" of the 1e9-row DQ config).
+"null/range UDF filters" of the 1e9-row DQ config); ``IqrRule`` is a ``RangeRule`` whose bounds
+are the interquartile fence measured on a frame.
 """
 from __future__ import annotations
 
@@ -97,6 +98,28 @@ class RangeRule(DQRule):
 class NotNullRule(RangeRule):
     def __init__(self, sentinel=-1.0, name="notNullRule"):
         super().__init__(None, None, sentinel, name)
+
+
+class IqrRule(RangeRule):
+    """The interquartile-range fence as a :class:`RangeRule`: ``lo = q_lo - k * (q_hi - q_lo)``,
+    ``hi = q_hi + k * (q_hi - q_lo)`` with the two quantiles measured on a frame by
+    :meth:`fit` (exact, ``DataFrame.approxQuantile``).  Values outside ``[lo, hi]`` and nulls map
+    to ``sentinel``; both rule contracts are the parent's."""
+
+    def __init__(self, lo, hi, sentinel=-1.0, name="iqrRule", q_lo=None, q_hi=None, k=1.5):
+        super().__init__(lo, hi, sentinel, name)
+        self.q_lo, self.q_hi, self.k = q_lo, q_hi, k
+
+    @classmethod
+    def fit(cls, df, col, k=1.5, lower=0.25, upper=0.75, sentinel=-1.0, name="iqrRule"):
+        if not 0.0 <= float(lower) <= float(upper) <= 1.0:
+            raise ValueError(f"IqrRule: need 0 <= lower <= upper <= 1, got {lower}, {upper}")
+        qs = df.approxQuantile(col, [float(lower), float(upper)], 0.0)
+        if not qs:
+            raise ValueError(f"IqrRule: column {col} has no non-null, non-NaN value")
+        q_lo, q_hi = float(qs[0]), float(qs[1])
+        spread = q_hi - q_lo
+        return cls(q_lo - float(k) * spread, q_hi + float(k) * spread, sentinel, name, q_lo, q_hi, float(k))
 
 
 def register_lab_rules(session):

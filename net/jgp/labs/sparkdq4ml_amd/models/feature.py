@@ -6,6 +6,9 @@ input column becomes one contiguous row of the matrix, cast to ``outputDtype`` (
 param; ``float64`` keeps Spark's double semantics, ``float32``/``bfloat16`` feed the fast MFMA Gram
 paths).  ``handleInvalid``: ``error`` (default, null -> job failure), ``skip`` (drop rows), ``keep``
 (NaN).
+
+``Imputer`` / ``ImputerModel`` (``org.apache.spark.ml.feature.Imputer``): mean or exact-median
+surrogates for the missing values of double / float columns, applied as lazy IR expressions.
 """
 from __future__ import annotations
 
@@ -20,10 +23,10 @@ from ..sql.expressions import (AnalysisException, ColRef, EvalContext, Expr, IsN
                                SparkException)
 from ..sql.plan import Filter, Project
 from ..sql.table import ColumnData, LazyVectorColumn
-from ..sql.types import (BooleanType, DoubleType, VectorUDT, is_numeric)
+from ..sql.types import (BooleanType, DoubleType, FloatType, VectorUDT, is_numeric)
 from .param import Param, Params, param_accessors
 
-__all__ = ["VectorAssembler", "VectorAssembleExpr"]
+__all__ = ["VectorAssembler", "VectorAssembleExpr", "Imputer", "ImputerModel"]
 
 _DT = {"float64": torch.float64, "double": torch.float64, "float32": torch.float32, "float": torch.float32,
        "bfloat16": torch.bfloat16, "bf16": torch.bfloat16, "float8": torch.float8_e4m3fn, "fp8": torch.float8_e4m3fn}
@@ -216,6 +219,151 @@ class VectorAssembler(Params):
         from .persistence import load_params_only
 
         return load_params_only(cls, path)
+
+
+def _is_nan(v) -> bool:
+    return isinstance(v, float) and v != v
+
+
+_IMPUTER_PARAMS = {
+    "inputCols": Param("inputCols", "input column names", None, has_default=False),
+    "outputCols": Param("outputCols", "output column names", None, has_default=False),
+    "strategy": Param("strategy", "strategy for imputation: mean or median of the non-missing values", "mean",
+                      lambda v: v in ("mean", "median")),
+    "missingValue": Param("missingValue", "the placeholder for the missing values; all occurrences of it (and "
+                                          "every null) are imputed", float("nan"), converter=float),
+}
+
+
+class _ImputerParams(Params):
+    _params = _IMPUTER_PARAMS
+
+    def setInputCols(self, cols):
+        return self.set("inputCols", list(cols))
+
+    def setOutputCols(self, cols):
+        return self.set("outputCols", list(cols))
+
+    def _io_cols(self, schema):
+        ins, outs = self.getOrDefault("inputCols"), self.getOrDefault("outputCols")
+        if len(ins) != len(set(ins)) or len(outs) != len(set(outs)):
+            raise ValueError("Imputer: inputCols and outputCols must each hold distinct names")
+        if len(ins) != len(outs) or not ins:
+            raise ValueError(f"Imputer: inputCols ({len(ins)}) and outputCols ({len(outs)}) must be non-empty and "
+                             "of one length")
+        for c in ins:
+            t = ColRef(c).data_type(schema)
+            if not isinstance(t, (DoubleType, FloatType)):
+                raise ValueError(f"Imputer: input column {c} must be of type double or float, but is "
+                                 f"{t.simpleString()}")
+        return ins, outs
+
+    def save(self, path):
+        raise NotImplementedError("Spark-ML persistence of the Imputer is not implemented")
+
+    def write(self):
+        raise NotImplementedError("Spark-ML persistence of the Imputer is not implemented")
+
+
+@param_accessors
+class Imputer(_ImputerParams):
+    """``org.apache.spark.ml.feature.Imputer`` (Spark 2.4): fill the missing values of double /
+    float columns with the mean or the median of the others.  Null and ``missingValue`` (default
+    NaN) are missing; NaN never counts towards a surrogate.  The median is the exact order
+    statistic of rank ``ceil(n / 2)`` (one ``kernels.quantiles`` call for all the columns; Spark
+    takes ``approxQuantile(0.5, 0.001)``), the mean a masked sum on the table's device; on a
+    sharded frame both are reduced over the ranks."""
+
+    uid_prefix = "imputer"
+
+    def __init__(self, inputCols=None, outputCols=None, strategy=None, missingValue=None, uid=None):
+        super().__init__(uid)
+        if inputCols is not None:
+            self.setInputCols(inputCols)
+        if outputCols is not None:
+            self.setOutputCols(outputCols)
+        if strategy is not None:
+            self.setStrategy(strategy)
+        if missingValue is not None:
+            self.setMissingValue(missingValue)
+
+    def fit(self, df: DataFrame) -> "ImputerModel":
+        from ..sql.plan import is_sharded
+        from ..sql.stat import column_quantiles
+
+        ins, _ = self._io_cols(df.schema)
+        mv = float(self.getOrDefault("missingValue"))
+        t = df._table()
+        cols = [t.column(c) for c in ins]
+        # valid, and not the placeholder, compared in double as transform's `x = missingValue` does
+        # (a float 0.1f is not the double 0.1); NaN is dropped by the reductions themselves
+        def _not_mv(c):
+            keep = c.values.to(torch.float64) != mv
+            return keep if c.valid is None else c.valid & keep
+        valids = [c.valid if _is_nan(mv) else _not_mv(c) for c in cols]
+        if self.getOrDefault("strategy") == "median":
+            values, counts = column_quantiles(df, ins, [0.5], valids)
+            surrogates = [float(v) for v in values[:, 0]]
+        else:
+            live = t.sel_mask()
+            acc = []
+            for c, v in zip(cols, valids):
+                x = c.values.to(torch.float64)
+                m = live & ~torch.isnan(x)
+                if v is not None:
+                    m = m & v
+                acc += [torch.where(m, x, torch.zeros_like(x)).sum(), m.sum().to(torch.float64)]
+            acc = torch.stack(acc)
+            if is_sharded(df._plan):
+                from ..parallel import comm
+
+                acc = comm.all_reduce_sum(acc)
+            acc = acc.cpu().tolist()  # the one host read
+            counts = [int(n) for n in acc[1::2]]
+            surrogates = [s / n if n else float("nan") for s, n in zip(acc[0::2], acc[1::2])]
+        empty = [c for c, n in zip(ins, counts) if n == 0]
+        if empty:
+            raise SparkException(f"surrogate cannot be computed. All the values in {','.join(empty)} are Null, Nan or "
+                                 f"missingValue({mv})")
+        return self.copyValues(ImputerModel(dict(zip(ins, surrogates)), df.sparkSession, uid=self.uid))
+
+
+@param_accessors
+class ImputerModel(_ImputerParams):
+    """Fitted :class:`Imputer`.  ``surrogateDF``: one row, one double column per input column."""
+
+    uid_prefix = "imputer"
+
+    def __init__(self, surrogates: dict, session=None, uid=None):
+        super().__init__(uid)
+        self.surrogates = dict(surrogates)
+        self._session = session
+
+    @property
+    def surrogateDF(self) -> DataFrame:
+        from ..sql.stat import replicated_frame
+        from ..sql.types import StructField, StructType
+
+        names = list(self.surrogates)
+        schema = StructType([StructField(n, DoubleType(), False) for n in names])
+        return replicated_frame(self._session, [tuple(self.surrogates[n] for n in names)], schema)
+
+    def transform(self, df: DataFrame) -> DataFrame:
+        """Every output column as the lazy expression ``if(x is null or x = missingValue,
+        surrogate, x)`` (Spark's NaN = NaN equality covers the default placeholder), so it fuses
+        with the DQ rules and filters around it."""
+        from ..sql.column import Column
+        from ..sql.expressions import Cast, If, IsNull, Lit
+
+        ins, outs = self._io_cols(df.schema)
+        mv = float(self.getOrDefault("missingValue"))
+        for i, o in zip(ins, outs):
+            x = ColRef(i)
+            e = If(BinOp("or", IsNull(x), BinOp("=", x, Lit(mv))), Lit(float(self.surrogates[i])), x)
+            if isinstance(x.data_type(df.schema), FloatType):
+                e = Cast(e, "float")
+            df = df.withColumn(o, Column(e))
+        return df
 
 
 class _SchemaOnly:

@@ -14,6 +14,7 @@
 #include "dqvm.h"
 #include "gram.h"
 #include "gram_folds.h"
+#include "quantile.h"
 #include "gram_wide.h"
 #include "gram_syrk.h"
 #include "wls_small.h"
@@ -209,6 +210,36 @@ PYBIND11_MODULE(_dq4ml_hip, m) {
   m.def("fold_ids", [fold_rule](int64_t n, int64_t granule, const std::vector<uint32_t>& thr, uint64_t seed,
                                 uintptr_t out, uintptr_t stream) {
     fold_ids(n, granule, fold_rule(thr, seed), P<uint8_t>(out), as_stream(stream));
+  });
+  m.def("quantile_blocks", &quantile_blocks);
+  m.def("quantile_limits", []() { return py::make_tuple(kMaxQuantiles, kMaxQuantCols, kQuantPasses, kQuantBins); });
+  auto quant_cols = [](const std::vector<uintptr_t>& cols, const std::vector<int>& dts,
+                       const std::vector<uintptr_t>& valids, uintptr_t sel, int64_t n, int Q) {
+    if (cols.empty() || cols.size() > (size_t)kMaxQuantCols || cols.size() != dts.size() || cols.size() != valids.size())
+      throw std::invalid_argument("quantiles: between 1 and " + std::to_string(kMaxQuantCols) +
+                                  " columns per launch, one dtype and one validity pointer each");
+    QuantCols a{};
+    for (size_t c = 0; c < cols.size(); ++c) {
+      a.col[c] = P<const void>(cols[c]);
+      a.valid[c] = P<const uint8_t>(valids[c]);
+      a.dt[c] = dts[c];
+    }
+    a.sel = P<const uint8_t>(sel);
+    a.n = n;
+    a.C = (int)cols.size();
+    a.Q = Q;
+    return a;
+  };
+  m.def("quantile_hist", [quant_cols](const std::vector<uintptr_t>& cols, const std::vector<int>& dts,
+                                      const std::vector<uintptr_t>& valids, uintptr_t sel, int64_t n, int Q, int pass,
+                                      uintptr_t state, uintptr_t hist, int blocks, uintptr_t stream) {
+    quantile_hist(quant_cols(cols, dts, valids, sel, n, Q), pass, P<const int64_t>(state),
+                  P<unsigned long long>(hist), blocks, as_stream(stream));
+  });
+  m.def("quantile_pick", [](int C, int Q, int pass, uintptr_t probs, uintptr_t state, uintptr_t hist, uintptr_t values,
+                            uintptr_t counts, uintptr_t stream) {
+    quantile_pick(C, Q, pass, P<const double>(probs), P<int64_t>(state), P<unsigned long long>(hist),
+                  P<double>(values), P<int64_t>(counts), as_stream(stream));
   });
   m.def("gram_window_fold", [](uintptr_t part, int64_t rows, int gw, uintptr_t flat, uintptr_t stream) {
     gram_window_fold(P<const double>(part), rows, gw, P<double>(flat), as_stream(stream));

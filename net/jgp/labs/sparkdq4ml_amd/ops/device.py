@@ -19,7 +19,7 @@ from ..runtime import faststream
 from . import native
 
 __all__ = ["dtype_code", "gram_stats", "compact_indices", "pack_columns", "predict", "regression_metrics",
-           "GRAM_MODES"]
+           "GRAM_MODES", "quantiles"]
 
 _DT = {torch.float64: 0, torch.float32: 1, torch.bfloat16: 2, torch.int32: 3, torch.int64: 4, torch.uint8: 5,
        torch.bool: 5, torch.float16: 6}
@@ -357,6 +357,82 @@ def gram_stats_folds(X, y, sel, k_or_weights, seed: int, granule: int, compute: 
     h.gram_folds(Xv.data_ptr(), int(ld), d, n, dtype_code(Xv), y.data_ptr(), dtype_code(y), _ptr(sel),
                  [int(t) for t in thr], int(seed64), partials.data_ptr(), nb, out.data_ptr(), _stream())
     return out
+
+
+# ------------------------------------------------------------------------------------------
+# exact quantiles: radix select (csrc/hip/quantile.hip)
+# ------------------------------------------------------------------------------------------
+_QUANT_DTYPES = (torch.float64, torch.float32, torch.int32, torch.int64)
+
+
+def _mask_u8(m: Optional[torch.Tensor], n: int, what: str) -> Optional[torch.Tensor]:
+    if m is None:
+        return None
+    if m.numel() != n or m.dim() != 1:
+        raise ValueError(f"quantiles: {what} must have one entry per row")
+    if m.dtype not in (torch.bool, torch.uint8):
+        m = m != 0
+    return m.contiguous()
+
+
+def quantiles(cols, valids, sel, probs, blocks: Optional[int] = None, reduce=None):
+    """Exact order statistics of ``cols`` (1-D f64 / f32 / i32 / i64 device tensors of one length)
+    at ``probs``: ``(values [C, Q] f64, counts [C] i64)``, both on the device.  A row counts for
+    column c when ``sel`` (optional, shared) and ``valids[c]`` (optional) are set and its value is
+    not NaN; ``values`` is NaN where no row counts.  Target rank: p = 0 the minimum, p = 1 the
+    maximum, else ``ceil(p * n)`` (1-based).  Every pass is enqueued on the current stream with no
+    host read; ``reduce`` (histogram tensor -> summed tensor) runs between each histogram pass
+    and its pick, which is where a data-parallel caller all-reduces the int64 counters."""
+    h = native.hip()
+    max_q, max_c, passes, bins = h.quantile_limits()
+    from . import kernels
+
+    assert (max_q, bins) == (kernels.MAX_QUANTILES, 1 << kernels.QUANT_BITS), "kernels.py / quantile.h constants differ"
+    cols = list(cols)
+    if not cols:
+        raise ValueError("quantiles: no column")
+    valids = [None] * len(cols) if valids is None else list(valids)
+    if len(valids) != len(cols):
+        raise ValueError("quantiles: one validity mask (or None) per column")
+    p = np.asarray(probs, dtype=np.float64).reshape(-1)
+    Q = int(p.size)
+    if not 1 <= Q <= max_q:
+        raise ValueError(f"quantiles: between 1 and {max_q} probabilities per call, got {Q}")
+    if not np.all((p >= 0.0) & (p <= 1.0)):
+        raise ValueError("quantiles: probabilities must lie in [0, 1]")
+    _check_dev(*cols, *valids, sel)
+    n = int(cols[0].numel())
+    for c in cols:
+        if c.dim() != 1 or int(c.numel()) != n:
+            raise ValueError("quantiles: columns must be 1-D and of one length")
+        if c.dtype not in _QUANT_DTYPES:
+            raise TypeError(f"quantiles: unsupported column dtype {c.dtype}")
+    if len(cols) > max_c:  # the kernel takes its column table by value: chunk
+        vs, ns = zip(*(quantiles(cols[i:i + max_c], valids[i:i + max_c], sel, p, blocks, reduce)
+                       for i in range(0, len(cols), max_c)))
+        return torch.cat(vs), torch.cat(ns)
+    dev = cols[0].device
+    cols = [c.contiguous() for c in cols]
+    valids = [_mask_u8(v, n, "a validity mask") for v in valids]
+    sel = _mask_u8(sel, n, "the selection")
+    C = len(cols)
+    nb = int(blocks) if blocks else int(h.quantile_blocks(n))
+    probs_d = _h2d(p, dev)
+    hist = torch.zeros(C, Q, bins, dtype=torch.int64, device=dev)
+    state = torch.zeros(C, 2 + 3 * Q, dtype=torch.int64, device=dev)
+    values = torch.empty(C, Q, dtype=torch.float64, device=dev)
+    counts = torch.empty(C, dtype=torch.int64, device=dev)
+    cp, dt, vp = [c.data_ptr() for c in cols], [dtype_code(c) for c in cols], [_ptr(v) for v in valids]
+    st = _stream()
+    for k in range(passes):
+        h.quantile_hist(cp, dt, vp, _ptr(sel), n, Q, k, state.data_ptr(), hist.data_ptr(), nb, st)
+        if reduce is not None:
+            r = reduce(hist)
+            if r is not hist:
+                hist.copy_(r)
+        h.quantile_pick(C, Q, k, probs_d.data_ptr(), state.data_ptr(), hist.data_ptr(), values.data_ptr(),
+                        counts.data_ptr(), st)
+    return values, counts
 
 
 def gram_skinny_cols(parts: List[torch.Tensor], y, w, sel, blocks: Optional[int] = None):

@@ -9,6 +9,7 @@ Ops:
   K3  ``selected_indices``   stream compaction of a selection vector
   K4  ``pack_columns``       columns -> feature-major [d, n] matrix (cast)
   K5  ``gram_stats``         WLS sufficient statistics (MFMA Gram) of [X | 1 | y] with weights/mask
+  K5q ``quantiles``          exact order statistics of C columns x Q probabilities (radix select)
   K7+K8 ``predict`` / ``regression_metrics``  fused GEMV + metric reductions
 """
 from __future__ import annotations
@@ -21,7 +22,7 @@ import torch
 from . import native
 
 __all__ = ["selected_indices", "pack_columns", "gram_stats", "predict", "regression_metrics",
-           "gram_layout_size", "gram_stats_folds", "fold_ids", "fold_thresholds", "fold_seed"]
+           "gram_layout_size", "gram_stats_folds", "fold_ids", "fold_thresholds", "fold_seed", "quantiles"]
 
 
 def _on_gpu(t: torch.Tensor) -> bool:
@@ -259,6 +260,127 @@ def gram_stats_folds(X: torch.Tensor, y: torch.Tensor, sel: Optional[torch.Tenso
         m = live & (ids == f)
         out[f] = gram_stats(Xd, yd, None, m, "fp64")
     return out
+
+
+# ------------------------------------------------------------------------------------------
+# K5q — exact quantiles (radix select over order-preserving 64-bit keys)
+# ------------------------------------------------------------------------------------------
+MAX_QUANTILES = 16
+QUANT_BITS = 8  # digit width of the select: 64 / 8 = 8 histogram passes
+_QUANT_BINS = 1 << QUANT_BITS
+_QUANT_PASSES = 64 // QUANT_BITS
+_SIGN = np.uint64(1 << 63)
+
+
+def quantile_keys(x: np.ndarray) -> np.ndarray:
+    """uint64 keys of non-NaN doubles whose unsigned order is the numeric order: -0.0 folded into
+    +0.0, IEEE bits, negative values flip every bit, the others the sign bit."""
+    b = (np.asarray(x, dtype=np.float64) + 0.0).view(np.uint64)
+    return np.where((b & _SIGN) != 0, ~b, b | _SIGN)
+
+
+def quantile_unkey(k: int) -> float:
+    k = int(k)
+    b = (k ^ (1 << 63)) if k >> 63 else (~k & _M64)
+    return float(np.array([b], dtype=np.uint64).view(np.float64)[0])
+
+
+def quantile_rank(p: float, n: int) -> int:
+    """1-based target rank of probability ``p`` among ``n`` values, as Spark's
+    ``QuantileSummaries.query`` ranks an exact summary: the minimum for p = 0, the maximum for
+    p = 1, else ``ceil(p * n)`` of one double multiply."""
+    if p <= 0.0:
+        return min(1, n)
+    if p >= 1.0:
+        return n
+    return min(max(1, int(np.ceil(np.float64(p) * np.float64(n)))), n)
+
+
+def _quantiles_host(cols, valids, sel, probs: np.ndarray, reduce):
+    """The device algorithm in numpy: same keys, digits, slot sharing, rank rule and ``reduce``
+    hook (the CPU engine and the gloo path)."""
+    C, Q = len(cols), int(probs.size)
+    live_sel = None if sel is None else sel.numpy().astype(bool)
+    keys = []
+    for c, v in zip(cols, valids):
+        x = c.numpy().astype(np.float64)
+        m = ~np.isnan(x)
+        if v is not None:
+            m &= v.numpy().astype(bool)
+        if live_sel is not None:
+            m &= live_sel
+        keys.append(quantile_keys(x[m]))
+    upref = [[0] for _ in range(C)]  # prefix of slot u
+    slot = [[0] * Q for _ in range(C)]  # slot of target q
+    rank = [[0] * Q for _ in range(C)]
+    counts = [0] * C
+    for k in range(_QUANT_PASSES):
+        dshift = np.uint64(64 - QUANT_BITS * (k + 1))
+        hist = np.zeros((C, Q, _QUANT_BINS), dtype=np.int64)
+        for c in range(C):
+            hi = keys[c] >> np.uint64(64 - QUANT_BITS * k) if k > 0 else None
+            keep = np.zeros(keys[c].size, dtype=bool)
+            for u, pref in enumerate(upref[c]):
+                m = np.ones(keys[c].size, dtype=bool) if hi is None else hi == np.uint64(pref)
+                keep |= m
+                d = ((keys[c][m] >> dshift) & np.uint64(_QUANT_BINS - 1)).astype(np.int64)
+                hist[c, u] = np.bincount(d, minlength=_QUANT_BINS)
+            keys[c] = keys[c][keep]  # a key outside every prefix never matches again
+        if reduce is not None:
+            hist = reduce(torch.from_numpy(hist)).numpy()
+        for c in range(C):
+            if k == 0:
+                counts[c] = int(hist[c, 0].sum())
+                rank[c] = [quantile_rank(float(p), counts[c]) for p in probs]
+            npref, nrank = [], []
+            for q in range(Q):
+                cum = np.cumsum(hist[c, slot[c][q]])
+                if counts[c] == 0:
+                    npref.append(0), nrank.append(0)
+                    continue
+                d = int(np.searchsorted(cum, rank[c][q], side="left"))
+                npref.append((upref[c][slot[c][q]] << QUANT_BITS) | d)
+                nrank.append(rank[c][q] - int(cum[d - 1] if d else 0))
+            upref[c] = []
+            for q in range(Q):
+                if npref[q] not in upref[c]:
+                    upref[c].append(npref[q])
+                slot[c][q] = upref[c].index(npref[q])
+            rank[c] = nrank
+    values = np.array([[quantile_unkey(upref[c][slot[c][q]]) if counts[c] else np.nan for q in range(Q)]
+                       for c in range(C)], dtype=np.float64).reshape(C, Q)
+    return torch.from_numpy(values), torch.tensor(counts, dtype=torch.int64)
+
+
+def quantiles(cols: Sequence[torch.Tensor], valids, sel: Optional[torch.Tensor], probs, blocks: Optional[int] = None,
+              reduce=None):
+    """Exact order statistics ``(values [C, Q] f64, counts [C] i64)`` of 1-D f64 / f32 / i32 / i64
+    columns at the probabilities ``probs`` (at most ``MAX_QUANTILES``).  A row counts for column c
+    when ``sel`` and ``valids[c]`` (each optional) are set and the value, cast to double, is not
+    NaN.  The order statistic of p is the minimum for p = 0, the maximum for p = 1, else the
+    ``ceil(p * n)``-th smallest; a column with no counted row gives NaN and count 0.  ``reduce``
+    sums the per-pass int64 histogram over ranks.  Device tensors: the ``quantile`` kernels; host
+    tensors: the same select in numpy."""
+    cols = list(cols)
+    if cols and _on_gpu(cols[0]):
+        from . import device
+
+        return device.quantiles(cols, valids, sel, probs, blocks=blocks, reduce=reduce)
+    if not cols:
+        raise ValueError("quantiles: no column")
+    p = np.asarray(probs, dtype=np.float64).reshape(-1)
+    if not 1 <= p.size <= MAX_QUANTILES:
+        raise ValueError(f"quantiles: between 1 and {MAX_QUANTILES} probabilities per call, got {p.size}")
+    if not np.all((p >= 0.0) & (p <= 1.0)):
+        raise ValueError("quantiles: probabilities must lie in [0, 1]")
+    valids = [None] * len(cols) if valids is None else list(valids)
+    n = int(cols[0].numel())
+    for c in cols:
+        if c.dim() != 1 or int(c.numel()) != n:
+            raise ValueError("quantiles: columns must be 1-D and of one length")
+        if c.dtype not in (torch.float64, torch.float32, torch.int32, torch.int64):
+            raise TypeError(f"quantiles: unsupported column dtype {c.dtype}")
+    return _quantiles_host(cols, valids, sel, p, reduce)
 
 
 # ------------------------------------------------------------------------------------------

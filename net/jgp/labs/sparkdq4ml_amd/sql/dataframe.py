@@ -482,6 +482,28 @@ class DataFrame:
         return describe(self, list(cols) or [f.name for f in self.schema.fields
                                              if not isinstance(f.dataType, VectorUDT)])
 
+    @property
+    def stat(self):
+        from .stat import DataFrameStatFunctions
+
+        return DataFrameStatFunctions(self)
+
+    def approxQuantile(self, col, probabilities, relativeError):
+        """Exact quantiles of numeric columns (``DataFrameStatFunctions.approxQuantile``)."""
+        return self.stat.approxQuantile(col, probabilities, relativeError)
+
+    def summary(self, *statistics):
+        """Spark 2.4's ``summary``: ``describe``'s frame (same shape, same cell formatting) with
+        any of ``count, mean, stddev, min, max`` and percentiles written ``"NN%"`` / ``"NN.N%"``;
+        default ``count, mean, stddev, min, 25%, 50%, 75%, max``.  Percentiles are exact order
+        statistics (``approxQuantile``); those of an integral column print in the column's own
+        type as min and max do, doubles as Java prints them, and a string column gets null
+        percentiles.  Columns that are neither numeric nor string are dropped; an unknown
+        statistic is a ``ValueError``."""
+        from .stat import summary
+
+        return summary(self, statistics)
+
     def createOrReplaceTempView(self, name: str):
         self.sparkSession.catalog._views[name.lower()] = self._plan
 
