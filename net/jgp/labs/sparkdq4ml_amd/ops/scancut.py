@@ -54,6 +54,24 @@ TARGET_PER_CU = 4   # resident blocks per CU the LDS budget aims at
 STATS = {"cut_grams": 0}
 LAST_STAMPS: dict = {}  # diagnostic phase clocks of the last launch (DQ4ML_CUT_STAMPS=1)
 
+# The macro prelude of the cutter kernel, ahead of ``scanfuse.header_text()``: csv_parse_dev.h's
+# primitives as the gfx950 builtins (the header's portable forms serve the host check)
+PRELUDE = ("#define CSV_UDOT4(a, b, c) __builtin_amdgcn_udot4((a), (b), (c), false)\n"
+           "#define CSV_MUL24(a, b) __umul24((a), (b))\n"
+           "#define CSV_ALIGNBIT(a, b, s) __builtin_amdgcn_alignbit((a), (b), (s))\n"
+           "#define CSV_PERM(a, b, s) __builtin_amdgcn_perm((a), (b), (s))\n"
+           "#define CSV_OPAQUE(x) asm(\"\" : \"+v\"(x))\n")
+# The converter's power-of-ten pair in LDS (kernel body text; ``tid`` = threadIdx.x, a barrier
+# follows before the first conversion)
+P10_TABLE = """  __shared__ double p10t[16], ip10t[16];  // 10^k and RN(10^-k) for the converter (k > 9: unused)
+  if (tid < 16) {
+    p10t[tid] = tid <= 9 ? csv_pow10(tid) : 1.0;
+    ip10t[tid] = tid <= 9 ? csv_inv_pow10(tid) : 1.0;
+  }
+"""
+# the converter's quotient from that table (both converters give fr <= 15)
+DIV_EXPR = "csv_div_pow10_fma((double)m, p10t[fr], ip10t[fr])"
+
 
 def head_for(max_line: int) -> int:
     """Staged head: a power of two >= the longest line + 32 bytes, in [256, 4096] (None above)."""
@@ -194,7 +212,8 @@ class _Shape:
 
 def _valu_gram(sh, slots):
     """4 x 4 f64 register blocks of the upper augmented Gram per thread, rows of the tile in
-    row groups (VALU FMAs; any d)."""
+    row groups (VALU FMAs; any d: one block per thread while the U blocks fit the 256 threads,
+    else ceil(U / 256) blocks per thread)."""
     d, PP, NB, U, RG, GW = sh.d, sh.PP, sh.NB, sh.U, sh.RG, sh.gw
     acc_decl = "  double acc[16];\n#pragma unroll\n  for (int k = 0; k < 16; ++k) acc[k] = 0.0;\n"
     acc_decl += f"""  const int gu = tid % {U}, grg = tid / {U};
@@ -236,6 +255,56 @@ for (int k = 0; k < 16; ++k) {{
   }}
 """
     tables = f"__device__ const short DQ_GIDX[{U * 16}] = {{{', '.join(str(x) for x in idx_tab)}}};\n"
+    if U > 256:
+        # more blocks than threads (d + 2 > 88): thread t owns blocks t, t + 256, ... (KB of them,
+        # 16 accumulators each) over every row of the tile.  (One block per thread left the blocks
+        # from 256 on -- the count, the label sums and the later columns -- unwritten.)  A thread
+        # past the last block repeats block 0 and writes nothing.
+        KB = -(-U // 256)
+        assert RG == 1
+        acc_decl = f"""  double acc[{16 * KB}];
+#pragma unroll
+  for (int k = 0; k < {16 * KB}; ++k) acc[k] = 0.0;
+  const int grg = 0;
+  int gbi[{KB}], gbj[{KB}];
+  bool gon[{KB}];
+#pragma unroll
+  for (int k = 0; k < {KB}; ++k) {{
+    gon[k] = tid + 256 * k < {U};
+    int bi = 0, brem = gon[k] ? tid + 256 * k : 0;
+    while (brem >= {NB} - bi) {{ brem -= {NB} - bi; ++bi; }}
+    gbi[k] = bi;
+    gbj[k] = bi + brem;
+  }}
+"""
+        gram_phase = f"""    for (int r = 0; r < nr; ++r) {{
+      const double* __restrict__ gr = gt + r * {PP};
+#pragma unroll
+      for (int k = 0; k < {KB}; ++k) {{
+        const f64x2 a01 = *reinterpret_cast<const f64x2*>(gr + 4 * gbi[k]), a23 = *reinterpret_cast<const f64x2*>(gr + 4 * gbi[k] + 2);
+        const f64x2 b01 = *reinterpret_cast<const f64x2*>(gr + 4 * gbj[k]), b23 = *reinterpret_cast<const f64x2*>(gr + 4 * gbj[k] + 2);
+        const double av[4] = {{a01[0], a01[1], a23[0], a23[1]}}, bv[4] = {{b01[0], b01[1], b23[0], b23[1]}};
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+          for (int v = 0; v < 4; ++v) acc[16 * k + 4 * u + v] = __builtin_fma(av[u], bv[v], acc[16 * k + 4 * u + v]);
+      }}
+    }}
+"""
+        epilogue = f"""  {{
+    DQG double* __restrict__ gp = (DQG double*)p[{slots['gpart']}] + (long long)blockIdx.x * {GW};
+#pragma unroll
+    for (int k = 0; k < {KB}; ++k) {{
+      if (gon[k]) {{
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {{
+          const int slot = DQ_GIDX[(tid + 256 * k) * 16 + e];
+          if (slot >= 0) gp[slot] = acc[16 * k + e];
+        }}
+      }}
+    }}
+  }}
+"""
     return acc_decl, gram_phase, epilogue, tables
 
 
@@ -497,7 +566,7 @@ def kernel_source(g, kinds, used, opts: dict, H: int, slots: dict, d: int, term:
         "true" if not ints else "csv_conforms(dot ? C_DOUBLE : C_INT, DQ_KIND[c])")
     # the quotient's power-of-ten pair from an LDS table (the VALU select chain measured slower:
     # profiles/r3_csv_cutter.md)
-    div_expr = "csv_div_pow10_fma((double)m, p10t[fr], ip10t[fr])"  # (both converters give fr <= 15)
+    div_expr = DIV_EXPR
     if abl & 16:  # (diagnostic) no table read: the quotient's LDS round trip
         div_expr = "csv_div_pow10_fma((double)m, 1.0 + fr, 1.0)"
     frame_load = ("const unsigned fw0 = fwp[0], fw1 = fwp[1], fw2 = fwp[2];\n        const int c0 = stage[start];"
@@ -660,11 +729,7 @@ def kernel_source(g, kinds, used, opts: dict, H: int, slots: dict, d: int, term:
         delim_body = f"  return dq_eq80(v, {sep4}) | dq_eq80(v, {term4});"
     kind_tab = ", ".join(str(int(k)) for k in kinds)
     lb = f"__launch_bounds__(256, {waves_per_simd})" if waves_per_simd else "__launch_bounds__(256)"
-    src = ("#define CSV_UDOT4(a, b, c) __builtin_amdgcn_udot4((a), (b), (c), false)\n"
-           "#define CSV_MUL24(a, b) __umul24((a), (b))\n"
-           "#define CSV_ALIGNBIT(a, b, s) __builtin_amdgcn_alignbit((a), (b), (s))\n"
-           "#define CSV_PERM(a, b, s) __builtin_amdgcn_perm((a), (b), (s))\n"
-           "#define CSV_OPAQUE(x) asm(\"\" : \"+v\"(x))\n") + header_text() + f"""
+    src = PRELUDE + header_text() + f"""
 using namespace dq4ml_csv;
 typedef unsigned int csv_u32x4 __attribute__((ext_vector_type(4)));
 typedef double f64x2 __attribute__((ext_vector_type(2)));
@@ -751,12 +816,7 @@ __device__ __forceinline__ void dq_fetch(const DQG unsigned char* ab, long long 
   const CsvOpts O = {o};
   bool bad = false;
 {stamp_decl}  for (int i = tid; i < {2 * C}; i += 256) ctab[i] = DQ_CTAB[i];
-  __shared__ double p10t[16], ip10t[16];  // 10^k and RN(10^-k) for the converter (k > 9: unused)
-  if (tid < 16) {{
-    p10t[tid] = tid <= 9 ? csv_pow10(tid) : 1.0;
-    ip10t[tid] = tid <= 9 ? csv_inv_pow10(tid) : 1.0;
-  }}
-{acc_decl}{gt_init}
+{P10_TABLE}{acc_decl}{gt_init}
   // a CONTIGUOUS run of windows per block: the row start of window k+1 is carried from the cut
   // of window k (only the first window searches back for it), and window k+1's bytes are in
   // flight (registers) while window k is cut

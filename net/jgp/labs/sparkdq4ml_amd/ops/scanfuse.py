@@ -59,6 +59,19 @@ def header_text() -> str:
     return _header_text
 
 
+# the SWAR converter's LDS table filled at kernel start (kernel body text; a barrier follows)
+P10_INIT = ("  if (threadIdx.x < 16) dq_p10[threadIdx.x] = threadIdx.x < 8 ? dq4ml_csv::csv_pow10(threadIdx.x)\n"
+            "                                                       : dq4ml_csv::csv_inv_pow10(threadIdx.x - 8);\n")
+
+
+def prelude(p10_lds: bool) -> str:
+    """The macro prelude of the per-line kernel, ahead of ``header_text()``: the digit combine's
+    gfx950 builtins and, with ``p10_lds``, the SWAR converter's power-of-ten table in LDS."""
+    p10_decl = "__shared__ double dq_p10[16];\n#define CSV_P10_TAB dq_p10\n" if p10_lds else ""
+    return ("#define CSV_UDOT4(a, b, c) __builtin_amdgcn_udot4((a), (b), (c), false)\n"
+            "#define CSV_MUL24(a, b) __umul24((a), (b))\n" + p10_decl)
+
+
 def head_bytes(mean_line: float) -> int:
     """LDS head region: the part of the line that straddles into the window — 4x the mean line
     length, a power of two in [256, 2048].  A longer straddling line parses from global memory."""
@@ -363,12 +376,8 @@ __device__ __forceinline__ void dq_row_swar(const unsigned char* B, int start, i
     # 10^k / RN(10^-k) for the SWAR converter's decimals: an LDS table (one ds_read2_b64) or VALU
     # selects and products (DQ4ML_SCAN_P10=valu); the kernel is VALU-issue-bound
     p10_lds = swar and os.environ.get("DQ4ML_SCAN_P10", "lds") == "lds"
-    p10_decl = ("__shared__ double dq_p10[16];\n#define CSV_P10_TAB dq_p10\n" if p10_lds else "")
-    p10_init = ("  if (threadIdx.x < 16) dq_p10[threadIdx.x] = threadIdx.x < 8 ? dq4ml_csv::csv_pow10(threadIdx.x)\n"
-                "                                                       : dq4ml_csv::csv_inv_pow10(threadIdx.x - 8);\n"
-                if p10_lds else "")
-    return ("#define CSV_UDOT4(a, b, c) __builtin_amdgcn_udot4((a), (b), (c), false)\n"
-            "#define CSV_MUL24(a, b) __umul24((a), (b))\n" + p10_decl + header_text() + f"""
+    p10_init = P10_INIT if p10_lds else ""
+    return (prelude(p10_lds) + header_text() + f"""
 using namespace dq4ml_csv;
 typedef unsigned int csv_u32x4 __attribute__((ext_vector_type(4)));
 // every global access names the global address space: generic (flat) accesses count in both

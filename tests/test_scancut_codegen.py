@@ -57,7 +57,9 @@ def test_tile_slot_map_covers_layout_once(d):
     assert scancut._tile_slot(sh, d, d + 1) == 1 and scancut._tile_slot(sh, 0, d) == 3 + d  # Σy, Σx0y
 
 
-def _cut_source(spark, d, lab, stamps=False, quoted=False, max_line=None):
+def _cut_source(spark, d, lab, stamps=False, quoted=False, max_line=None, shape=None, want_shape=False):
+    """``shape`` (a ``_cut_cases.Shape``): its column kinds, feature subset, label column and
+    terminator, with the line-length facts of its pools (1-byte to 11-byte fields)."""
     import torch
 
     from net.jgp.labs.sparkdq4ml_amd.ops.csvscan import _opt_args
@@ -68,12 +70,21 @@ def _cut_source(spark, d, lab, stamps=False, quoted=False, max_line=None):
 
     ncol = 2 if lab else d + 1
     kinds = [1, 0] if lab else [0] * ncol
+    term, crlf, ycol = 13, False, d
+    if shape is not None:
+        ncol, d, ycol = shape.C, shape.d, shape.label
+        kinds = [1 if k == "i" else 0 for k in shape.kinds]
+        term, crlf = (10 if shape.term == b"\n" else 13), shape.term == b"\r\n"
     schema = StructType([StructField(f"_c{i}", IntegerType() if k == 1 else DoubleType(), True)
                          for i, k in enumerate(kinds)])
     fused = {"kinds": kinds, "nullable": [False] * ncol, "strict": False, "fast_only": True, "empty_lines": 0,
              "uniform_fields": True, "max_line": max_line or (10 if lab else 11 * ncol), "device": torch.device("cpu"),
-             "min_line": 6 if lab else 9 * ncol, "term_kinds": [100, 0, 0],
+             "min_line": 6 if lab else 9 * ncol,
+             "term_kinds": [100, 0, 0] if term == 13 and not crlf else ([0, 100, 0] if term == 10 else [100, 0, 100]),
              "opts": dict(_opt_args({"comment": 0}), sep=",", strict=False)}
+    if shape is not None:
+        fused["min_line"] = 2 * ncol - 1
+        fused["max_line"] = ncol - 1 + (ncol if shape.name == "ones" else sum(10 if k else 11 for k in kinds))
     rel = CsvScanRelation(schema, lambda: None, fused, "Relation[csv]")
     df = DataFrame(rel, spark)
     if lab:
@@ -89,9 +100,9 @@ def _cut_source(spark, d, lab, stamps=False, quoted=False, max_line=None):
         inputs = ["guest"]
     else:
         spark.udf().register("rangeRule", RangeRule(0.0, 150.0, name="rangeRule"), DataTypes.DoubleType)
-        df = df.withColumn("y_ok", callUDF("rangeRule", col(f"_c{d}"))).filter(col("y_ok") > 0)
+        df = df.withColumn("y_ok", callUDF("rangeRule", col(f"_c{ycol}"))).filter(col("y_ok") > 0)
         df = df.withColumn("label", col("y_ok"))
-        inputs = [f"_c{i}" for i in range(d)]
+        inputs = [f"_c{i}" for i in (range(d) if shape is None else shape.feats)]
     df = VectorAssembler().setInputCols(inputs).setOutputCol("features").transform(df)
     plan = prune_columns(df._plan, {"label", "features"})
     nodes, p = [], plan
@@ -109,12 +120,12 @@ def _cut_source(spark, d, lab, stamps=False, quoted=False, max_line=None):
     _, g, _, _ = dqvm.compile_chain(chain, base, False, gen=g)
     slots = {k: g.slot(None, (k,)) for k in ("buf", "nwin", "trailing", "vflag", "gpart") + (("dbg",) if stamps else ())}
     ml = fused["max_line"]
-    src, sh = scancut.kernel_source(g, kinds, g.used, fused["opts"], H, slots, d, 13, False, fused["min_line"],
+    src, sh = scancut.kernel_source(g, kinds, g.used, fused["opts"], H, slots, d, term, crlf, fused["min_line"],
                                     scancut.blocks_per_cu(scancut.kernel_source(g, kinds, g.used, fused["opts"], H,
-                                                                                slots, d, 13, False,
+                                                                                slots, d, term, crlf,
                                                                                 fused["min_line"], 0, ml, quoted)[1].lds),
                                     ml, quoted)
-    return src
+    return (src, sh) if want_shape else src
 
 
 @pytest.mark.parametrize("d,lab,stamps,quoted", [(1, True, False, False), (12, False, False, False),
@@ -130,6 +141,50 @@ def test_cut_kernel_compiles_for_gfx950(cpu_session, tmp_path, monkeypatch, d, l
     assert ("DQ_TIDX" in src) == (d > 8)  # the MFMA Gram of the row tile
     assert ("csv_num_r<2>(stage, end" in src) == lab  # 8-byte converter frame for the lab's short fields
     assert ("gt[q_ga] = dv;" in src) == (d > 8)  # every column stored straight into its row-tile slot
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("no hipcc")
+    f = tmp_path / "cut.hip"
+    f.write_text("#include <hip/hip_runtime.h>\n" + src)
+    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-c", str(f), "-o", str(tmp_path / "c.o")],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-4000:]
+
+
+@pytest.mark.parametrize("name", ["d32", "sub12", "sub12i", "d3of40", "d9of200", "d80", "d100", "d128", "ones", "d32c", "d100c"])
+def test_field_test_shapes_compile_for_gfx950(cpu_session, tmp_path, name):
+    """Every kernel shape tests/test_gpu_scancut_fields.py launches, generated from the facts its
+    files have, with the source features that tell the code paths apart."""
+    import _cut_cases as cc
+
+    shape = cc.SHAPES[name]
+    src, sh = _cut_source(cpu_session, shape.d, False, shape=shape, want_shape=True)
+    d, subset = shape.d, shape.feats != list(range(shape.d))
+    nint = shape.kinds.count("i")
+    assert ("DQ_TIDX" in src) == (8 < d < 79) and ("DQ_GIDX" in src) == (d >= 79)  # MFMA / VALU blocked Gram
+    assert sh.mfma == (8 < d < 79) and sh.blocked == (d > 8)
+    assert ("gt[q_ga] = dv;" in src) == (not subset and d > 8) and sh.yfirst == (not subset and d > 8)
+    assert sh.vstrip == (sh.yfirst and sh.mfma)
+    if subset and d > 8:  # one store per field through the column table
+        assert "*(fs >= 0 ? gt + q_gb + fs" in src and "ctab[2 * c + 1]" in src
+    if d >= 79:  # every 4 x 4 block of the VALU Gram has a thread: 256 threads x KB blocks cover all U
+        import re
+
+        kb = re.search(r"bool gon\[(\d+)\];", src)
+        assert (kb is not None) == (sh.U > 256)
+        assert sh.U <= 256 * (int(kb.group(1)) if kb else 1) and f"DQ_GIDX[{sh.U * 16}]" in src
+        if kb:
+            assert int(kb.group(1)) == -(-sh.U // 256) and f"tid + 256 * k < {sh.U};" in src and sh.RG == 1
+    assert ("csv_conforms(dot ?" in src) == (nint > 8)
+    assert ("? !dot : true" in src) == (0 < nint <= 8)
+    assert ("const bool hfast = false;" in src) == (sh.H > 1024)
+    if name == "d9of200":
+        assert sh.H == 4096 and sh.HG == 2
+    if name == "ones":
+        assert sh.DCAP == (sh.H + sh.W) // 2 + 64 and "csv_num_r<2>(stage, end" in src
+    else:
+        assert "csv_num_r<4>(stage, end" in src
+    assert ("0x0A0A0A0Au" in src) == (shape.term == b"\n")  # the one terminator byte: LF, else CR
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
         pytest.skip("no hipcc")
