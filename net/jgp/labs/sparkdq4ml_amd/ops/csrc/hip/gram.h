@@ -51,6 +51,12 @@ struct GramArgs {
   // digits through the cast and the f32 accumulators; stats_unshift restores those of x in f64
   // (SURVEY.md §7e.2).  Dead and padding rows stay exactly zero.
   const float* xshift;
+  // tiled storage with a 12-bit packed companion (pack_tiles below; null: none).  xdir[s * NT + t]
+  // is the exponent base of superstep-tile (s, t), or 0xFF where that entry is read raw from X;
+  // xpack holds one 3 KiB slot per entry at (s * NT + t) * 768 dwords.  The directory is word
+  // aligned and allocated in whole 32-bit words (the kernel reads the aligned word around a byte).
+  const uint32_t* xpack;
+  const uint8_t* xdir;
 };
 
 #ifndef __HIPCC_RTC__
@@ -65,6 +71,18 @@ int gram_interleave();
 // shift: per-feature f32 shift subtracted before the bf16 cast (null: none; rows >= n stay zero)
 void tile_bf16(const void* X, int xdt, int64_t ld, int d, int64_t n, void* out, hipStream_t st,
                const float* shift = nullptr);
+
+// Lossless 12-bit companion of the tiled storage (the layout and its torch reference: ops/layout.py
+// pack_reference).  Entry (s, t) is packable iff the 8-bit exponent fields of its 2048 stored
+// values span <= 15 binades (emax - emin <= 15, emin <= 254); then dir = emin and every value is
+// sign + 4-bit exponent offset + 7-bit mantissa.  A lane's fragment of k-step i (8 values = 4
+// dwords R0..R3) becomes 3 dwords D0..D2: Dk keeps the sign (bit 15) and the low 11 code bits of
+// R_k's two halfwords, and bits 14..11 of D0 / D1 / D2 carry code bits 3..0 / 7..4 / sign:10..8 of
+// R3's.  The slot is 3 pieces of 64 lanes x 16 B; piece k holds lane l's D_k of k-steps 0..3.
+// Raw entries (dir 0xFF) have a zero-filled slot.  *npacked (one device word, zeroed by the
+// caller) counts the packed entries.  One wave per entry.
+void pack_tiles(const void* tiles, int d, int64_t n, uint8_t* dir, uint32_t* slots, uint32_t* npacked,
+                hipStream_t st);
 
 int64_t gram_partial_stride(int mode, int d);
 int gram_default_blocks(int64_t n);

@@ -83,6 +83,47 @@ __device__ __forceinline__ RowVals row_vals(const GramArgs& a, int64_t r) {
   return v;
 }
 
+// The label of row r as loaded bits (f32 or f64 labels only), converted where it is used: a load
+// issued a superstep ahead then waits for nothing where it is issued.  row_vals with the label
+// taken from such bits: the same values through the same operations.
+struct LabelBits {
+  uint32_t lo, hi;
+};
+
+__device__ __forceinline__ LabelBits label_bits(const GramArgs& a, int64_t r) {
+  LabelBits b{0u, 0u};
+  if (r < a.n) {
+    if (a.ydt == DT_F64) {
+      const u32x2 v = reinterpret_cast<const u32x2*>(a.y)[r];
+      b.lo = v[0];
+      b.hi = v[1];
+    } else {
+      b.lo = reinterpret_cast<const uint32_t*>(a.y)[r];
+    }
+  }
+  return b;
+}
+
+// (WEIGHTS = false: a.w is null -- no weight load whose wait would also drain the loads in flight)
+template <bool WEIGHTS>
+__device__ __forceinline__ RowVals row_vals(const GramArgs& a, int64_t r, LabelBits b) {
+  RowVals v{false, 0.0, 0.0, 0.0};
+  if (r < a.n) {
+    bool live = a.sel ? (a.sel[r] != 0) : true;
+    if (live) {
+      double w = 1.0;
+      if constexpr (WEIGHTS) w = a.w ? load_as_f64(a.w, a.wdt, r) : 1.0;
+      double y = a.ydt == DT_F64 ? __longlong_as_double(((long long)b.hi << 32) | (long long)b.lo)
+                                 : (double)__uint_as_float(b.lo);
+      v.live = true;
+      v.w = w;
+      v.y = y;
+      v.wy = w * y;
+    }
+  }
+  return v;
+}
+
 struct RowAcc {
   double cnt = 0, ws = 0, wws = 0, bs = 0, bbs = 0;
   __device__ __forceinline__ void add(const RowVals& v) {
@@ -202,12 +243,33 @@ __device__ __forceinline__ void slab_put(double* p, double v) {
   __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// ---- 12-bit packed tiles (gram.h: pack_tiles) -------------------------------------------------
+// One lane's three 16-byte pieces of a packed entry -> its four raw fragments.  B2 = base << 7 in
+// both halfwords; code + B2 <= 0x7FFF per halfword, so the add never reaches a sign bit.
+__device__ __forceinline__ void unpack_tile(const u32x4 (&raw)[4], uint32_t B2, bf16x8 (&fr)[4]) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const uint32_t d0 = raw[0][i], d1 = raw[1][i], d2 = raw[2][i];
+    uint32_t q = (d0 >> 11) & 0x000F000Fu;
+    q |= (d1 >> 7) & 0x00F000F0u;
+    q |= (d2 >> 3) & 0x07000700u;
+    q |= (d2 & 0x40004000u) << 1;
+    u32x4 r;
+    r[0] = (d0 & 0x87FF87FFu) + B2;
+    r[1] = (d1 & 0x87FF87FFu) + B2;
+    r[2] = (d2 & 0x87FF87FFu) + B2;
+    r[3] = q + B2;
+    fr[i] = __builtin_bit_cast(bf16x8, r);
+  }
+}
+
 // =============================================================================================
 // bf16 MFMA kernel
 // =============================================================================================
-template <typename TX, int NT, int XMODE, bool TILED, bool HALF = false>
+template <typename TX, int NT, int XMODE, bool TILED, bool HALF = false, bool PACKED = false>
 __global__ __launch_bounds__((BF16Geom<NT, XMODE, HALF>::kBlock), (BF16Geom<NT, XMODE, HALF>::kMinBlocks)) void
 gram_tall_bf16_kernel(GramArgs a) {
+  static_assert(!PACKED || TILED, "the packed companion belongs to tiled storage");
   typedef BF16Geom<NT, XMODE, HALF> Geo;
   constexpr int NPAIR = NT * (NT + 1) / 2;
   // LDS: per wave 4 cols x 64 rows bf16 (W fragments) + 64 f32 row weights; reused for the
@@ -237,17 +299,19 @@ gram_tall_bf16_kernel(GramArgs a) {
     fp[t] = X + (int64_t)(fvalid[t] ? feat : 0) * a.ld + 32 * h;
   }
 
-  const int64_t gw = (int64_t)blockIdx.x * Geo::kWaves + wave;
+  // (packed: the wave index as a scalar, so the superstep loop and its directory branches are
+  // scalar control flow)
+  const int64_t gw = (int64_t)blockIdx.x * Geo::kWaves + (PACKED ? __builtin_amdgcn_readfirstlane(wave) : wave);
   const int64_t total_waves = (int64_t)gridDim.x * Geo::kWaves;
   int64_t s0 = gw * a.spw;
   int64_t s1 = s0 + a.spw;
   if (s1 > a.nsuper) s1 = a.nsuper;
   const bool do_tail = (gw == total_waves - 1) && (a.n > a.nsuper * 64);
 
-  // One superstep of compute on already-loaded feature fragments.
-  auto compute = [&](int64_t r0, bf16x8 (&fr)[NT][4]) {
+  // One superstep of compute on already-loaded feature fragments (rv: the row scalars of row
+  // r0 + lane).
+  auto compute_rv = [&](const RowVals& rv, bf16x8 (&fr)[NT][4]) {
     // 1) per-row scalars, lane = row
-    RowVals rv = row_vals(a, r0 + lane);
     ra.add(rv);
     {
       const float w_hi = (float)(__bf16)(float)rv.w;
@@ -296,6 +360,7 @@ gram_tall_bf16_kernel(GramArgs a) {
       for (int i = 0; i < 4; ++i) accw[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[t][i], wf[i], accw[t], 0, 0, 0);
     __builtin_amdgcn_wave_barrier();
   };
+  auto compute = [&](int64_t r0, bf16x8 (&fr)[NT][4]) { compute_rv(row_vals(a, r0 + lane), fr); };
   auto load = [&](int64_t r0, int64_t rows_left, bf16x8 (&fr)[NT][4]) {
     if constexpr (TILED) {
       // MFMA-fragment-ordered storage: superstep s, tile t, k-step i = 1 KiB contiguous
@@ -317,6 +382,106 @@ gram_tall_bf16_kernel(GramArgs a) {
     }
   };
 
+  // Packed companion: entry (s, t) is either three 1 KiB pieces of its slot (decoded at the top of
+  // compute, so the packed form is what sits in flight) or today's four loads from the raw tiles.
+  // The directory byte is wave-uniform: pk_dir reads the aligned word around it (a scalar load, so
+  // it shares no counter with the tile loads; the directory is allocated in whole words) a whole
+  // iteration before pk_load branches on it; the byte is cut out of the word only there
+  // (dir_bytes), so the load is not waited for where it is issued.  The label of a superstep is
+  // loaded with its tiles (pk_y) and converted in compute: nothing between two computes waits for
+  // a load issued after the tiles, so the next superstep's loads stay in flight through all of
+  // this one's compute.
+  auto pk_dir = [&](int64_t s, uint32_t (&dv)[NT]) {
+    const uint32_t* words = reinterpret_cast<const uint32_t*>(a.xdir);
+#pragma unroll
+    for (int t = 0; t < NT; ++t) dv[t] = words[(s * NT + t) >> 2];
+  };
+  auto dir_bytes = [&](int64_t s, const uint32_t (&dv)[NT], int (&db)[NT]) {
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+      db[t] = (int)((__builtin_amdgcn_readfirstlane(dv[t]) >> (8 * (int)((s * NT + t) & 3))) & 0xFFu);
+  };
+  auto pk_y = [&](int64_t s) { return label_bits(a, s * 64 + lane); };
+  // ln: the lane's 16-byte offset within a piece (its lane index; 0 for the placeholder below)
+  auto pk_load = [&](int64_t s, const int (&db)[NT], u32x4 (&raw)[NT][4], int ln) {
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      // both forms are 1 KiB pieces 1 KiB apart: three of the slot, or four of the raw entry
+      const bool pk = db[t] != 0xFF;
+      const int64_t e = s * NT + t;
+      const u32x4* q = (pk ? reinterpret_cast<const u32x4*>(a.xpack) + e * 3 * 64
+                           : reinterpret_cast<const u32x4*>(a.X) + e * 4 * 64) + ln;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) raw[t][k] = __builtin_nontemporal_load(q + k * 64);
+      if (!pk) raw[t][3] = __builtin_nontemporal_load(q + 3 * 64);
+    }
+  };
+  auto pk_compute = [&](int64_t s, const int (&db)[NT], const u32x4 (&raw)[NT][4], LabelBits yb) {
+    bf16x8 fr[NT][4];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      if (db[t] != 0xFF) {
+        unpack_tile(raw[t], (uint32_t)db[t] * 0x00800080u, fr[t]);
+      } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) fr[t][i] = __builtin_bit_cast(bf16x8, raw[t][i]);
+      }
+    }
+    compute_rv(row_vals<XMODE == 2>(a, s * 64 + lane, yb), fr);
+  };
+
+  if constexpr (PACKED) {
+    // The raw loop's wave -> superstep map, two supersteps per trip: buffers A and B swap roles
+    // instead of being copied.  The loads of the next superstep are issued on every path to a
+    // compute, so that the waits in it count exactly those as still in flight (a path without
+    // them would make every wait drain them): after a wave's last superstep the "next" is a
+    // placeholder, three 16-byte loads from slot 0 (the same word for every lane) and the wave's
+    // own label again, which nobody reads.
+    const int64_t step = a.interleave ? total_waves : 1;
+    const int64_t end = a.interleave ? a.nsuper : s1;
+    int64_t s = a.interleave ? gw : s0;
+    auto pk_next = [&](int64_t s, const uint32_t (&dv)[NT], int (&db)[NT], u32x4 (&raw)[NT][4], LabelBits& yb) {
+      const bool more = s + step < end;
+      dir_bytes(s + step, dv, db);
+#pragma unroll
+      for (int t = 0; t < NT; ++t) db[t] = more ? db[t] : 0;
+      pk_load(more ? s + step : 0, db, raw, more ? lane : 0);
+      yb = pk_y(more ? s + step : s);
+      return more;
+    };
+    if (s < end) {
+      u32x4 A[NT][4], B[NT][4];
+      int dA[NT], dB[NT];
+      uint32_t dv[NT];
+      LabelBits yA, yB;
+      pk_dir(s, dv);
+      dir_bytes(s, dv, dA);
+      pk_load(s, dA, A, lane);
+      yA = pk_y(s);
+      if (s + step < end) pk_dir(s + step, dv);
+      for (;;) {
+        bool more = pk_next(s, dv, dB, B, yB);
+        if (s + 2 * step < end) pk_dir(s + 2 * step, dv);
+        pk_compute(s, dA, A, yA);
+        if (!more) break;
+        s += step;
+        more = pk_next(s, dv, dA, A, yA);
+        if (s + 2 * step < end) pk_dir(s + 2 * step, dv);
+        pk_compute(s, dB, B, yB);
+        if (!more) break;
+        s += step;
+      }
+    }
+    if (do_tail) {  // the zero-padded last superstep has a directory entry and a slot like any other
+      u32x4 A[NT][4];
+      int dA[NT];
+      uint32_t dv[NT];
+      pk_dir(a.nsuper, dv);
+      dir_bytes(a.nsuper, dv, dA);
+      pk_load(a.nsuper, dA, A, lane);
+      pk_compute(a.nsuper, dA, A, pk_y(a.nsuper));
+    }
+  } else
   // full supersteps: register double buffer (loads of s+1 in flight while s computes)
   if (a.interleave) {
     if (gw < a.nsuper) {
@@ -344,7 +509,7 @@ gram_tall_bf16_kernel(GramArgs a) {
     }
   }
   // ragged tail (rows not filling a 64-row superstep): last wave only, guarded loads
-  if (do_tail) {
+  if (!PACKED && do_tail) {
     bf16x8 tl[NT][4];
     const int64_t r0 = a.nsuper * 64;
     load(r0, a.n - (r0 + 32 * h), tl);  // tiled storage is zero padded to a whole superstep
@@ -1147,6 +1312,54 @@ __global__ __launch_bounds__(256) void tile_bf16_kernel<uint16_t>(const uint16_t
   }
 }
 
+// tiles -> directory + 12-bit slots (gram.h: pack_tiles); one wave per (superstep, tile) entry
+__global__ __launch_bounds__(256) void pack_tiles_kernel(const u32x4* __restrict__ tiles, int64_t nent,
+                                                        uint8_t* __restrict__ dir, u32x4* __restrict__ slots,
+                                                        uint32_t* __restrict__ npacked) {
+  const int lane = threadIdx.x & 63;
+  const int64_t w0 = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  const int64_t nw = (int64_t)gridDim.x * (blockDim.x >> 6);
+  uint32_t mine = 0;
+  for (int64_t e = w0; e < nent; e += nw) {
+    u32x4 r[4];
+    uint32_t emin = 255u, emax = 0u;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      r[i] = tiles[(e * 4 + i) * 64 + lane];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const uint32_t lo = (r[i][j] >> 7) & 0xFFu, hi = (r[i][j] >> 23) & 0xFFu;
+        emin = min(emin, min(lo, hi));
+        emax = max(emax, max(lo, hi));
+      }
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+      emin = min(emin, (uint32_t)__shfl_xor((int)emin, o, 64));
+      emax = max(emax, (uint32_t)__shfl_xor((int)emax, o, 64));
+    }
+    const bool ok = emax - emin <= 15u && emin <= 254u;
+    if (lane == 0) dir[e] = ok ? (uint8_t)emin : (uint8_t)0xFF;
+    u32x4 D[3] = {u32x4{0u, 0u, 0u, 0u}, u32x4{0u, 0u, 0u, 0u}, u32x4{0u, 0u, 0u, 0u}};
+    if (ok) {
+      ++mine;
+      const uint32_t B2 = emin * 0x00800080u;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const uint32_t p3 = (r[i][3] & 0x7FFF7FFFu) - B2;  // 11-bit codes: no borrow between halfwords
+#pragma unroll
+        for (int k = 0; k < 3; ++k) D[k][i] = (r[i][k] & 0x80008000u) | ((r[i][k] & 0x7FFF7FFFu) - B2);
+        D[0][i] |= (p3 & 0x000F000Fu) << 11;
+        D[1][i] |= (p3 & 0x00F000F0u) << 7;
+        D[2][i] |= ((p3 & 0x07000700u) << 3) | ((r[i][3] & 0x80008000u) >> 1);
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) slots[(e * 3 + k) * 64 + lane] = D[k];
+  }
+  if (lane == 0 && mine) atomicAdd(npacked, mine);
+}
+
 // Un-shift of the packed statistics (gram.h: stats_unshift).  Pass 1 rewrites the Σxxᵀ entries
 // (reading the shifted column sums and Σw, which it does not write), pass 2 the column sums.
 __global__ __launch_bounds__(256) void unshift_aa_kernel(double* __restrict__ flat, const float* __restrict__ shift,
@@ -1211,6 +1424,18 @@ void tile_bf16(const void* X, int xdt, int64_t ld, int d, int64_t n, void* out, 
   DQ_HIP_CHECK(hipGetLastError());
 }
 
+void pack_tiles(const void* tiles, int d, int64_t n, uint8_t* dir, uint32_t* slots, uint32_t* npacked,
+                hipStream_t st) {
+  if (d < 1 || d > 64) throw std::invalid_argument("pack_tiles: d must be in [1, 64]");
+  const int64_t nent = ((n + 63) / 64) * ((d + 31) / 32);
+  if (nent < 1) return;
+  int64_t g = (nent + 3) / 4;
+  if (g > 16384) g = 16384;
+  hipLaunchKernelGGL(pack_tiles_kernel, dim3(g), dim3(256), 0, st, reinterpret_cast<const u32x4*>(tiles), nent, dir,
+                     reinterpret_cast<u32x4*>(slots), npacked);
+  DQ_HIP_CHECK(hipGetLastError());
+}
+
 int64_t gram_partial_stride(int mode, int d) {
   if (mode == GRAM_F64) {
     const int NT = (d + 15) / 16;
@@ -1255,19 +1480,21 @@ static size_t f64_lds(int d) {
 
 // Dispatch table: call F with the kernel instantiation for (mode, xdt, d, xmode).
 template <typename F>
-static void with_kernel(int mode, int xdt, int d, int xmode, bool tiled, F&& f) {
+static void with_kernel(int mode, int xdt, int d, int xmode, bool tiled, bool packed, F&& f) {
   if (mode == GRAM_BF16) {
     const int NT = (d + 31) / 32;
-#define DQ_BF16_CASE(TX, NTV, TL)                                                 \
-    if (xmode == 0 && NTV == 1) return f(gram_tall_bf16_kernel<TX, 1, 0, TL, true>); \
-    if (xmode == 0) return f(gram_tall_bf16_kernel<TX, NTV, 0, TL>);              \
-    if (xmode == 1) return f(gram_tall_bf16_kernel<TX, NTV, 1, TL>);              \
-    return f(gram_tall_bf16_kernel<TX, NTV, 2, TL>);
-    if (xdt == DT_BF16 && tiled) { if (NT == 1) { DQ_BF16_CASE(uint16_t, 1, true) } else { DQ_BF16_CASE(uint16_t, 2, true) } }
+#define DQ_BF16_CASE(TX, NTV, TL, PK)                                                    \
+    if (xmode == 0 && NTV == 1) return f(gram_tall_bf16_kernel<TX, 1, 0, TL, true, PK>); \
+    if (xmode == 0) return f(gram_tall_bf16_kernel<TX, NTV, 0, TL, false, PK>);          \
+    if (xmode == 1) return f(gram_tall_bf16_kernel<TX, NTV, 1, TL, false, PK>);          \
+    return f(gram_tall_bf16_kernel<TX, NTV, 2, TL, false, PK>);
+    if (packed && !(xdt == DT_BF16 && tiled)) throw std::invalid_argument("gram_tall: packed tiles need tiled bf16 storage");
+    if (packed) { if (NT == 1) { DQ_BF16_CASE(uint16_t, 1, true, true) } else { DQ_BF16_CASE(uint16_t, 2, true, true) } }
+    if (xdt == DT_BF16 && tiled) { if (NT == 1) { DQ_BF16_CASE(uint16_t, 1, true, false) } else { DQ_BF16_CASE(uint16_t, 2, true, false) } }
     if (tiled) throw std::invalid_argument("gram_tall: tiled storage must be bf16");
-    if (xdt == DT_BF16) { if (NT == 1) { DQ_BF16_CASE(uint16_t, 1, false) } else { DQ_BF16_CASE(uint16_t, 2, false) } }
-    if (xdt == DT_F32) { if (NT == 1) { DQ_BF16_CASE(float, 1, false) } else { DQ_BF16_CASE(float, 2, false) } }
-    if (xdt == DT_F64) { if (NT == 1) { DQ_BF16_CASE(double, 1, false) } else { DQ_BF16_CASE(double, 2, false) } }
+    if (xdt == DT_BF16) { if (NT == 1) { DQ_BF16_CASE(uint16_t, 1, false, false) } else { DQ_BF16_CASE(uint16_t, 2, false, false) } }
+    if (xdt == DT_F32) { if (NT == 1) { DQ_BF16_CASE(float, 1, false, false) } else { DQ_BF16_CASE(float, 2, false, false) } }
+    if (xdt == DT_F64) { if (NT == 1) { DQ_BF16_CASE(double, 1, false, false) } else { DQ_BF16_CASE(double, 2, false, false) } }
 #undef DQ_BF16_CASE
     throw std::invalid_argument("gram_tall(bf16): unsupported feature dtype");
   }
@@ -1364,7 +1591,7 @@ int gram_plan_blocks(int mode, int d, int64_t n, int xdt, int xmode) {
   const size_t lds = mode == GRAM_BF16 ? bf16_lds(d, xmode) : f64_lds(d);
   int full = 1;
   const int block = mode == GRAM_BF16 ? bf16_block(d, xmode) : kBlock;
-  with_kernel(mode, xdt, d, xmode, false, [&](auto kern) { full = occupancy_blocks(kern, lds, block); });
+  with_kernel(mode, xdt, d, xmode, false, false, [&](auto kern) { full = occupancy_blocks(kern, lds, block); });
   // at least ~4 supersteps per wave, at most one full residency wave of blocks
   const int64_t nsuper = (n + 63) / 64;
   const int wpb = block / kWave;
@@ -1406,6 +1633,12 @@ void gram_tall(int mode, GramArgs a, int xmode, int blocks, double* out, hipStre
   a.P = (int)gram_partial_stride(mode, a.d);
   const size_t lds = mode == GRAM_BF16 ? bf16_lds(a.d, xmode) : f64_lds(a.d);
   if (a.tiled && mode != GRAM_BF16) throw std::invalid_argument("gram_tall: tiled storage needs bf16 mode");
+  if ((a.xpack != nullptr) != (a.xdir != nullptr) || (a.xpack && !(a.tiled && mode == GRAM_BF16)))
+    throw std::invalid_argument("gram_tall: packed tiles come as a slot buffer plus a directory, with tiled bf16 storage");
+  if (a.xpack && a.w && xmode != 2) throw std::invalid_argument("gram_tall: packed tiles with weights need xmode 2");
+  if (a.xpack && ((a.ydt != DT_F32 && a.ydt != DT_F64) || (reinterpret_cast<uintptr_t>(a.xdir) & 3) ||
+                  (reinterpret_cast<uintptr_t>(a.xpack) & 15)))
+    throw std::invalid_argument("gram_tall: packed tiles need f32 / f64 labels, a word-aligned directory and 16-byte aligned slots");
   if (a.xshift) {
     // only the f32 stream kernels subtract a shift (tiled storage is shifted when it is tiled)
     if (!((mode == GRAM_F32 || mode == GRAM_BF16 || mode == GRAM_F32S) && a.xdt == DT_F32 && !a.tiled && a.cols == 0 &&
@@ -1428,7 +1661,7 @@ void gram_tall(int mode, GramArgs a, int xmode, int blocks, double* out, hipStre
   } else if (mode == GRAM_F32 || mode == GRAM_F32S) {
     throw std::invalid_argument("gram_tall(f32): needs 16-byte aligned f32 features and f32/f64 labels");
   } else {
-    with_kernel(mode, a.xdt, a.d, xmode, a.tiled != 0,
+    with_kernel(mode, a.xdt, a.d, xmode, a.tiled != 0, a.xpack != nullptr,
                 [&](auto kern) { hipLaunchKernelGGL(kern, dim3(blocks), dim3(block), lds, st, a); });
   }
   DQ_HIP_CHECK(hipGetLastError());

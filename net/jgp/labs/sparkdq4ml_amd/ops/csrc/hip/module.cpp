@@ -125,6 +125,30 @@ PYBIND11_MODULE(_dq4ml_hip, m) {
           a.partials = P<double>(partials);
           gram_tall(mode, a, xmode, blocks, P<double>(out), as_stream(stream), reduce);
         });
+  // tiled bf16 storage with its 12-bit companion (gram.h: pack_tiles); xmode etc. as gram_tall
+  m.def("gram_tall_packed",
+        [](uintptr_t X, uintptr_t xpack, uintptr_t xdir, int d, int64_t n, uintptr_t y, int ydt, uintptr_t w, int wdt,
+           uintptr_t sel, int xmode, uintptr_t partials, int blocks, uintptr_t out, uintptr_t stream, bool reduce) {
+          GramArgs a{};
+          a.tiled = 1;
+          a.X = P<const void>(X);
+          a.xpack = P<const uint32_t>(xpack);
+          a.xdir = P<const uint8_t>(xdir);
+          a.d = d;
+          a.n = n;
+          a.xdt = DT_BF16;
+          a.y = P<const void>(y);
+          a.ydt = ydt;
+          a.w = P<const void>(w);
+          a.wdt = wdt;
+          a.sel = P<const uint8_t>(sel);
+          a.partials = P<double>(partials);
+          gram_tall(GRAM_BF16, a, xmode, blocks, P<double>(out), as_stream(stream), reduce);
+        });
+  m.def("pack_tiles", [](uintptr_t tiles, int d, int64_t n, uintptr_t dir, uintptr_t slots, uintptr_t npacked,
+                         uintptr_t stream) {
+    pack_tiles(P<const void>(tiles), d, n, P<uint8_t>(dir), P<uint32_t>(slots), P<uint32_t>(npacked), as_stream(stream));
+  });
   m.def("gram_stream_cols",
         [](int mode, uintptr_t srcs, int d, int64_t n, int xdt, uintptr_t y, int ydt, uintptr_t w, int wdt,
            uintptr_t sel, uintptr_t partials, int blocks, uintptr_t out, uintptr_t stream, uintptr_t xshift) {

@@ -125,7 +125,7 @@ def _feature_view(X: torch.Tensor, align_elems: int):
 
 
 # ------------------------------------------------------------------------------------------
-from .layout import TiledBF16, TiledWide  # noqa: E402
+from .layout import SLOT_DWORDS, PackedTiles, TiledBF16, TiledWide  # noqa: E402
 from .shift import column_shift  # noqa: E402
 
 FP8_MAX = 448.0
@@ -152,9 +152,46 @@ def _unshift(h, out: torch.Tensor, shift, d: int) -> torch.Tensor:
     return out
 
 
-def tile_bf16(X: torch.Tensor, shift="auto") -> TiledBF16:
+# Rows from which an ingested table also gets the 12-bit packed companion under pack="auto"
+# (layout.PackedTiles; DQ4ML_TILE_PACK=0 switches it off for A/B runs).
+PACK_MIN_ROWS = 3_000_000
+
+
+def pack_tiles(T: TiledBF16) -> PackedTiles:
+    """The 12-bit packed companion of ``T.buf`` (``pack_tiles`` kernel; one D2H read of the count
+    of packed entries -- ingest time, not a fit path)."""
+    h = native.hip()
+    _check_dev(T.buf)
+    if T.d > 64:
+        raise ValueError("packed tiles support d <= 64")
+    ne = int(h.tiled_elems(T.d, T.n)) // 2048
+    # (allocated in whole 32-bit words: the Gram kernel reads the aligned word around a byte)
+    dirb = torch.empty((ne + 3) // 4 * 4, dtype=torch.uint8, device=T.device)[:ne]
+    slots = torch.empty(ne * SLOT_DWORDS, dtype=torch.int32, device=T.device)
+    cnt = torch.zeros(1, dtype=torch.int32, device=T.device)
+    if ne:
+        h.pack_tiles(T.buf.data_ptr(), int(T.d), int(T.n), dirb.data_ptr(), slots.data_ptr(), cnt.data_ptr(), _stream())
+    return PackedTiles(dirb, slots, int(cnt.item()))
+
+
+def _maybe_pack(T: TiledBF16, pack) -> TiledBF16:
+    if pack is True:
+        T.packed = pack_tiles(T)
+    elif pack == "auto":
+        if os.environ.get("DQ4ML_TILE_PACK", "1") != "0" and T.n >= PACK_MIN_ROWS and T.d <= 64:
+            p = pack_tiles(T)
+            # mostly raw data (zeros, a wide dynamic range) would read a directory for nothing
+            T.packed = p if 2 * p.npacked >= p.dir.numel() else None
+    elif pack is not False:
+        raise ValueError(f"pack: True, False or 'auto', not {pack!r}")
+    return T
+
+
+def tile_bf16(X: torch.Tensor, shift="auto", pack="auto") -> TiledBF16:
     """[d, n] features -> MFMA-fragment-ordered bf16 tiles of x - s (``shift``: "auto" = the
-    sampled per-column shift, None = unshifted, or an ``ops.shift.Shift``)."""
+    sampled per-column shift, None = unshifted, or an ``ops.shift.Shift``).  ``pack``: also build
+    the 12-bit packed companion the tall Gram pass reads (True / False; "auto": from
+    ``PACK_MIN_ROWS`` rows on, kept when at least half of the entries packed)."""
     h = native.hip()
     _check_dev(X)
     d, n = X.shape
@@ -164,7 +201,7 @@ def tile_bf16(X: torch.Tensor, shift="auto") -> TiledBF16:
     ld = X.stride(0) if d > 1 else max(n, 1)
     buf = torch.empty(int(h.tiled_elems(d, n)), dtype=torch.bfloat16, device=X.device)
     h.tile_bf16(X.data_ptr(), dtype_code(X), int(ld), int(d), int(n), buf.data_ptr(), _stream(), _sptr(shift))
-    return TiledBF16(buf, d, n, shift)
+    return _maybe_pack(TiledBF16(buf, d, n, shift), pack)
 
 
 class DeferredGram:
@@ -239,7 +276,7 @@ def gram_stats(X, y, w, sel, compute: str = "fp64", x_zero_dead: bool = False, b
         shift = column_shift([X])
         if shift is not None and X.dtype != torch.float32:
             if mode == 2 and w is None:
-                return _gram_tiled(h, tile_bf16(X, shift), y, None, sel, False, blocks, defer)
+                return _gram_tiled(h, tile_bf16(X, shift, pack=False), y, None, sel, False, blocks, defer)
             X = X.to(torch.float32).contiguous()
     align = 16 // X.element_size()
     Xv, ld = _feature_view(X, align)
@@ -579,13 +616,22 @@ def _prep_rows(y, w, sel, n):
     return y, w, sel
 
 
+def _tiled_pre(T: "TiledBF16", y, w, sel, xmode):
+    """Leading arguments of the tiled pass: ``gram_tall_packed`` where ``T`` carries the packed
+    companion (same grid, same wave -> superstep map, bit-identical sums), else ``gram_tall``."""
+    rows = (y.data_ptr(), dtype_code(y), _ptr(w), dtype_code(w) if w is not None else 0, _ptr(sel), xmode)
+    if T.packed is not None:
+        return (T.buf.data_ptr(), T.packed.a.data_ptr(), T.packed.dir.data_ptr(), int(T.d), int(T.n)) + rows
+    return (2, T.buf.data_ptr(), 0, int(T.d), int(T.n), 2) + rows
+
+
 class TiledGramPlan:
     """The resolved launch of one tiled bf16 Gram pass (``gram_tall`` mode 2 with the fold left to
     the fit's side stream): row operands prepared, block count planned and argument tuple built
     once, so a repeated fit of the same table only allocates its outputs and launches
     (``models/regression.py`` fit replay, ~0.14 ms of device work per fit at the 8-GPU shard)."""
 
-    __slots__ = ("h", "T", "y", "w", "sel", "d", "nb", "flat_len", "part_len", "dev", "pre", "post")
+    __slots__ = ("h", "T", "y", "w", "sel", "d", "nb", "flat_len", "part_len", "dev", "pre", "post", "packed")
 
     def __init__(self, h, T: "TiledBF16", y, w, sel, x_zero_dead):
         d, n = T.d, T.n
@@ -598,15 +644,18 @@ class TiledGramPlan:
         self.nb = int(_plan_blocks(h, 2, d, n, 2, xmode))
         self.flat_len = 5 + 2 * d + d * (d + 1) // 2
         self.part_len = self.nb * int(h.gram_partial_stride(2, d))
-        self.pre = (2, T.buf.data_ptr(), 0, int(d), int(n), 2, y.data_ptr(), dtype_code(y), _ptr(w),
-                    dtype_code(w) if w is not None else 0, _ptr(sel), xmode)
+        self.pre = _tiled_pre(T, y, w, sel, xmode)
+        self.packed = T.packed is not None
 
     def launch(self, stream: int, defer: bool):
         """Enqueue the pass on ``stream``: a :class:`DeferredGram` (``defer``, the fold and the
         un-shift left to the caller) or the folded, un-shifted statistics."""
         out = torch.empty(self.flat_len, dtype=torch.float64, device=self.dev)
         partials = torch.empty(self.part_len, dtype=torch.float64, device=self.dev)
-        self.h.gram_tall(*self.pre, partials.data_ptr(), self.nb, out.data_ptr(), stream, 1, not defer, 0)
+        if self.packed:
+            self.h.gram_tall_packed(*self.pre, partials.data_ptr(), self.nb, out.data_ptr(), stream, not defer)
+        else:
+            self.h.gram_tall(*self.pre, partials.data_ptr(), self.nb, out.data_ptr(), stream, 1, not defer, 0)
         sh = self.T.shift
         if defer:
             return DeferredGram(self.h, 2, partials, self.nb, self.d, out, sh)
@@ -627,9 +676,11 @@ def _gram_tiled(h, T: "TiledBF16", y, w, sel, x_zero_dead, blocks, defer=False):
     P = int(h.gram_partial_stride(2, d))
     partials = torch.empty(nb * P, dtype=torch.float64, device=T.device)
     # (the tiles hold x - s already: the kernel takes no shift, the statistics are un-shifted after the fold)
-    h.gram_tall(2, T.buf.data_ptr(), 0, int(d), int(n), 2, y.data_ptr(), dtype_code(y), _ptr(w),
-                dtype_code(w) if w is not None else 0, _ptr(sel), xmode, partials.data_ptr(), nb, out.data_ptr(),
-                _stream(), 1, not defer, 0)
+    pre = _tiled_pre(T, y, w, sel, xmode)
+    if T.packed is not None:
+        h.gram_tall_packed(*pre, partials.data_ptr(), nb, out.data_ptr(), _stream(), not defer)
+    else:
+        h.gram_tall(*pre, partials.data_ptr(), nb, out.data_ptr(), _stream(), 1, not defer, 0)
     if defer:
         return DeferredGram(h, 2, partials, nb, d, out, T.shift)
     return _unshift(h, out, T.shift, d)

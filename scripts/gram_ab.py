@@ -13,10 +13,17 @@ d = int(os.environ.get("D", "32"))
 rounds = int(os.environ.get("ROUNDS", "5"))
 X = torch.randn(d, n, device="cuda").to(torch.bfloat16)
 y = torch.randn(n, device="cuda")
-T = device.tile_bf16(X)
+T = device.tile_bf16(X, pack=False)
+# the same tiles with their 12-bit packed companion (N=1.25e7 for the 8-GPU shard)
+torch.cuda.synchronize()
+t0 = time.perf_counter()
+Tp = device.TiledBF16(T.buf, d, n, T.shift, packed=device.pack_tiles(T))
+print(f"pack_tiles {1e3 * (time.perf_counter() - t0):.2f} ms (with its counter read), packed fraction "
+      f"{Tp.packed.fraction:.4f}")
 ref = device.gram_stats(X, y, None, None, "bf16")
 got = device.gram_stats(T, y, None, None, "bf16")
 print("tiled vs plain max rel diff", float((got - ref).abs().max() / ref.abs().max()))
+print("packed == tiled bitwise", bool(torch.equal(device.gram_stats(Tp, y, None, None, "bf16"), got)))
 bytes_x = X.numel() * 2 + y.numel() * 4
 
 
@@ -34,9 +41,13 @@ def timeit(fn, reps=10):
 variants = {
     "plain": lambda: device.gram_stats(X, y, None, None, "bf16"),
     "tiled": lambda: device.gram_stats(T, y, None, None, "bf16"),
+    "packed": lambda: device.gram_stats(Tp, y, None, None, "bf16"),
     "read_sum": lambda: torch.sum(T.buf.view(torch.int16), dtype=torch.int64),
     "copy": lambda: T.buf.clone(),
 }
+only = os.environ.get("ONLY")  # e.g. ONLY=tiled,packed
+if only:
+    variants = {k: f for k, f in variants.items() if k in only.split(",")}
 res = {k: [] for k in variants}
 for r in range(rounds):
     for k, f in variants.items():
@@ -44,5 +55,6 @@ for r in range(rounds):
 for k, v in res.items():
     v.sort()
     ms = v[len(v) // 2]
-    gbs = (bytes_x if k in ("plain", "tiled") else T.buf.numel() * 2 * (2 if k == "copy" else 1)) / ms / 1e6
+    # ("packed": the rate in bytes of the raw tiles it stands for, to compare with "tiled")
+    gbs = (bytes_x if k in ("plain", "tiled", "packed") else T.buf.numel() * 2 * (2 if k == "copy" else 1)) / ms / 1e6
     print(f"{k:10s} median {ms:.3f} ms  min {v[0]:.3f}  -> {gbs:.0f} GB/s")
