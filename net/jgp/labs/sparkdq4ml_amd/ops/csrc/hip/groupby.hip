@@ -1,0 +1,527 @@
+// Grouped aggregation on integer words.
+//
+// group_encode turns one key column into group ids.  A key value becomes an order-preserving u64
+// (floats: IEEE bits of the value as a double, -0.0 folded into +0.0, every NaN one canonical NaN
+// above +inf; integers and booleans: biased by the sign bit).  Integer keys of a small live range
+// index a slot directly (gid = key - base + 1, null = 0); everything else goes through an
+// open-addressing table of u64 slots in HBM (linear probing, 64-bit atomicCAS, power-of-two
+// capacity).  The empty slot is all ones, which is the key of INT64_MAX: that one key never enters
+// the table, a flag records that it was seen and the launcher gives it the last group id.
+//
+// group_agg makes one pass over the rows for up to kGroupMaxSlots aggregate slots.  Every
+// accumulator word is a u64 updated by an integer atomic (add / or / max / min), so any order of
+// the updates gives the same bits.  Doubles are summed in fixed point: with e the frexp exponent
+// of the largest finite |x| of the column, x is split into four signed 32-bit limbs of
+// x * 2^(128 - e) (each step exact in f64) and limb k is an i64 add.
+//
+// Contention: before any atomic the lanes of a wave that share the first live lane's group reduce
+// their contributions in the wave and the leader issues one atomic, twice in a row; whatever is
+// left takes per-lane atomics.  When G * words fits kGroupLdsWords a block accumulates in LDS and
+// flushes its non-identity words once.
+#include "groupby.h"
+
+#include <stdexcept>
+
+#include "common.h"
+
+namespace dq4ml {
+namespace {
+
+typedef __attribute__((ext_vector_type(2))) long long i64x2;
+typedef __attribute__((ext_vector_type(4))) int i32x4;
+typedef unsigned long long u64;
+
+constexpr u64 kSign = 0x8000000000000000ull;
+constexpr u64 kNaNBits = 0x7ff8000000000000ull;
+constexpr u64 kInfBits = 0x7ff0000000000000ull;
+constexpr u64 kEmpty = ~0ull;
+
+__device__ __forceinline__ bool is_float_dt(int dt) { return dt == DT_F64 || dt == DT_F32; }
+
+// kGroupRun consecutive rows [r0, r0 + 4) of a typed column widened to 64 bits (floats: the bits of
+// the value as a double; integers and booleans: the value as an i64; 0 past n).  16-byte loads when
+// the run is complete and aligned (r0 is a multiple of 4), else a guarded scalar tail.
+template <int DT>
+__device__ __forceinline__ void load_run_raw(const void* p, int64_t r0, int64_t n, u64 x[kGroupRun]) {
+  const bool aligned = (reinterpret_cast<uintptr_t>(p) & 15) == 0;
+  if (aligned && r0 + kGroupRun <= n) {
+    if constexpr (DT == DT_F64) {
+      const f64x2 a = *gptr<f64x2>(reinterpret_cast<const double*>(p) + r0);
+      const f64x2 b = *gptr<f64x2>(reinterpret_cast<const double*>(p) + r0 + 2);
+      x[0] = (u64)__double_as_longlong(a[0]), x[1] = (u64)__double_as_longlong(a[1]);
+      x[2] = (u64)__double_as_longlong(b[0]), x[3] = (u64)__double_as_longlong(b[1]);
+    } else if constexpr (DT == DT_I64) {
+      const i64x2 a = *gptr<i64x2>(reinterpret_cast<const long long*>(p) + r0);
+      const i64x2 b = *gptr<i64x2>(reinterpret_cast<const long long*>(p) + r0 + 2);
+      x[0] = (u64)a[0], x[1] = (u64)a[1], x[2] = (u64)b[0], x[3] = (u64)b[1];
+    } else if constexpr (DT == DT_F32) {
+      const f32x4 a = *gptr<f32x4>(reinterpret_cast<const float*>(p) + r0);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) x[j] = (u64)__double_as_longlong((double)a[j]);
+    } else if constexpr (DT == DT_I32) {
+      const i32x4 a = *gptr<i32x4>(reinterpret_cast<const int*>(p) + r0);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) x[j] = (u64)(long long)a[j];
+    } else {
+      const uint32_t w = *gptr<uint32_t>(reinterpret_cast<const uint8_t*>(p) + r0);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) x[j] = ((w >> (8 * j)) & 0xffu) ? 1ull : 0ull;
+    }
+    return;
+  }
+#pragma unroll
+  for (int j = 0; j < kGroupRun; ++j) {
+    const int64_t r = r0 + j;
+    u64 v = 0;
+    if (r < n) {
+      if constexpr (DT == DT_F64) v = (u64)__double_as_longlong(gptr<double>(p)[r]);
+      else if constexpr (DT == DT_I64) v = (u64)gptr<long long>(p)[r];
+      else if constexpr (DT == DT_F32) v = (u64)__double_as_longlong((double)gptr<float>(p)[r]);
+      else if constexpr (DT == DT_I32) v = (u64)(long long)gptr<int>(p)[r];
+      else v = gptr<uint8_t>(p)[r] != 0 ? 1ull : 0ull;
+    }
+    x[j] = v;
+  }
+}
+
+// (the switch is block-uniform)
+__device__ __forceinline__ void load_run(const void* p, int dt, int64_t r0, int64_t n, u64 x[kGroupRun]) {
+  switch (dt) {
+    case DT_F64: load_run_raw<DT_F64>(p, r0, n, x); break;
+    case DT_F32: load_run_raw<DT_F32>(p, r0, n, x); break;
+    case DT_I32: load_run_raw<DT_I32>(p, r0, n, x); break;
+    case DT_I64: load_run_raw<DT_I64>(p, r0, n, x); break;
+    default: load_run_raw<DT_U8>(p, r0, n, x); break;
+  }
+}
+
+// bit j: row r0 + j is inside n and its 0/1 byte is set (null mask: every row inside n)
+__device__ __forceinline__ unsigned mask_run(const uint8_t* m, int64_t r0, int64_t n) {
+  unsigned out = 0;
+  if (m != nullptr && r0 + kGroupRun <= n && ((reinterpret_cast<uintptr_t>(m + r0) & 3) == 0)) {
+    const uint32_t w = *gptr<uint32_t>(m + r0);
+#pragma unroll
+    for (int j = 0; j < kGroupRun; ++j) out |= ((w >> (8 * j)) & 0xffu) ? (1u << j) : 0u;
+    return out;
+  }
+#pragma unroll
+  for (int j = 0; j < kGroupRun; ++j) {
+    const int64_t r = r0 + j;
+    if (r < n && (m == nullptr || gptr<uint8_t>(m)[r] != 0)) out |= 1u << j;
+  }
+  return out;
+}
+
+// order key of a widened value; fold: the grouping rule (-0.0 == +0.0), else -0.0 < +0.0 (MIN / MAX)
+__device__ __forceinline__ u64 order_key(u64 raw, bool isf, bool fold) {
+  if (!isf) return raw ^ kSign;
+  u64 b = raw;
+  if ((b & ~kSign) > kInfBits) b = kNaNBits;  // every NaN: one canonical NaN above +inf
+  if (fold && b == kSign) b = 0;
+  return (b & kSign) ? ~b : (b | kSign);
+}
+
+__device__ __forceinline__ int word_kind(int op, int w) {
+  switch (op) {
+    case GOP_SUM_F: return w == kGroupSumWords - 1 ? GK_OR : GK_ADD;
+    case GOP_MIN:
+    case GOP_FIRST: return GK_MIN;
+    case GOP_MAX:
+    case GOP_ABSMAX: return GK_MAX;
+    default: return GK_ADD;
+  }
+}
+
+__device__ __forceinline__ u64 kind_identity(int kind) { return kind == GK_MIN ? ~0ull : 0ull; }
+
+__device__ __forceinline__ void word_update(u64* p, int kind, u64 v) {
+  switch (kind) {
+    case GK_ADD: atomicAdd(p, v); break;
+    case GK_OR: atomicOr(p, v); break;
+    case GK_MAX: atomicMax(p, v); break;
+    default: atomicMin(p, v); break;
+  }
+}
+
+__device__ __forceinline__ u64 wave_reduce(int kind, u64 v) {
+  switch (kind) {  // wave-uniform
+    case GK_ADD:
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
+      break;
+    case GK_OR:
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) v |= __shfl_xor(v, o, kWave);
+      break;
+    case GK_MAX:
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const u64 u = __shfl_xor(v, o, kWave);
+        v = u > v ? u : v;
+      }
+      break;
+    default:
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const u64 u = __shfl_xor(v, o, kWave);
+        v = u < v ? u : v;
+      }
+      break;
+  }
+  return v;
+}
+
+// Word w of group g takes v from every lane with `on` set.  Two rounds of "the lanes that share
+// the first live lane's group reduce in the wave, the leader issues one atomic", then per-lane
+// atomics.  Identity contributions are dropped.  Every lane of the wave calls this.
+__device__ __forceinline__ void emit(u64* acc, int words, bool on, int g, int w, int kind, u64 v, int lane) {
+  const u64 ident = kind_identity(kind);
+  on = on && v != ident;
+  uint64_t rem = __ballot(on);
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+    if (rem == 0) return;  // wave-uniform
+    const int leader = __ffsll((long long)rem) - 1;
+    const int g0 = __builtin_amdgcn_readlane(g, leader);
+    const bool same = on && g == g0;
+    const uint64_t grp = __ballot(same);
+    u64 red = v;  // (a group of one lane: the leader's own value)
+    if (__popcll(grp) > 1) red = wave_reduce(kind, same ? v : ident);
+    if (lane == leader && red != ident) word_update(acc + (int64_t)g0 * words + w, kind, red);
+    on = on && !same;
+    rem &= ~grp;
+  }
+  if (on) word_update(acc + (int64_t)g * words + w, kind, v);
+}
+
+template <bool LDS>
+__global__ __launch_bounds__(kGroupThreads) void group_agg_kernel(GroupAggArgs a, u64* out) {
+  __shared__ u64 lds[LDS ? kGroupLdsWords : 1];
+  __shared__ int wkind[kGroupMaxWords];
+  const int lane = threadIdx.x & (kWave - 1);
+  const int total = LDS ? a.G * a.words : 0;  // at most kGroupLdsWords (the launcher picks the kernel)
+  if constexpr (LDS) {
+    if ((int)threadIdx.x < a.words) {
+      int kind = GK_ADD;
+      for (int s = 0; s < a.S; ++s) {
+        const int w = (int)threadIdx.x - a.woff[s];
+        if (w >= 0 && w < group_op_words(a.op[s])) kind = word_kind(a.op[s], w);
+      }
+      wkind[threadIdx.x] = kind;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < total; i += kGroupThreads) lds[i] = kind_identity(wkind[i % a.words]);
+    __syncthreads();
+  }
+  u64* acc = LDS ? lds : out;
+  const bool galigned = (reinterpret_cast<uintptr_t>(a.gid) & 15) == 0;
+  const int64_t trips = (a.n + kGroupTrip - 1) / kGroupTrip;
+  // the trip loop is block-uniform: rows past n are dead lanes, never absent ones
+  for (int64_t t = blockIdx.x; t < trips; t += gridDim.x) {
+    const int64_t r0 = t * kGroupTrip + (int64_t)threadIdx.x * kGroupRun;
+    unsigned live = mask_run(a.sel, r0, a.n);
+    int g[kGroupRun] = {0, 0, 0, 0};
+    if (a.gid != nullptr) {
+      if (galigned && r0 + kGroupRun <= a.n) {
+        const i32x4 v = *gptr<i32x4>(a.gid + r0);
+#pragma unroll
+        for (int j = 0; j < kGroupRun; ++j) g[j] = v[j];
+      } else {
+#pragma unroll
+        for (int j = 0; j < kGroupRun; ++j) g[j] = r0 + j < a.n ? gptr<int>(a.gid)[r0 + j] : -1;
+      }
+#pragma unroll
+      for (int j = 0; j < kGroupRun; ++j)
+        if (g[j] < 0 || g[j] >= a.G) live &= ~(1u << j), g[j] = 0;  // -1: dead row; never index past G
+    }
+    for (int s = 0; s < a.S; ++s) {  // block-uniform
+      const int op = a.op[s], w0 = a.woff[s], dt = a.dt[s];
+      const bool isf = is_float_dt(dt);
+      const bool reads = op != GOP_ROWS && op != GOP_FIRST && op != GOP_COUNT;
+      u64 raw[kGroupRun] = {0, 0, 0, 0};
+      if (reads) load_run(a.col[s], dt, r0, a.n, raw);
+      unsigned ok = live;
+      if (op != GOP_ROWS && op != GOP_FIRST && a.valid[s] != nullptr) ok &= mask_run(a.valid[s], r0, a.n);
+#pragma unroll
+      for (int j = 0; j < kGroupRun; ++j) {
+        const bool on = (ok >> j) & 1u;
+        switch (op) {  // block-uniform
+          case GOP_ROWS:
+          case GOP_COUNT: emit(acc, a.words, on, g[j], w0, GK_ADD, 1ull, lane); break;
+          case GOP_SUM_I: emit(acc, a.words, on, g[j], w0, GK_ADD, raw[j], lane); break;
+          case GOP_MIN: emit(acc, a.words, on, g[j], w0, GK_MIN, order_key(raw[j], isf, false), lane); break;
+          case GOP_MAX: emit(acc, a.words, on, g[j], w0, GK_MAX, order_key(raw[j], isf, false), lane); break;
+          case GOP_FIRST: emit(acc, a.words, on, g[j], w0, GK_MIN, (u64)(a.row_offset + r0 + j), lane); break;
+          case GOP_ABSMAX: {
+            const double x = isf ? __longlong_as_double((long long)raw[j]) : (double)(long long)raw[j];
+            const u64 b = (u64)__double_as_longlong(x) & ~kSign;
+            emit(acc, a.words, on && b < kInfBits, g[j], w0, GK_MAX, b, lane);
+            break;
+          }
+          default: {  // GOP_SUM_F
+            const double x = isf ? __longlong_as_double((long long)raw[j]) : (double)(long long)raw[j];
+            const u64 b = (u64)__double_as_longlong(x);
+            const bool finite = (b & ~kSign) < kInfBits;
+            const u64 flag = finite ? 0ull : ((b & ~kSign) > kInfBits ? 1ull : ((b & kSign) ? 4ull : 2ull));
+            double tt = finite ? ldexp(x, 32 - a.e[s]) : 0.0;
+#pragma unroll
+            for (int k = 0; k < kGroupSumWords - 1; ++k) {
+              const double c = trunc(tt);
+              emit(acc, a.words, on, g[j], w0 + k, GK_ADD, (u64)(long long)c, lane);
+              tt = ldexp(tt - c, 32);
+            }
+            emit(acc, a.words, on, g[j], w0 + kGroupSumWords - 1, GK_OR, flag, lane);
+            break;
+          }
+        }
+      }
+    }
+  }
+  if constexpr (LDS) {
+    __syncthreads();
+    for (int i = threadIdx.x; i < total; i += kGroupThreads) {
+      const int kind = wkind[i % a.words];
+      const u64 v = lds[i];
+      if (v != kind_identity(kind)) word_update(out + i, kind, v);
+    }
+  }
+}
+
+// the key of row j of a run: `ins` rows carry a key that lives in the table
+struct KeyRun {
+  u64 key[kGroupRun];
+  unsigned live, valid;
+};
+
+__device__ __forceinline__ KeyRun load_keys(const GroupKeyCol& a, int64_t r0) {
+  KeyRun k;
+  u64 raw[kGroupRun];
+  load_run(a.col, a.dt, r0, a.n, raw);
+  const bool isf = is_float_dt(a.dt);
+#pragma unroll
+  for (int j = 0; j < kGroupRun; ++j) k.key[j] = order_key(raw[j], isf, true);
+  k.live = mask_run(a.sel, r0, a.n);
+  k.valid = k.live;
+  if (a.valid != nullptr) k.valid &= mask_run(a.valid, r0, a.n);
+  return k;
+}
+
+__device__ __forceinline__ void store_gids(int* gid, int64_t r0, int64_t n, const int g[kGroupRun]) {
+  if (r0 + kGroupRun <= n && ((reinterpret_cast<uintptr_t>(gid) & 15) == 0)) {
+    i32x4 v;
+#pragma unroll
+    for (int j = 0; j < kGroupRun; ++j) v[j] = g[j];
+    *reinterpret_cast<i32x4*>(gid + r0) = v;
+    return;
+  }
+#pragma unroll
+  for (int j = 0; j < kGroupRun; ++j)
+    if (r0 + j < n) gid[r0 + j] = g[j];
+}
+
+__global__ __launch_bounds__(kGroupThreads) void group_direct_kernel(GroupKeyCol a, int64_t base, int64_t span, int* gid) {
+  const int64_t trips = (a.n + kGroupTrip - 1) / kGroupTrip;
+  for (int64_t t = blockIdx.x; t < trips; t += gridDim.x) {
+    const int64_t r0 = t * kGroupTrip + (int64_t)threadIdx.x * kGroupRun;
+    u64 raw[kGroupRun];
+    load_run(a.col, a.dt, r0, a.n, raw);
+    const unsigned live = mask_run(a.sel, r0, a.n);
+    unsigned valid = live;
+    if (a.valid != nullptr) valid &= mask_run(a.valid, r0, a.n);
+    int g[kGroupRun];
+#pragma unroll
+    for (int j = 0; j < kGroupRun; ++j) {
+      const u64 off = raw[j] - (u64)base;  // (unsigned: a value below base wraps far past span)
+      g[j] = !((live >> j) & 1u) ? -1 : (!((valid >> j) & 1u) ? 0 : (off < (u64)span ? (int)off + 1 : -1));
+    }
+    store_gids(gid, r0, a.n, g);
+  }
+}
+
+__device__ __forceinline__ u64 home_slot(u64 key, u64 mask) { return ((key * 0x9E3779B97F4A7C15ull) >> 20) & mask; }
+
+__device__ __forceinline__ u64 load_slot(const u64* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// state: [0] occupied slots, [1] overflow, [2] a null key was seen, [3] the all-ones key was seen
+__device__ __forceinline__ void table_insert(u64* table, u64 mask, u64* state, u64 key) {
+  u64 slot = home_slot(key, mask);
+  // a slot only ever changes from empty to a key, so a stale read costs one failed CAS at most;
+  // the bound ends the probe of a table that other waves filled after the overflow check
+  for (u64 i = 0; i <= mask; ++i) {
+    const u64 cur = load_slot(table + slot);
+    if (cur == key) return;
+    if (cur == kEmpty) {
+      const u64 old = atomicCAS(table + slot, kEmpty, key);
+      if (old == key) return;
+      if (old == kEmpty) {
+        const u64 c = atomicAdd(state, 1ull) + 1;
+        if (c > (mask + 1) / 2) atomicOr(state + 1, 1ull);
+        return;
+      }
+    }
+    slot = (slot + 1) & mask;
+  }
+  atomicOr(state + 1, 1ull);
+}
+
+__global__ __launch_bounds__(kGroupThreads) void group_hash_insert_kernel(GroupKeyCol a, u64* table, u64 mask, u64* state) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t trips = (a.n + kGroupTrip - 1) / kGroupTrip;
+  bool saw_null = false, saw_top = false;
+  for (int64_t t = blockIdx.x; t < trips; t += gridDim.x) {
+    // past half full: stop inserting, the launcher retries with a larger table (wave-uniform read)
+    if (__builtin_amdgcn_readfirstlane((int)load_slot(state + 1)) != 0) break;
+    const int64_t r0 = t * kGroupTrip + (int64_t)threadIdx.x * kGroupRun;
+    const KeyRun k = load_keys(a, r0);
+#pragma unroll
+    for (int j = 0; j < kGroupRun; ++j) {
+      const bool live = (k.live >> j) & 1u, valid = (k.valid >> j) & 1u;
+      saw_null = saw_null || (live && !valid);
+      saw_top = saw_top || (valid && k.key[j] == kEmpty);
+      bool ins = valid && k.key[j] != kEmpty;
+      // the lanes that hold the first live lane's key insert once
+      const uint64_t rem = __ballot(ins);
+      if (rem != 0) {
+        const int leader = __ffsll((long long)rem) - 1;
+        const u64 k0 = __shfl(k.key[j], leader, kWave);
+        if (ins && k.key[j] == k0 && lane != leader) ins = false;
+      }
+      if (ins) table_insert(table, mask, state, k.key[j]);
+    }
+  }
+  if (saw_null) atomicOr(state + 2, 1ull);
+  if (saw_top) atomicOr(state + 3, 1ull);
+}
+
+__device__ __forceinline__ int table_find(const u64* table, u64 mask, const int* slot_gid, u64 key) {
+  u64 slot = home_slot(key, mask);
+  for (u64 i = 0; i <= mask; ++i) {
+    const u64 cur = gptr<u64>(table)[slot];
+    if (cur == key) return gptr<int>(slot_gid)[slot];
+    if (cur == kEmpty) return -1;
+    slot = (slot + 1) & mask;
+  }
+  return -1;
+}
+
+__global__ __launch_bounds__(kGroupThreads) void group_hash_lookup_kernel(GroupKeyCol a, const u64* table, u64 mask,
+                                                                         const int* slot_gid, int top_gid, int* gid) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t trips = (a.n + kGroupTrip - 1) / kGroupTrip;
+  for (int64_t t = blockIdx.x; t < trips; t += gridDim.x) {
+    const int64_t r0 = t * kGroupTrip + (int64_t)threadIdx.x * kGroupRun;
+    const KeyRun k = load_keys(a, r0);
+    int g[kGroupRun];
+#pragma unroll
+    for (int j = 0; j < kGroupRun; ++j) {
+      const bool live = (k.live >> j) & 1u, valid = (k.valid >> j) & 1u;
+      int res = !live ? -1 : (!valid ? 0 : top_gid);
+      bool need = valid && k.key[j] != kEmpty;
+      // the lanes that hold the first live lane's key look it up once
+      const uint64_t rem = __ballot(need);
+      if (rem != 0) {
+        const int leader = __ffsll((long long)rem) - 1;
+        const u64 k0 = __shfl(k.key[j], leader, kWave);
+        int g0 = -1;
+        if (lane == leader) g0 = table_find(table, mask, slot_gid, k0);
+        g0 = __builtin_amdgcn_readlane(g0, leader);
+        if (need && k.key[j] == k0) res = g0, need = false;
+      }
+      if (need) res = table_find(table, mask, slot_gid, k.key[j]);
+      g[j] = res;
+    }
+    store_gids(gid, r0, a.n, g);
+  }
+}
+
+void check_key(const GroupKeyCol& a, int blocks) {
+  if (a.n < 0) throw std::invalid_argument("group_encode: negative row count");
+  if (blocks < 1) throw std::invalid_argument("group_encode: blocks must be >= 1");
+  if (a.dt != DT_F64 && a.dt != DT_F32 && a.dt != DT_I32 && a.dt != DT_I64 && a.dt != DT_U8)
+    throw std::invalid_argument("group_encode: keys must be f64, f32, i32, i64 or u8");
+  if (a.col == nullptr && a.n > 0) throw std::invalid_argument("group_encode: null column");
+}
+
+void check_table(int64_t capacity) {
+  if (capacity < 2 || (capacity & (capacity - 1)) != 0 || capacity > ((int64_t)1 << 40))
+    throw std::invalid_argument("group_encode: the table capacity must be a power of two >= 2");
+}
+
+}  // namespace
+
+int group_blocks(int64_t n) {
+  int dev = 0, cus = 0;
+  DQ_HIP_CHECK(hipGetDevice(&dev));
+  DQ_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+  // 4 blocks of 4 waves per CU: the 32 KiB of LDS accumulators allow that many, and 16 to 48 bytes
+  // in flight per thread and slot cover the HBM latency
+  const int64_t full = 4 * (int64_t)(cus < 1 ? 1 : cus);
+  int64_t want = (n + kGroupTrip - 1) / kGroupTrip;
+  if (want < 1) want = 1;
+  return (int)(want < full ? want : full);
+}
+
+void group_agg(const GroupAggArgs& a, unsigned long long* acc, int blocks, hipStream_t st) {
+  if (a.n < 0) throw std::invalid_argument("group_agg: negative row count");
+  if (blocks < 1) throw std::invalid_argument("group_agg: blocks must be >= 1");
+  if (a.G < 1) throw std::invalid_argument("group_agg: at least one group");
+  if (a.S < 1 || a.S > kGroupMaxSlots)
+    throw std::invalid_argument("group_agg: between 1 and " + std::to_string(kGroupMaxSlots) + " slots per call");
+  if (acc == nullptr) throw std::invalid_argument("group_agg: null accumulator");
+  int words = 0;
+  for (int s = 0; s < a.S; ++s) {
+    const int op = a.op[s];
+    if (op < GOP_ROWS || op > GOP_ABSMAX) throw std::invalid_argument("group_agg: unknown op");
+    if (a.woff[s] != words) throw std::invalid_argument("group_agg: slot words must be packed in slot order");
+    words += group_op_words(op);
+    const bool reads = op != GOP_ROWS && op != GOP_FIRST && op != GOP_COUNT;
+    if (reads) {
+      const int dt = a.dt[s];
+      if (dt != DT_F64 && dt != DT_F32 && dt != DT_I32 && dt != DT_I64 && dt != DT_U8)
+        throw std::invalid_argument("group_agg: columns must be f64, f32, i32, i64 or u8");
+      if (a.col[s] == nullptr && a.n > 0) throw std::invalid_argument("group_agg: null column");
+      if (op == GOP_SUM_I && (dt == DT_F64 || dt == DT_F32)) throw std::invalid_argument("group_agg: SUM_I of a float column");
+    }
+    if (op == GOP_SUM_F && a.n >= ((int64_t)1 << 31))
+      throw std::invalid_argument("group_agg: a fixed-point sum takes fewer than 2^31 rows per call");
+  }
+  if (words != a.words) throw std::invalid_argument("group_agg: words does not match the slots");
+  if (a.n == 0) return;  // the accumulators keep their identities
+  const bool lds = (int64_t)a.G * a.words <= kGroupLdsWords;
+  if (lds)
+    hipLaunchKernelGGL(group_agg_kernel<true>, dim3((unsigned)blocks), dim3(kGroupThreads), 0, st, a, acc);
+  else
+    hipLaunchKernelGGL(group_agg_kernel<false>, dim3((unsigned)blocks), dim3(kGroupThreads), 0, st, a, acc);
+  DQ_HIP_CHECK(hipGetLastError());
+}
+
+void group_encode_direct(const GroupKeyCol& a, int64_t base, int64_t span, int* gid, int blocks, hipStream_t st) {
+  check_key(a, blocks);
+  if (a.dt == DT_F64 || a.dt == DT_F32) throw std::invalid_argument("group_encode: direct mode takes integer keys");
+  if (span < 0 || span > kGroupDirectCap) throw std::invalid_argument("group_encode: direct range above the cap");
+  if (a.n == 0) return;
+  hipLaunchKernelGGL(group_direct_kernel, dim3((unsigned)blocks), dim3(kGroupThreads), 0, st, a, base, span, gid);
+  DQ_HIP_CHECK(hipGetLastError());
+}
+
+void group_hash_insert(const GroupKeyCol& a, unsigned long long* table, int64_t capacity, unsigned long long* state,
+                       int blocks, hipStream_t st) {
+  check_key(a, blocks);
+  check_table(capacity);
+  if (a.n == 0) return;
+  hipLaunchKernelGGL(group_hash_insert_kernel, dim3((unsigned)blocks), dim3(kGroupThreads), 0, st, a, table,
+                     (u64)(capacity - 1), state);
+  DQ_HIP_CHECK(hipGetLastError());
+}
+
+void group_hash_lookup(const GroupKeyCol& a, const unsigned long long* table, int64_t capacity, const int* slot_gid,
+                       int top_gid, int* gid, int blocks, hipStream_t st) {
+  check_key(a, blocks);
+  check_table(capacity);
+  if (a.n == 0) return;
+  hipLaunchKernelGGL(group_hash_lookup_kernel, dim3((unsigned)blocks), dim3(kGroupThreads), 0, st, a, table,
+                     (u64)(capacity - 1), slot_gid, top_gid, gid);
+  DQ_HIP_CHECK(hipGetLastError());
+}
+
+}  // namespace dq4ml

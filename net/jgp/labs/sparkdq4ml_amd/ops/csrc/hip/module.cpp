@@ -15,6 +15,7 @@
 #include "gram.h"
 #include "gram_folds.h"
 #include "quantile.h"
+#include "groupby.h"
 #include "gram_wide.h"
 #include "gram_syrk.h"
 #include "wls_small.h"
@@ -264,6 +265,63 @@ PYBIND11_MODULE(_dq4ml_hip, m) {
                             uintptr_t counts, uintptr_t stream) {
     quantile_pick(C, Q, pass, P<const double>(probs), P<int64_t>(state), P<unsigned long long>(hist),
                   P<double>(values), P<int64_t>(counts), as_stream(stream));
+  });
+  m.def("group_blocks", &group_blocks);
+  // rows per trip, LDS budget in words, aggregate slots per call, default table capacity, direct-range cap
+  m.def("group_limits", []() {
+    return py::make_tuple(kGroupTrip, kGroupLdsWords, kGroupMaxSlots, kGroupDefaultCapacity, kGroupDirectCap);
+  });
+  auto group_key = [](uintptr_t col, int dt, uintptr_t valid, uintptr_t sel, int64_t n) {
+    GroupKeyCol a{};
+    a.col = P<const void>(col);
+    a.valid = P<const uint8_t>(valid);
+    a.sel = P<const uint8_t>(sel);
+    a.n = n;
+    a.dt = dt;
+    return a;
+  };
+  m.def("group_encode_direct", [group_key](uintptr_t col, int dt, uintptr_t valid, uintptr_t sel, int64_t n, int64_t base,
+                                           int64_t span, uintptr_t gid, int blocks, uintptr_t stream) {
+    group_encode_direct(group_key(col, dt, valid, sel, n), base, span, P<int>(gid), blocks, as_stream(stream));
+  });
+  m.def("group_hash_insert", [group_key](uintptr_t col, int dt, uintptr_t valid, uintptr_t sel, int64_t n, uintptr_t table,
+                                         int64_t capacity, uintptr_t state, int blocks, uintptr_t stream) {
+    group_hash_insert(group_key(col, dt, valid, sel, n), P<unsigned long long>(table), capacity,
+                      P<unsigned long long>(state), blocks, as_stream(stream));
+  });
+  m.def("group_hash_lookup", [group_key](uintptr_t col, int dt, uintptr_t valid, uintptr_t sel, int64_t n, uintptr_t table,
+                                         int64_t capacity, uintptr_t slot_gid, int top_gid, uintptr_t gid, int blocks,
+                                         uintptr_t stream) {
+    group_hash_lookup(group_key(col, dt, valid, sel, n), P<const unsigned long long>(table), capacity,
+                      P<const int>(slot_gid), top_gid, P<int>(gid), blocks, as_stream(stream));
+  });
+  // slots: (op, column, dtype, valid, e) each; the words of slot s follow those of slot s - 1
+  m.def("group_agg", [](uintptr_t gid, int G, const std::vector<int>& ops, const std::vector<uintptr_t>& cols,
+                        const std::vector<int>& dts, const std::vector<uintptr_t>& valids, const std::vector<int>& es,
+                        uintptr_t sel, int64_t n, int64_t row_offset, uintptr_t acc, int blocks, uintptr_t stream) {
+    const size_t S = ops.size();
+    if (S < 1 || S > (size_t)kGroupMaxSlots || cols.size() != S || dts.size() != S || valids.size() != S || es.size() != S)
+      throw std::invalid_argument("group_agg: between 1 and " + std::to_string(kGroupMaxSlots) +
+                                  " slots per call, one column, dtype, validity pointer and exponent each");
+    GroupAggArgs a{};
+    int words = 0;
+    for (size_t s = 0; s < S; ++s) {
+      a.op[s] = ops[s];
+      a.col[s] = P<const void>(cols[s]);
+      a.dt[s] = dts[s];
+      a.valid[s] = P<const uint8_t>(valids[s]);
+      a.e[s] = es[s];
+      a.woff[s] = words;
+      words += group_op_words(ops[s]);
+    }
+    a.gid = P<const int>(gid);
+    a.sel = P<const uint8_t>(sel);
+    a.n = n;
+    a.row_offset = row_offset;
+    a.G = G;
+    a.S = (int)S;
+    a.words = words;
+    group_agg(a, P<unsigned long long>(acc), blocks, as_stream(stream));
   });
   m.def("gram_window_fold", [](uintptr_t part, int64_t rows, int gw, uintptr_t flat, uintptr_t stream) {
     gram_window_fold(P<const double>(part), rows, gw, P<double>(flat), as_stream(stream));

@@ -19,7 +19,7 @@ from ..runtime import faststream
 from . import native
 
 __all__ = ["dtype_code", "gram_stats", "compact_indices", "pack_columns", "predict", "regression_metrics",
-           "GRAM_MODES", "quantiles"]
+           "GRAM_MODES", "quantiles", "group_agg_raw", "group_encode_direct", "group_encode_hash"]
 
 _DT = {torch.float64: 0, torch.float32: 1, torch.bfloat16: 2, torch.int32: 3, torch.int64: 4, torch.uint8: 5,
        torch.bool: 5, torch.float16: 6}
@@ -402,11 +402,11 @@ def gram_stats_folds(X, y, sel, k_or_weights, seed: int, granule: int, compute: 
 _QUANT_DTYPES = (torch.float64, torch.float32, torch.int32, torch.int64)
 
 
-def _mask_u8(m: Optional[torch.Tensor], n: int, what: str) -> Optional[torch.Tensor]:
+def _mask_u8(m: Optional[torch.Tensor], n: int, what: str, who: str = "quantiles") -> Optional[torch.Tensor]:
     if m is None:
         return None
     if m.numel() != n or m.dim() != 1:
-        raise ValueError(f"quantiles: {what} must have one entry per row")
+        raise ValueError(f"{who}: {what} must have one entry per row")
     if m.dtype not in (torch.bool, torch.uint8):
         m = m != 0
     return m.contiguous()
@@ -470,6 +470,111 @@ def quantiles(cols, valids, sel, probs, blocks: Optional[int] = None, reduce=Non
         h.quantile_pick(C, Q, k, probs_d.data_ptr(), state.data_ptr(), hist.data_ptr(), values.data_ptr(),
                         counts.data_ptr(), st)
     return values, counts
+
+
+# ------------------------------------------------------------------------------------------
+# grouped aggregation on integer words (csrc/hip/groupby.hip); orchestration in ops/groupby.py
+# ------------------------------------------------------------------------------------------
+_GROUP_DTYPES = (torch.float64, torch.float32, torch.int32, torch.int64, torch.uint8, torch.bool)
+_I64_MIN = -(1 << 63)
+
+
+def _group_col(c: torch.Tensor, n: int, what: str) -> torch.Tensor:
+    if c.dim() != 1 or int(c.numel()) != n:
+        raise ValueError(f"{what}: columns must be 1-D and of one length")
+    if c.dtype not in _GROUP_DTYPES:
+        raise TypeError(f"{what}: unsupported column dtype {c.dtype}")
+    return c.contiguous()
+
+
+def _group_blocks(h, n: int, blocks: Optional[int]) -> int:
+    if blocks is not None and int(blocks) < 1:
+        raise ValueError("blocks must be >= 1")
+    return int(blocks) if blocks else int(h.group_blocks(n))
+
+
+def group_agg_raw(gid, G: int, ops, cols, valids, es, sel, n: int, row_offset: int, init: np.ndarray,
+                  blocks: Optional[int] = None) -> torch.Tensor:
+    """One ``group_agg`` launch: at most ``group_limits()[2]`` slots, ``init`` the identity of each
+    word of a group's row.  Returns the raw ``[G, words]`` int64 accumulators on the device."""
+    h = native.hip()
+    from . import groupby
+
+    assert tuple(h.group_limits()) == groupby.group_limits(), "groupby.py / groupby.h constants differ"
+    n, G = int(n), int(G)
+    live = [t for t in (gid, sel, *cols, *valids) if t is not None]
+    _check_dev(*live)
+    if not live:
+        raise ValueError("group_agg: no device tensor to take the device from")
+    dev = live[0].device
+    if gid is not None and (gid.dtype != torch.int32 or gid.dim() != 1 or int(gid.numel()) != n):
+        raise ValueError("group_agg: gid must be int32 with one entry per row")
+    if G < 1 or G >= 1 << 31:
+        raise ValueError("group_agg: the number of groups must lie in [1, 2^31)")
+    cols = [None if c is None else _group_col(c, n, "group_agg") for c in cols]
+    valids = [_mask_u8(v, n, "a validity mask", "group_agg") for v in valids]
+    sel = _mask_u8(sel, n, "the selection", "group_agg")
+    gid = None if gid is None else gid.contiguous()
+    acc = _h2d(np.ascontiguousarray(init, dtype=np.int64).reshape(1, -1), dev).repeat(G, 1).contiguous()
+    h.group_agg(_ptr(gid), G, [int(o) for o in ops], [_ptr(c) for c in cols],
+                [0 if c is None else dtype_code(c) for c in cols], [_ptr(v) for v in valids], [int(e) for e in es],
+                _ptr(sel), n, int(row_offset), acc.data_ptr(), _group_blocks(h, n, blocks), _stream())
+    return acc
+
+
+def group_encode_direct(col, valid, sel, base: int, span: int, blocks: Optional[int] = None) -> torch.Tensor:
+    """``gid`` (int32) of an integer / boolean key column whose live values lie in
+    ``[base, base + span)``: -1 dead, 0 null, else ``key - base + 1``."""
+    h = native.hip()
+    _check_dev(col, valid, sel)
+    n = int(col.numel())
+    col = _group_col(col, n, "group_encode")
+    valid, sel = _mask_u8(valid, n, "the validity mask", "group_encode"), _mask_u8(sel, n, "the selection", "group_encode")
+    gid = torch.empty(n, dtype=torch.int32, device=col.device)
+    h.group_encode_direct(col.data_ptr(), dtype_code(col), _ptr(valid), _ptr(sel), n, int(base), int(span),
+                          gid.data_ptr(), _group_blocks(h, n, blocks), _stream())
+    return gid
+
+
+def group_encode_hash(col, valid, sel, capacity: int, max_capacity: int, union=None, blocks: Optional[int] = None):
+    """Hash mode of ``group_encode``: ``(gid int32 [n], sorted signed order keys int64 [K], capacity
+    used)``.  ``gid`` is -1 dead, 0 null, else 1 + the rank of the row's key among the sorted keys.
+    The insert launch fills a table of ``capacity`` u64 slots; past half full the launcher retries
+    with 8x the capacity (at most ``max_capacity``).  ``union`` (sorted local keys -> sorted keys of
+    all ranks) widens the key list before the lookup launch."""
+    h = native.hip()
+    _check_dev(col, valid, sel)
+    n = int(col.numel())
+    col = _group_col(col, n, "group_encode")
+    valid, sel = _mask_u8(valid, n, "the validity mask", "group_encode"), _mask_u8(sel, n, "the selection", "group_encode")
+    dev = col.device
+    nb, st, dt = _group_blocks(h, n, blocks), _stream(), dtype_code(col)
+    cap = int(capacity)
+    while True:
+        table = torch.full((cap,), -1, dtype=torch.int64, device=dev)
+        state = torch.zeros(4, dtype=torch.int64, device=dev)
+        h.group_hash_insert(col.data_ptr(), dt, _ptr(valid), _ptr(sel), n, table.data_ptr(), cap, state.data_ptr(), nb, st)
+        count, overflow, _has_null, has_top = (int(v) for v in state.tolist())  # the group count sizes the output
+        if not overflow:
+            break
+        if cap >= max_capacity:
+            raise RuntimeError("group_encode: the hash table overflowed at its largest capacity")
+        cap = min(cap * 8, int(max_capacity))
+    # table-sized work: compact the occupied slots, sort the unique keys, build slot -> gid
+    occ = torch.nonzero(table != -1, as_tuple=False).flatten()
+    skeys = table[occ] ^ _I64_MIN  # signed order == unsigned key order
+    keys = torch.sort(skeys).values
+    if has_top:
+        keys = torch.cat([keys, torch.full((1,), (1 << 63) - 1, dtype=torch.int64, device=dev)])
+    if union is not None:
+        keys = union(keys)
+    assert count == int(occ.numel())
+    slot_gid = torch.full((cap,), -1, dtype=torch.int32, device=dev)
+    slot_gid[occ] = (torch.searchsorted(keys, skeys) + 1).to(torch.int32)
+    gid = torch.empty(n, dtype=torch.int32, device=dev)
+    h.group_hash_lookup(col.data_ptr(), dt, _ptr(valid), _ptr(sel), n, table.data_ptr(), cap, slot_gid.data_ptr(),
+                        int(keys.numel()), gid.data_ptr(), nb, st)
+    return gid, keys, cap
 
 
 def gram_skinny_cols(parts: List[torch.Tensor], y, w, sel, blocks: Optional[int] = None):

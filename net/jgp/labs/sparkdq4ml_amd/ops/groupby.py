@@ -1,0 +1,416 @@
+"""Grouped aggregation on integer words: ``group_encode`` / ``group_agg`` and their finalisation.
+
+Device tensors run the ``groupby.hip`` kernels through ``ops/device.py``; host tensors run the
+numpy forms below, which do exactly the kernels' arithmetic: the raw accumulators of the two
+engines are bit-identical, and so is every result built from them (the finalisation is one piece
+of torch integer code for both).
+
+Keys.  A key value becomes an order-preserving 64-bit key.  Doubles and floats use the IEEE bits
+of the value as a double with ``-0.0`` folded into ``+0.0`` and every NaN mapped to one canonical
+NaN that orders above ``+inf`` (Spark 3's grouping rule; 2.4 kept them apart, SPARK-26021);
+integers and booleans are biased by the sign bit.  Python holds a key as the *signed* order key
+(the u64 key with its top bit flipped, as int64), which for an integer column is the value itself.
+Null keys form one group, slot 0; slots ascend with the key.
+
+Accumulators.  Every word is an int64 updated by an integer add / or / max / min, so the result
+does not depend on the grid, the schedule or a shard split.  A double sum is kept in fixed point:
+with ``e = frexp(M)[1]`` of the largest finite ``|x|`` of the column, ``x * 2^(128 - e)`` is cut
+into four signed 32-bit limbs (every step exact in f64), limb k is an i64 add, and NaN / +inf /
+-inf set flag bits instead.  Values at or above ``2^(e - 75)`` in magnitude are represented
+exactly, smaller ones are truncated toward zero by less than ``2^(e - 128)`` each.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import List, Optional, Sequence
+
+import numpy as np
+import torch
+
+__all__ = ["ROWS", "COUNT", "SUM_I", "SUM_F", "MIN", "MAX", "FIRST", "ABSMAX", "GroupEncoding", "group_limits",
+           "group_encode", "group_encode_columns", "group_agg", "group_scale", "op_words", "word_kinds",
+           "finalize_sum", "keys_to_values", "hash_home"]
+
+ROWS, COUNT, SUM_I, SUM_F, MIN, MAX, FIRST, ABSMAX = range(8)
+K_ADD, K_OR, K_MAX, K_MIN = range(4)
+
+# groupby.h (checked against the extension's group_limits() on the device path)
+GROUP_TRIP = 1024
+GROUP_LDS_WORDS = 4096
+GROUP_MAX_SLOTS = 8
+GROUP_DEFAULT_CAPACITY = 1 << 16
+GROUP_DIRECT_CAP = 1 << 20
+
+_I64_MIN = -(1 << 63)
+_I64_MAX = (1 << 63) - 1
+_NAN_BITS = 0x7FF8000000000000
+_INF_BITS = 0x7FF0000000000000
+_FLOATS = (torch.float64, torch.float32)
+_INTS = (torch.int32, torch.int64, torch.uint8, torch.bool)
+
+
+def group_limits():
+    """(rows per trip, LDS budget in words, aggregate slots per call, default table capacity,
+    direct-range cap)."""
+    return GROUP_TRIP, GROUP_LDS_WORDS, GROUP_MAX_SLOTS, GROUP_DEFAULT_CAPACITY, GROUP_DIRECT_CAP
+
+
+def op_words(op: int) -> int:
+    return 5 if op == SUM_F else 1
+
+
+def word_kinds(ops: Sequence[int]) -> List[int]:
+    """How each word of a group's accumulator row is combined (add / or / max / min)."""
+    out = []
+    for op in ops:
+        if op == SUM_F:
+            out += [K_ADD] * 4 + [K_OR]
+        elif op in (MIN, FIRST):
+            out.append(K_MIN)
+        elif op in (MAX, ABSMAX):
+            out.append(K_MAX)
+        else:
+            out.append(K_ADD)
+    return out
+
+
+def _identity(kinds) -> np.ndarray:
+    return np.array([-1 if k == K_MIN else 0 for k in kinds], dtype=np.int64)
+
+
+def hash_home(skey: int, capacity: int) -> int:
+    """Home slot of a signed order key in a table of ``capacity`` slots (the kernels' hash)."""
+    key = (int(skey) ^ _I64_MIN) & ((1 << 64) - 1)
+    return ((key * 0x9E3779B97F4A7C15 & ((1 << 64) - 1)) >> 20) & (capacity - 1)
+
+
+# ------------------------------------------------------------------------------------------
+# numpy twins
+# ------------------------------------------------------------------------------------------
+def _np(t) -> Optional[np.ndarray]:
+    return None if t is None else t.detach().numpy()
+
+
+def _skeys_np(x: np.ndarray, fold: bool) -> np.ndarray:
+    """Signed order keys of a column (int64)."""
+    if x.dtype.kind in "iub":
+        return x.astype(np.int64)
+    b = x.astype(np.float64).view(np.int64).copy()
+    b[(b & _I64_MAX) > _INF_BITS] = _NAN_BITS
+    if fold:
+        b[b == _I64_MIN] = 0
+    return np.where(b >= 0, b, ~b ^ np.int64(_I64_MIN))
+
+
+def _live_np(sel, n: int) -> np.ndarray:
+    return np.ones(n, dtype=bool) if sel is None else (_np(sel) != 0)
+
+
+def _agg_host(gid, G, ops, cols, valids, es, sel, n, row_offset, init):
+    acc = np.tile(np.asarray(init, dtype=np.int64).reshape(1, -1), (G, 1))
+    live = _live_np(sel, n)
+    g = np.zeros(n, dtype=np.int64)
+    if gid is not None:
+        g = _np(gid).astype(np.int64)
+        live = live & (g >= 0) & (g < G)
+    w = 0
+    with np.errstate(over="ignore", invalid="ignore"):
+        for op, c, v, e in zip(ops, cols, valids, es):
+            ok = live if (v is None or op in (ROWS, FIRST)) else live & (_np(v) != 0)
+            x = None if c is None else _np(c)
+            if op in (ROWS, COUNT):
+                np.add.at(acc[:, w], g[ok], 1)
+            elif op == SUM_I:
+                np.add.at(acc[:, w], g[ok], x[ok].astype(np.int64))
+            elif op in (MIN, MAX):
+                k = _skeys_np(x[ok], False)
+                m = np.full(G, _I64_MAX if op == MIN else _I64_MIN, dtype=np.int64)
+                (np.minimum if op == MIN else np.maximum).at(m, g[ok], k)
+                acc[:, w] = m ^ np.int64(_I64_MIN)
+            elif op == FIRST:
+                m = acc[:, w].view(np.uint64)
+                np.minimum.at(m, g[ok], (np.nonzero(ok)[0] + int(row_offset)).astype(np.uint64))
+            elif op == ABSMAX:
+                b = x[ok].astype(np.float64).view(np.int64) & np.int64(_I64_MAX)
+                fin = b < _INF_BITS
+                np.maximum.at(acc[:, w], g[ok][fin], b[fin])
+            else:  # SUM_F
+                xs, gs = x[ok].astype(np.float64), g[ok]
+                fin = np.isfinite(xs)
+                t = np.ldexp(xs[fin], 32 - int(e))
+                for k in range(4):
+                    c_k = np.trunc(t)
+                    np.add.at(acc[:, w + k], gs[fin], c_k.astype(np.int64))
+                    t = np.ldexp(t - c_k, 32)
+                flag = np.where(np.isnan(xs), 1, np.where(xs > 0, 2, 4))[~fin].astype(np.int64)
+                np.bitwise_or.at(acc[:, w + 4], gs[~fin], flag)
+            w += op_words(op)
+    return torch.from_numpy(acc)
+
+
+def _direct_host(col, valid, sel, base, span):
+    x = _np(col).astype(np.int64)
+    live = _live_np(sel, x.size)
+    ok = live if valid is None else live & (_np(valid) != 0)
+    off = x - np.int64(base)  # (wraps like the kernel's unsigned subtraction)
+    inside = (off >= 0) & (off < span)
+    g = np.where(~live, -1, np.where(~ok, 0, np.where(inside, off + 1, -1)))
+    return torch.from_numpy(g.astype(np.int32))
+
+
+def _hash_host(col, valid, sel, union):
+    x = _np(col)
+    live = _live_np(sel, x.size)
+    ok = live if valid is None else live & (_np(valid) != 0)
+    k = _skeys_np(x, True)
+    keys = torch.from_numpy(np.unique(k[ok]))
+    if union is not None:
+        keys = union(keys)
+    g = np.where(~live, -1, np.where(~ok, 0, np.searchsorted(keys.numpy(), k) + 1))
+    return torch.from_numpy(g.astype(np.int32)), keys
+
+
+# ------------------------------------------------------------------------------------------
+# group_agg
+# ------------------------------------------------------------------------------------------
+def _n_rows(gid, sel, slots) -> int:
+    for t in (gid, sel):
+        if t is not None:
+            return int(t.numel())
+    for s in slots:
+        for t in (s[1], s[2]):
+            if t is not None:
+                return int(t.numel())
+    raise ValueError("group_agg: nothing tells the row count (no gid, selection, column or mask)")
+
+
+def _is_cuda(*ts) -> bool:
+    return any(t is not None and t.is_cuda for t in ts)
+
+
+def _agg_call(gid, G, ops, cols, valids, es, sel, n, row_offset, blocks):
+    init = _identity(word_kinds(ops))
+    if _is_cuda(gid, sel, *cols, *valids):
+        from . import device
+
+        return device.group_agg_raw(gid, G, ops, cols, valids, es, sel, n, row_offset, init, blocks)
+    return _agg_host(gid, G, ops, cols, valids, es, sel, n, row_offset, init)
+
+
+def group_scale(cols, valids, sel, blocks: Optional[int] = None, reduce=None) -> List[int]:
+    """The fixed-point exponent of each column: ``frexp(M)[1]`` of the largest finite ``|x|`` among
+    its live non-null rows over all groups (and, through ``reduce``, all ranks); 0 when there is
+    none.  One ``ABSMAX`` pass and one host read."""
+    if not cols:
+        return []
+    acc, off = group_agg(None, 1, [(ABSMAX, c, v, 0) for c, v in zip(cols, valids)], sel, blocks=blocks, reduce=reduce)
+    bits = acc[0, off].cpu().numpy().astype(np.int64)
+    return [int(x) for x in np.frexp(bits.view(np.float64))[1]]  # (frexp(0) = (0, 0))
+
+
+def group_agg(gid, G: int, slots, sel=None, row_offset: int = 0, blocks: Optional[int] = None, reduce=None, n=None):
+    """Raw integer accumulators of the aggregate ``slots`` per group.
+
+    ``gid``: int32 per row from ``group_encode`` (-1: dead row), or None: every live row is group
+    0.  ``slots``: ``(op, column, valid, e)`` each -- ``column`` / ``valid`` None where the op reads
+    none, ``e`` the fixed-point exponent of a ``SUM_F`` slot (None: measured here by an ``ABSMAX``
+    pre-pass, see ``group_scale``).  A ``ROWS`` slot is always put first.  Returns ``(acc, offsets)``:
+    ``acc`` int64 ``[G, words]`` with word 0 the live rows of the group, ``offsets[i]`` the first
+    word of ``slots[i]``.  ``reduce(acc, kinds)`` combines the ranks' accumulators."""
+    slots = [tuple(s) + (None,) * (4 - len(s)) for s in slots]
+    n = _n_rows(gid, sel, slots) if n is None else int(n)
+    need = [i for i, s in enumerate(slots) if s[0] == SUM_F and s[3] is None]
+    if need:
+        es = group_scale([slots[i][1] for i in need], [slots[i][2] for i in need], sel, blocks, reduce)
+        for i, e in zip(need, es):
+            slots[i] = slots[i][:3] + (e,)
+    if any(s[0] == SUM_F for s in slots) and n >= 1 << 31:
+        raise ValueError("group_agg: a fixed-point sum takes fewer than 2^31 rows per call")
+    parts, offsets, w = [], [], 1
+    per = GROUP_MAX_SLOTS - 1  # every call carries ROWS in slot 0
+    for i in range(0, max(len(slots), 1), per):
+        chunk = [(ROWS, None, None, 0)] + slots[i:i + per]
+        ops = [s[0] for s in chunk]
+        a = _agg_call(gid, int(G), ops, [s[1] for s in chunk], [s[2] for s in chunk], [int(s[3] or 0) for s in chunk],
+                      sel, n, row_offset, blocks)
+        parts.append(a if i == 0 else a[:, 1:])
+        for s in chunk[1:]:
+            offsets.append(w)
+            w += op_words(s[0])
+    acc = parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)
+    if reduce is not None:
+        acc = reduce(acc, [K_ADD] + word_kinds([s[0] for s in slots]))
+    return acc, offsets
+
+
+# ------------------------------------------------------------------------------------------
+# group_encode
+# ------------------------------------------------------------------------------------------
+@dataclass
+class GroupEncoding:
+    """``gid``: int32 per row (-1 dead, 0 null key, else the key's slot); ``G`` slots; ``keys``:
+    the signed order key of each slot (int64 ``[G]`` on the rows' device, slot 0 unused).  A direct
+    encoding has a slot for every value of the live range, so some may receive no row: drop them
+    by the ``ROWS`` word after aggregation."""
+    gid: torch.Tensor
+    G: int
+    keys: torch.Tensor
+    mode: str
+    dtype: torch.dtype
+    capacity: Optional[int] = None
+
+
+def _next_pow2(v: int) -> int:
+    return 1 << max(1, int(v - 1).bit_length())
+
+
+def group_encode(col: torch.Tensor, valid=None, sel=None, capacity: Optional[int] = None, blocks: Optional[int] = None,
+                 reduce=None, union=None, mode: Optional[str] = None) -> GroupEncoding:
+    """Group ids of one key column (f64 / f32 / i32 / i64 / bool / u8).  Integer and boolean keys
+    whose live range is at most ``GROUP_DIRECT_CAP`` index their slot directly (``mode`` "hash"
+    overrides); the rest go through the hash table, first of ``capacity`` slots.  ``reduce`` /
+    ``union`` make the slots global over ranks: the range is all-reduced, the sorted unique keys
+    are exchanged."""
+    if col.dim() != 1:
+        raise ValueError("group_encode: the key column must be 1-D")
+    if col.dtype not in _FLOATS + _INTS:
+        raise TypeError(f"group_encode: unsupported key dtype {col.dtype}")
+    n = int(col.numel())
+    if n >= 1 << 31:
+        raise ValueError("group_encode: fewer than 2^31 rows per call")
+    dev = col.device
+    if col.dtype in _INTS and mode != "hash":
+        acc, off = group_agg(None, 1, [(MIN, col, valid), (MAX, col, valid), (COUNT, None, valid)], sel, blocks=blocks,
+                             reduce=reduce, n=n)
+        lo, hi, cnt = (int(v) for v in acc[0, off].tolist())
+        lo, hi = lo ^ _I64_MIN, hi ^ _I64_MIN
+        lo, hi = (lo + (1 << 63)) % (1 << 64) - (1 << 63), (hi + (1 << 63)) % (1 << 64) - (1 << 63)
+        span = hi - lo + 1 if cnt > 0 else 0
+        if span <= GROUP_DIRECT_CAP:
+            base = lo if cnt > 0 else 0
+            if col.is_cuda:
+                from . import device
+
+                gid = device.group_encode_direct(col, valid, sel, base, span, blocks)
+            else:
+                gid = _direct_host(col, valid, sel, base, span)
+            keys = torch.arange(span + 1, dtype=torch.int64, device=dev) - 1 + base  # (slot 0 is unused)
+            return GroupEncoding(gid, span + 1, keys, "direct", col.dtype)
+    if mode == "direct":
+        raise ValueError("group_encode: direct mode takes integer keys of a live range within the cap")
+    cap = _next_pow2(int(capacity)) if capacity else GROUP_DEFAULT_CAPACITY
+    if cap < 2:
+        raise ValueError("group_encode: capacity must be at least 2")
+    used = None
+    if col.is_cuda:
+        from . import device
+
+        gid, keys, used = device.group_encode_hash(col, valid, sel, cap, max(cap, _next_pow2(2 * max(n, 1))), union, blocks)
+    else:
+        gid, keys = _hash_host(col, valid, sel, union)
+    keys = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), keys.to(dev)])
+    return GroupEncoding(gid, int(keys.numel()), keys, "hash", col.dtype, used)
+
+
+def keys_to_values(keys: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    """The column values (of ``dtype``) behind signed order keys."""
+    if dtype in _FLOATS:
+        bits = torch.where(keys >= 0, keys, ~(keys ^ _I64_MIN))
+        return bits.view(torch.float64).to(dtype)
+    return keys.to(dtype) if dtype != torch.bool else keys != 0
+
+
+def group_encode_columns(cols, valids=None, sel=None, capacity: Optional[int] = None, blocks: Optional[int] = None,
+                         reduce=None, union=None):
+    """Group ids of a key of several columns: ``(gid, G, [(values, valid) per column])`` with the
+    key values of every slot (``valid`` False where that column's key is null).  Each column is
+    encoded on its own, the codes are combined in mixed radix into one int64 (an elementwise op) and
+    the combination is encoded once more."""
+    cols = list(cols)
+    valids = [None] * len(cols) if valids is None else list(valids)
+    if not cols:
+        raise ValueError("group_encode: no key column")
+    encs = [group_encode(c, v, sel, capacity, blocks, reduce, union) for c, v in zip(cols, valids)]
+    if len(encs) == 1:
+        e = encs[0]
+        slot = torch.arange(e.G, device=e.keys.device)
+        return e.gid, e.G, [(keys_to_values(e.keys, e.dtype), slot > 0)]
+    total = 1
+    for e in encs:
+        total *= e.G
+    if total >= 1 << 63:
+        raise ValueError("group_encode: the product of the key columns' cardinalities does not fit in 63 bits")
+    code, stride, strides = None, 1, []
+    for e in reversed(encs):  # the first column is the most significant digit
+        term = e.gid.to(torch.int64) * stride
+        code = term if code is None else code + term
+        strides.append(stride)
+        stride *= e.G
+    strides.reverse()
+    c = group_encode(code, None, sel, capacity, blocks, reduce, union)  # (a dead row's code is never read)
+    out = []
+    for e, s in zip(encs, strides):
+        slot = (c.keys // s) % e.G
+        slot[0] = 0
+        out.append((keys_to_values(e.keys, e.dtype)[slot], slot > 0))
+    return c.gid, c.G, out
+
+
+# ------------------------------------------------------------------------------------------
+# finalisation (G-sized torch integer code, the same for both engines)
+# ------------------------------------------------------------------------------------------
+def _ldexp2(m: torch.Tensor, s: torch.Tensor) -> torch.Tensor:
+    """m * 2^s for |s| beyond one power's range: two exact-or-final steps."""
+    h = torch.div(s, 2, rounding_mode="floor")
+    return torch.ldexp(torch.ldexp(m, h), s - h)
+
+
+def finalize_sum(limbs: torch.Tensor, flags: torch.Tensor, e) -> torch.Tensor:
+    """The double nearest (ties to even) to ``T * 2^(e - 128)``, ``T = sum_k limbs[:, k] *
+    2^(32 * (3 - k))``, per group; overflow gives +-inf, then the flags override: NaN or both
+    infinities give NaN, one infinity gives that infinity.  ``limbs`` int64 ``[G, 4]``."""
+    M = 0xFFFFFFFF
+    a = [limbs[:, k].clone() for k in range(4)]
+    # carry-normalise: a0 keeps the sign, the lower three become digits in [0, 2^32)
+    for k in (3, 2, 1):
+        a[k - 1] = a[k - 1] + (a[k] >> 32)
+        a[k] = a[k] & M
+    neg = a[0] < 0
+    # magnitude: two's complement of the four-word number where it is negative
+    d = [torch.where(neg, ~x & M, x) for x in a[1:]]
+    hi = torch.where(neg, ~a[0], a[0])
+    carry = neg.to(torch.int64)
+    for k in (2, 1, 0):
+        v = d[k] + carry
+        carry = v >> 32
+        d[k] = v & M
+    hi = hi + carry
+    z = torch.zeros_like(hi)
+    D = torch.stack([hi >> 32, hi & M, d[0], d[1], d[2], z, z, z], dim=1)  # 32-bit digits, weight 2^(32 * (4 - i))
+    nz = D != 0
+    i = torch.argmax(nz.to(torch.int8), dim=1)  # first non-zero digit (0 when there is none)
+    idx = i.unsqueeze(1)
+    d0, d1, d2 = (torch.gather(D, 1, idx + j).squeeze(1) for j in range(3))
+    tail = torch.flip(torch.cumsum(torch.flip(nz.to(torch.int64), [1]), 1), [1])  # non-zero digits at or after i
+    sticky = torch.gather(tail, 1, idx + 3).squeeze(1) > 0
+    lz = 32 - torch.frexp(d0.to(torch.float64))[1].to(torch.int64)  # leading zeros of d0 in 32 bits
+    # W: the top 63 bits of d0:d1:d2 with the leading one at bit 62
+    b1 = d1 << 31
+    sh1 = 32 - lz
+    sh2 = 33 - lz
+    W = (d0 << (lz + 31)) + (b1 >> sh1) + (d2 >> sh2)
+    one = torch.ones_like(lz)
+    sticky = sticky | ((b1 & ((one << sh1) - 1)) != 0) | ((d2 & ((one << sh2) - 1)) != 0)
+    mant = W >> 10
+    rb = W & 0x3FF
+    up = (rb > 0x200) | ((rb == 0x200) & (sticky | ((mant & 1) != 0)))
+    mant = mant + up.to(torch.int64)
+    e_t = torch.as_tensor(e, dtype=torch.int64, device=limbs.device)
+    scale = 43 - lz + 32 * (2 - i) + e_t - 128
+    val = _ldexp2(mant.to(torch.float64), scale)
+    val = torch.where(neg, -val, val)
+    nan = ((flags & 1) != 0) | (((flags & 2) != 0) & ((flags & 4) != 0))
+    inf = torch.full_like(val, float("inf"))
+    val = torch.where((flags & 2) != 0, inf, val)
+    val = torch.where((flags & 4) != 0, -inf, val)
+    return torch.where(nan, torch.full_like(val, float("nan")), val)

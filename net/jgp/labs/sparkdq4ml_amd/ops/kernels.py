@@ -10,6 +10,7 @@ Ops:
   K4  ``pack_columns``       columns -> feature-major [d, n] matrix (cast)
   K5  ``gram_stats``         WLS sufficient statistics (MFMA Gram) of [X | 1 | y] with weights/mask
   K5q ``quantiles``          exact order statistics of C columns x Q probabilities (radix select)
+  K5g ``group_encode`` / ``group_agg``  group ids of key columns, integer-word grouped aggregates
   K7+K8 ``predict`` / ``regression_metrics``  fused GEMV + metric reductions
 """
 from __future__ import annotations
@@ -20,9 +21,11 @@ import numpy as np
 import torch
 
 from . import native
+from .groupby import group_agg, group_encode, group_encode_columns, group_limits, group_scale  # noqa: F401  (K5g)
 
 __all__ = ["selected_indices", "pack_columns", "gram_stats", "predict", "regression_metrics",
-           "gram_layout_size", "gram_stats_folds", "fold_ids", "fold_thresholds", "fold_seed", "quantiles"]
+           "gram_layout_size", "gram_stats_folds", "fold_ids", "fold_thresholds", "fold_seed", "quantiles", "group_encode", "group_encode_columns",
+           "group_agg", "group_scale", "group_limits"]
 
 
 def _on_gpu(t: torch.Tensor) -> bool:

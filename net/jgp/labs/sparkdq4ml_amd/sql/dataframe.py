@@ -351,6 +351,45 @@ class DataFrame:
             raise ValueError("number of column names does not match")
         return self._with(Project(self._plan, [Alias(ColRef(o), n) for o, n in zip(self.columns, names)]))
 
+    # ---- grouping -------------------------------------------------------------------------
+    def groupBy(self, *cols):
+        """``RelationalGroupedDataset`` over the key columns (names or Columns); none: one global
+        group.  Groups follow Spark 3's rule for floating keys (-0.0 = 0.0, all NaN equal), null
+        keys form one group, and results come in key order, null first."""
+        from .aggregates import GroupedData
+
+        if len(cols) == 1 and isinstance(cols[0], (list, tuple)):
+            cols = cols[0]
+        keys = [ColRef(c) if isinstance(c, str) else to_expr(c) for c in cols]
+        self._check_refs(keys)
+        return GroupedData(self, keys)
+
+    groupby = groupBy
+
+    def agg(self, *exprs):
+        """Global aggregates: one row, even over an empty frame (counts 0, the rest null)."""
+        return self.groupBy().agg(*exprs)
+
+    def distinct(self) -> "DataFrame":
+        from .plan import Aggregate
+
+        return self._with(Aggregate(self._plan, self.columns, []))
+
+    def dropDuplicates(self, subset=None) -> "DataFrame":
+        """Keeps the first live row of every group of ``subset`` (default: all columns) in row
+        order; the table keeps its rows and only the selection vector narrows."""
+        from .plan import Deduplicate
+
+        if subset is not None and (isinstance(subset, str) or not isinstance(subset, (list, tuple))):
+            raise TypeError("Parameter 'subset' must be a list of columns")
+        names = list(subset) if subset is not None else self.columns
+        self._check_refs([ColRef(c) for c in names])
+        if not names:
+            return self
+        return self._with(Deduplicate(self._plan, names))
+
+    drop_duplicates = dropDuplicates
+
     # ---- persistence -----------------------------------------------------------------------
     def cache(self):
         execute(self._plan, self.sparkSession)

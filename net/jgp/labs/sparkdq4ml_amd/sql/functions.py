@@ -5,7 +5,8 @@ from __future__ import annotations
 from .column import Column
 from .expressions import CaseWhen, Coalesce, ColRef, IsNull, Lit, UdfCall, to_expr
 
-__all__ = ["col", "column", "lit", "callUDF", "call_udf", "udf", "when", "coalesce", "isnull", "expr"]
+__all__ = ["col", "column", "lit", "callUDF", "call_udf", "udf", "when", "coalesce", "isnull", "expr",
+           "count", "sum", "avg", "mean", "min", "max"]
 
 
 def col(name: str) -> Column:
@@ -37,6 +38,38 @@ def coalesce(*cols) -> Column:
 
 def isnull(c) -> Column:
     return Column(IsNull(c._expr if isinstance(c, Column) else ColRef(c)))
+
+
+def _agg(fn: str, c) -> Column:
+    from .aggregates import AggExpr
+
+    if fn == "count" and isinstance(c, str) and c == "*":
+        return Column(AggExpr("count", None))
+    return Column(AggExpr(fn, ColRef(c) if isinstance(c, str) else to_expr(c)))
+
+
+def count(c="*") -> Column:
+    """``count(col)``: the non-null rows; ``count("*")``: all rows (named ``count(1)``)."""
+    return _agg("count", c)
+
+
+def sum(c) -> Column:  # noqa: A001 (pyspark's names)
+    return _agg("sum", c)
+
+
+def avg(c) -> Column:
+    return _agg("avg", c)
+
+
+mean = avg
+
+
+def min(c) -> Column:  # noqa: A001
+    return _agg("min", c)
+
+
+def max(c) -> Column:  # noqa: A001
+    return _agg("max", c)
 
 
 def expr(text: str) -> Column:

@@ -15,8 +15,10 @@ from typing import List, Optional, Tuple
 
 from .expressions import (Alias, AnalysisException, BinOp, CaseWhen, Cast, ColRef, Coalesce,
                           Expr, If, IsNotNull, IsNull, Lit, Neg, Not, UdfCall)
+from .aggregates import AggExpr, build_aggregate, contains_aggregate
 from .fn import MathFn, BUILTIN_MATH
-from .plan import Filter, Limit, Project
+from .plan import Aggregate, Filter, Limit, Project, output_name
+from .skey import expr_key
 
 __all__ = ["parse_expression", "parse_select_item", "plan_sql", "ParseException"]
 
@@ -35,7 +37,7 @@ _TOKEN = re.compile(r"""
 """, re.VERBOSE)
 
 _KEYWORDS = {"select", "from", "where", "as", "and", "or", "not", "cast", "is", "null", "true", "false",
-             "case", "when", "then", "else", "end", "limit", "between", "in", "distinct", "like"}
+             "case", "when", "then", "else", "end", "limit", "between", "in", "distinct", "like", "group", "by"}
 
 
 def _tokenize(text: str) -> List[Tuple[str, str]]:
@@ -95,7 +97,7 @@ class _Parser:
         """The statement's syntax: (select items, view name, alias, WHERE, LIMIT) -- nothing of
         the catalog is read here, so the result is cached per text (``plan_sql``)."""
         self.expect("kw", "select")
-        self.accept("kw", "distinct")
+        distinct = bool(self.accept("kw", "distinct"))
         items = self.select_list()
         self.expect("kw", "from")
         tname = self.expect("ident")[1]
@@ -107,6 +109,12 @@ class _Parser:
         where = None
         if self.accept("kw", "where"):
             where = self.expr()
+        group = None
+        if self.accept("kw", "group"):
+            self.expect("kw", "by")
+            group = [self.expr()]
+            while self.accept("op", ","):
+                group.append(self.expr())
         limit = None
         if self.accept("kw", "limit"):
             limit = int(self.expect("num")[1])
@@ -115,7 +123,9 @@ class _Parser:
         items = [(_strip_qual(e, quals)) for e in items]
         if where is not None:
             where = _strip_qual(where, quals)
-        return items, tname, where, limit
+        if group is not None:
+            group = [_strip_qual(e, quals) for e in group]
+        return items, tname, where, limit, distinct, group
 
     def select_list(self):
         items = [self.select_item()]
@@ -266,6 +276,9 @@ class _Parser:
             return e
         if kind == "ident":
             if self.accept("op", "("):
+                if val.lower() == "count" and self.accept("op", "*"):
+                    self.expect("op", ")")
+                    return AggExpr("count", None)
                 args = []
                 if not self.accept("op", ")"):
                     args.append(self.expr())
@@ -292,6 +305,10 @@ def _function(name: str, args: List[Expr]) -> Expr:
         return If(*args)
     if low in BUILTIN_MATH:
         return MathFn(low, args)
+    if low in ("count", "sum", "avg", "mean", "min", "max"):
+        if len(args) != 1:
+            raise AnalysisException(f"Invalid number of arguments for function {low}")
+        return AggExpr(low, args[0])
     return UdfCall(name, args)
 
 
@@ -334,7 +351,7 @@ def _bind_query(syntax, text: str, session):
     replaced between two runs of the same text binds to the new plan).  Expression trees are
     immutable once parsed, so plans may share them; a statement bound over a view of the same
     structure (sql/skey.py) reuses the analyzed nodes (fresh copies: no result is shared)."""
-    items, tname, where, limit = syntax
+    items, tname, where, limit, distinct, group = syntax
     plan = session.catalog._views.get(tname.lower())
     if plan is None:
         raise AnalysisException(f"Table or view not found: {tname}; line 1 pos {text.lower().find(tname.lower())}")
@@ -345,7 +362,7 @@ def _bind_query(syntax, text: str, session):
         for t in tmpl:
             plan = t.fresh(plan)
         return plan
-    out = _bind_new(items, where, limit, plan)
+    out = _bind_new(items, where, limit, plan, distinct, group)
     if key is not None and out.skey() is not None:
         nodes, p = [], out
         while p is not plan:
@@ -363,8 +380,10 @@ def _bind_query(syntax, text: str, session):
     return out
 
 
-def _bind_new(items, where, limit, plan):
+def _bind_new(items, where, limit, plan, distinct=False, group=None):
     if where is not None:
+        if contains_aggregate(where):
+            raise AnalysisException("Aggregate/Window/Generate expressions are not valid in where clause of the query.")
         plan = Filter(plan, where)
     exprs = []
     for e in items:
@@ -372,13 +391,48 @@ def _bind_new(items, where, limit, plan):
             exprs += [ColRef(n) for n in plan.schema().names]
         else:
             exprs.append(e)
-    plan = Project(plan, exprs)
-    cs = plan.child.schema()
-    for e in exprs:
-        e.data_type(cs)
+    if group is not None or any(contains_aggregate(e) for e in exprs):
+        plan = _bind_grouped(exprs, group or [], plan)
+    else:
+        plan = Project(plan, exprs)
+        cs = plan.child.schema()
+        for e in exprs:
+            e.data_type(cs)
+    if distinct:  # the distinct rows of the select list
+        plan = Aggregate(plan, plan.schema().names, [])
     if limit is not None:
         plan = Limit(plan, limit)
     return plan
+
+
+def _bind_grouped(exprs, group, plan):
+    """``SELECT key..., agg(...) ... GROUP BY key...``: the aggregate over the grouping
+    expressions, then a Project that puts the select list in its order under its names.  A select
+    item that is neither a grouping expression nor an aggregate is an AnalysisException."""
+    def same(a, b):
+        ka, kb = expr_key(a), expr_key(b)
+        if ka is not None and ka == kb:
+            return True
+        return a.sql_name().lower() == b.sql_name().lower()
+
+    aggs, out = [], []
+    for i, e in enumerate(exprs):
+        base = e.child if isinstance(e, Alias) else e
+        if isinstance(base, AggExpr):
+            name = f"_agg_out_{i}"
+            aggs.append(Alias(base, name))
+            out.append(Alias(ColRef(name), output_name(e)))
+            continue
+        if contains_aggregate(base):
+            raise AnalysisException(f"expressions over aggregates are not supported: {base.sql_name()}")
+        k = next((g for g in group if same(g, base)), None)
+        if k is None:
+            raise AnalysisException(f"expression '{base.sql_name()}' is neither present in the group by, nor is it an "
+                                    f"aggregate function. Add to group by or wrap in first() (or first_value) if you "
+                                    f"don't care which value you get.;")
+        out.append(Alias(ColRef(output_name(k)), output_name(e)))
+    agg = build_aggregate(plan, group, aggs)
+    return Project(agg, out)
 
 
 _SYNTAX: dict = {}

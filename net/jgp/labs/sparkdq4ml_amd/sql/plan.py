@@ -18,7 +18,8 @@ from .skey import expr_key, exprs_key, intern
 from .table import ColumnData, Table
 from .types import BooleanType, StructField, StructType
 
-__all__ = ["LogicalPlan", "LocalRelation", "CsvScanRelation", "Project", "Filter", "Limit", "Union", "execute", "prune_columns"]
+__all__ = ["LogicalPlan", "LocalRelation", "CsvScanRelation", "Project", "Filter", "Limit", "Union", "Aggregate", "Deduplicate",
+           "execute", "prune_columns"]
 
 
 class LogicalPlan:
@@ -144,6 +145,8 @@ def is_sharded(plan) -> bool:
     ranks: counts all-reduce, rows gather in rank order)."""
     if isinstance(plan, LocalRelation):
         return plan.sharded
+    if isinstance(plan, Aggregate):
+        return False  # every rank holds the whole (small) result
     return any(is_sharded(c) for c in plan.children())
 
 
@@ -332,6 +335,89 @@ class Union(LogicalPlan):
         return Table(a.schema, cols, a.nrows + b.nrows, None, a.device)
 
 
+class Aggregate(LogicalPlan):
+    """``GROUP BY keys`` with the aggregates ``aggs`` = ``(fn, input column or None, output name)``
+    (``fn`` one of count / sum / avg / min / max; input None: ``count(*)``).  Keys and inputs are
+    column references of the child (``aggregates.build_aggregate`` puts a Project underneath for
+    anything else).  No key: one global row, even over an empty input.  No aggregate: the distinct
+    keys.  The result is a small table on the session's device, one row per group in key order
+    (null first); on a data-parallel plan every rank holds all of it."""
+
+    def __init__(self, child: LogicalPlan, keys: Sequence[str], aggs: Sequence[Tuple]):
+        self.child = child
+        self.keys = list(keys)
+        self.aggs = [tuple(a) for a in aggs]
+        self._schema = None
+
+    def children(self):
+        return [self.child]
+
+    def skey(self):
+        k = self._skey
+        if k == 0:
+            ck = self.child.skey()
+            k = self._skey = intern(("Aggregate", ck, tuple(self.keys), tuple(self.aggs))) if ck is not None else None
+        return k
+
+    def schema(self):
+        if self._schema is None:
+            from .aggregates import AggExpr
+
+            cs = self.child.schema()
+            fields = []
+            for k in self.keys:
+                f = ColRef(k)._field(cs)
+                fields.append(StructField(f.name, f.dataType, f.nullable, dict(f.metadata)))
+            for fn, inp, name in self.aggs:
+                a = AggExpr(fn, None if inp is None else ColRef(inp))
+                fields.append(StructField(name, a.result_type(cs), fn != "count"))
+            self._schema = StructType(fields)
+        return self._schema
+
+    def references(self) -> set:
+        return set(self.keys) | {inp for _, inp, _ in self.aggs if inp is not None}
+
+    def _compute(self, session):
+        from .aggregates import aggregate_table
+
+        return aggregate_table(execute(self.child, session), self.keys, self.aggs, self.schema(), is_sharded(self.child))
+
+    def _label(self):
+        aggs = ", ".join(name for _, _, name in self.aggs)
+        return f"Aggregate [{', '.join(self.keys)}] [{aggs}]"
+
+
+class Deduplicate(LogicalPlan):
+    """``dropDuplicates(subset)``: the child's table with its selection narrowed to the first live
+    row of every group of the ``subset`` columns (row order; across shards, rank order)."""
+
+    def __init__(self, child: LogicalPlan, subset: Sequence[str]):
+        self.child = child
+        cs = child.schema()
+        self.subset = [ColRef(c)._field(cs).name for c in subset]
+
+    def children(self):
+        return [self.child]
+
+    def skey(self):
+        k = self._skey
+        if k == 0:
+            ck = self.child.skey()
+            k = self._skey = intern(("Deduplicate", ck, tuple(self.subset))) if ck is not None else None
+        return k
+
+    def schema(self):
+        return self.child.schema()
+
+    def _compute(self, session):
+        from .aggregates import dedupe_table
+
+        return dedupe_table(execute(self.child, session), self.subset, is_sharded(self.child))
+
+    def _label(self):
+        return f"Deduplicate [{', '.join(self.subset)}]"
+
+
 def prune_columns(plan: LogicalPlan, required) -> LogicalPlan:
     """Catalyst-style ColumnPruning: a plan whose Projects compute only the output columns some
     consumer needs (``required``: column names, case-insensitive; None = all).  Filters keep
@@ -362,6 +448,10 @@ def prune_columns(plan: LogicalPlan, required) -> LogicalPlan:
             # Project/Filter chain evaluates them in registers and never stores them
             return Project(f, [ColRef(n) for n in names if n.lower() in req])
         return f
+    if isinstance(plan, Aggregate):
+        # exactly the key and input references pass through, whatever the consumer asks for
+        child = prune_columns(plan.child, plan.references())
+        return plan if child is plan.child else Aggregate(child, plan.keys, plan.aggs)
     return plan
 
 
