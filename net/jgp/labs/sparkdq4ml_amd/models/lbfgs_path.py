@@ -213,9 +213,8 @@ def _train_passes(est, df, X, y, w, sel, d, checks=(), device_qn=True):
         use_dev = comm.all_agree(use_dev)
     if use_dev:
         with tracing.span("solve"):
-            # X4: one (d + 2)-f64 all-reduce per evaluation, no host read.  DQ4ML_QN_SPLIT=1 runs
-            # the same split form on one rank without a group (plain launches: counter runs)
-            if comm.collectives_active() or os.environ.get("DQ4ML_QN_SPLIT") == "1":
+            # X4: one (d + 2)-f64 all-reduce per evaluation, no host read
+            if comm.collectives_active():
                 out = P.qn_fit_dp(head, fit_icpt, std_flag, reg, enet, max_iter, tol, comm.all_reduce_sum)
             else:
                 out = P.qn_fit(head, fit_icpt, std_flag, reg, enet, max_iter, tol)

@@ -594,7 +594,7 @@ def _pipe_stream(df, tbl):
     return st
 
 
-# DQ4ML_TAIL_STANDIN=blocks:usec -- after each overlapped fit's all-reduce, a stand-in kernel of
+# set_tail_standin("blocks:usec") -- after each overlapped fit's all-reduce, a stand-in kernel of
 # `blocks` workgroups holding a CU slot for `usec` us (rowops.hip standin) runs on the tail
 # stream, bracketed by timing events: (end - start) - usec is how long the emulated collective
 # waited for CUs beside the next fit's Gram pass (tests/test_gpu_pipeline.py, ops/device.py
@@ -616,9 +616,6 @@ def _standin(h, side):
     h.standin(blocks, usec, side.cuda_stream)
     e1.record(side)
     STANDIN_EVENTS.append((e0, e1, usec))
-
-
-set_tail_standin(os.environ.get("DQ4ML_TAIL_STANDIN"))
 
 
 def _tail_masks(dev):

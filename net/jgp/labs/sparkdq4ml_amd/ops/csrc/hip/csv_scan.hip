@@ -20,8 +20,6 @@
 //      whole scan is re-done by the host scanner.
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
-
 #include "common.h"
 #include "csv_scan.h"
 
@@ -588,12 +586,8 @@ void csv_parse(const uint8_t* buf, int64_t n, const void* ends, int64_t nlines, 
   if (nlines <= 0) return;
   int64_t g = (nlines + 255) / 256;
   if (g > 16384) g = 16384;
-  // variant: DQ4ML_CSV_PARSE_LDS (8192 | 32768) forces one; default by mean line length
-  static const int forced = [] {
-    const char* e = getenv("DQ4ML_CSV_PARSE_LDS");
-    return e ? atoi(e) : 0;
-  }();
-  const bool small = forced ? forced == kParseLdsSmall : (n / nlines) * 256 * 5 / 4 <= kParseLdsSmall;
+  // variant by mean line length
+  const bool small = (n / nlines) * 256 * 5 / 4 <= kParseLdsSmall;
   auto* stats64 = reinterpret_cast<unsigned long long*>(stats);
   if (csv_ends_i32(n))
     launch_parse(small, g, st, buf, n, static_cast<const int32_t*>(ends), nlines, ncols, o, dcols, valid, keep,

@@ -38,9 +38,10 @@ struct GramArgs {
   // (column pointer, dtype) pairs — feature f is column srcs[2 f] (all of X's dtype xdt)
   const int64_t* srcs;
   // bf16 + stream kernels: 1 = wave w takes supersteps (stages) w, w + W, w + 2W, ... (W = total waves) instead of
-  // one contiguous range (default; DQ4ML_GRAM_INTERLEAVE=0 restores the contiguous ranges; both orders are fixed, so run-to-run
-  // deterministic).  Every wave sweeps the whole row range in step with the others: measured ~1 % faster
-  // at 1e8 rows and ~2.5 % at the 1.25e7-row 8-GPU shard (the waves' drain is more even)
+  // one contiguous range (both orders are fixed, so run-to-run deterministic).  gram_tall sets 1 for the tall
+  // bf16 / f64 kernels: every wave sweeps the whole row range in step with the others, measured ~1 % faster
+  // at 1e8 rows and ~2.5 % at the 1.25e7-row 8-GPU shard (the waves' drain is more even).  The stream
+  // kernels always keep contiguous ranges (their interleaved A/B lost and was removed)
   int interleave;
   // stream kernels compiled with a DQ row predicate (ops/streamfuse.py, hipRTC): per-lane DMA
   // sources of the stage's row-scalar area — [64 lanes][(base, bytes per row) x 2 instructions]
@@ -65,9 +66,6 @@ struct GramArgs {
 // feature 32t+f.  One wave load instruction = 1 KiB contiguous; zero padded to whole supersteps.
 int64_t tiled_elems(int d, int64_t n);
 
-// GramArgs::interleave for the tall bf16 kernel (1 unless DQ4ML_GRAM_INTERLEAVE=0); the stream
-// kernels always keep contiguous ranges (their interleaved A/B lost and was removed)
-int gram_interleave();
 // shift: per-feature f32 shift subtracted before the bf16 cast (null: none; rows >= n stay zero)
 void tile_bf16(const void* X, int xdt, int64_t ld, int d, int64_t n, void* out, hipStream_t st,
                const float* shift = nullptr);

@@ -24,8 +24,6 @@
 //    atomics: bit-reproducible run to run).
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
-
 #include "common.h"
 #include "gram.h"
 
@@ -1566,19 +1564,10 @@ static bool use_skinny(int mode, int d, int xdt, int tiled) {
   return mode == GRAM_F64 && !tiled && d <= kSkinnyMaxD && (xdt == DT_F64 || xdt == DT_F32);
 }
 
-// DQ4ML_GRAM_STREAM=0 keeps the round-1 register-staged f64 kernel (A/B measurements only)
-static bool use_stream() {
-  static const bool on = [] {
-    const char* e = getenv("DQ4ML_GRAM_STREAM");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-
 int gram_plan_blocks(int mode, int d, int64_t n, int xdt, int xmode) {
-  if (mode == GRAM_F32 || mode == GRAM_F32S || (use_stream() && ((mode == GRAM_F64 && !use_skinny(mode, d, xdt, 0) &&
-                                              (xdt == DT_F64 || xdt == DT_F32)) ||
-                                             (mode == GRAM_BF16 && xdt == DT_F32))))
+  if (mode == GRAM_F32 || mode == GRAM_F32S ||
+      (mode == GRAM_F64 && !use_skinny(mode, d, xdt, 0) && (xdt == DT_F64 || xdt == DT_F32)) ||
+      (mode == GRAM_BF16 && xdt == DT_F32))
     return gram_stream_blocks(mode, d, n, xdt);
   if (use_skinny(mode, d, xdt, 0)) {
     int full = 1;
@@ -1615,12 +1604,6 @@ void gram_reduce(int mode, const double* partials, int blocks, int d, double* ou
   DQ_HIP_CHECK(hipGetLastError());
 }
 
-int gram_interleave() {
-  // always on: same-box A/B against contiguous ranges (5 alternations) 1e8 rows 1.011-1.015 vs
-  // 1.020-1.026 ms, 1.25e7 rows 0.1426-0.1441 vs 0.1471-0.1476 ms per fit (tall bf16 kernel)
-  return 1;
-}
-
 void gram_tall(int mode, GramArgs a, int xmode, int blocks, double* out, hipStream_t st, bool reduce) {
   if (a.d < 1 || a.d > 64) throw std::invalid_argument("gram_tall: d must be in [1, 64]");
   if (blocks < 1) throw std::invalid_argument("gram_tall: blocks must be >= 1");
@@ -1629,7 +1612,10 @@ void gram_tall(int mode, GramArgs a, int xmode, int blocks, double* out, hipStre
   const int64_t total_waves = (int64_t)blocks * (block / kWave);
   a.spw = (a.nsuper + total_waves - 1) / total_waves;
   if (a.spw < 1) a.spw = 1;
-  a.interleave = gram_interleave();
+  // interleaved supersteps: same-box A/B against contiguous ranges (5 alternations) 1e8 rows
+  // 1.011-1.015 vs 1.020-1.026 ms, 1.25e7 rows 0.1426-0.1441 vs 0.1471-0.1476 ms per fit (tall
+  // bf16 kernel); the stream kernels set their own (contiguous ranges)
+  a.interleave = 1;
   a.P = (int)gram_partial_stride(mode, a.d);
   const size_t lds = mode == GRAM_BF16 ? bf16_lds(a.d, xmode) : f64_lds(a.d);
   if (a.tiled && mode != GRAM_BF16) throw std::invalid_argument("gram_tall: tiled storage needs bf16 mode");
@@ -1653,8 +1639,7 @@ void gram_tall(int mode, GramArgs a, int xmode, int blocks, double* out, hipStre
     with_skinny_cols(a, [&](auto kern) { hipLaunchKernelGGL(kern, dim3(blocks), dim3(kBlock), 0, st, a); });
   } else if (use_skinny(mode, a.d, a.xdt, a.tiled)) {
     with_skinny(a.xdt, a.d, [&](auto kern) { hipLaunchKernelGGL(kern, dim3(blocks), dim3(kBlock), 0, st, a); });
-  } else if ((mode == GRAM_F32 || mode == GRAM_F32S ||
-              (use_stream() && (mode == GRAM_F64 || (mode == GRAM_BF16 && a.xdt == DT_F32)))) &&
+  } else if ((mode == GRAM_F32 || mode == GRAM_F32S || mode == GRAM_F64 || (mode == GRAM_BF16 && a.xdt == DT_F32)) &&
              gram_stream_ok(mode, a)) {
     gram_stream(mode, a, xmode, blocks, out, st, reduce);
     return;

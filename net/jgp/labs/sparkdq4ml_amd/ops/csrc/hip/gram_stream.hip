@@ -26,8 +26,6 @@
 #ifndef __HIPCC_RTC__  // (ops/streamfuse.py compiles the device part below with hipRTC too)
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
-
 #include "common.h"
 #include "gram.h"
 #endif
@@ -42,17 +40,14 @@ constexpr int kRawBytes = 1280;  // [y | w]: 1 KiB (lanes 0-31 | 32-63 x 16 B); 
 constexpr int kFlush = 16;       // exact-f32 kernel: stages per f32 accumulation chunk
 
 // cache policy of the stream's DMA loads: every byte is read once per pass (the rows stream
-// through, nothing is re-read from L2 / MALL), so non-temporal (aux 2 = nt) by default
-#ifndef DQ4ML_GLDS_AUX
-#define DQ4ML_GLDS_AUX 2
-#endif
+// through, nothing is re-read from L2 / MALL), so non-temporal (aux 2 = nt)
 __device__ __forceinline__ void glds16(const void* g, void* l) {
   __builtin_amdgcn_global_load_lds((__attribute__((address_space(1))) void*)(g),
-                                   (__attribute__((address_space(3))) void*)(l), 16, 0, DQ4ML_GLDS_AUX);
+                                   (__attribute__((address_space(3))) void*)(l), 16, 0, 2);
 }
 __device__ __forceinline__ void glds4(const void* g, void* l) {
   __builtin_amdgcn_global_load_lds((__attribute__((address_space(1))) void*)(g),
-                                   (__attribute__((address_space(3))) void*)(l), 4, 0, DQ4ML_GLDS_AUX);
+                                   (__attribute__((address_space(3))) void*)(l), 4, 0, 2);
 }
 template <int N>
 __device__ __forceinline__ void wait_vm() {
@@ -447,9 +442,9 @@ __global__ __launch_bounds__(kSB) void gram_stream_f64_kernel(GramArgs a) {
 // "32 float features" storage of the headline config).  Side sums Σw·x, Σw·x·y on the f32 VALU
 // from the unrounded features in both.
 // =============================================================================================
-template <int NT, int RING, int CMP, int XM, int RS = 64>
+template <int NT, int RING, int CMP, int XM>
 __device__ __forceinline__ void gram_stream_f32_body(const GramArgs& a) {
-  static_assert(RS == 64 || RS == 32, "f32 stream kernel: 64- or 32-row stages");
+  constexpr int RS = 64;  // rows per stage
   typedef SGeom<float, 32, NT, RS, RING> G;
   constexpr int HC = G::kCPF / 2;  // chunks per half stage: lane h reads rows [h * RS / 2, (h + 1) * RS / 2)
   constexpr int NPAIR = NT * (NT + 1) / 2;
@@ -621,7 +616,7 @@ __device__ __forceinline__ void gram_stream_f32_body(const GramArgs& a) {
 #pragma unroll
     for (int t = 0; t < NT; ++t) cs[t] += (double)c32[t], ab[t] += (double)a32[t];
     wait_lgkm0();
-    if (++chunk == kFlush * 64 / RS) {  // f32 accumulation chunks of 1024 rows
+    if (++chunk == kFlush) {  // f32 accumulation chunks of 1024 rows
       flush();
       chunk = 0;
     }
@@ -675,118 +670,81 @@ __device__ __forceinline__ void gram_stream_f32_body(const GramArgs& a) {
   for (int i = threadIdx.x; i < P; i += kSB) out[i] = red[i];
 }
 
-template <int NT, int RING, int CMP, int XM, int RS = 64>
+template <int NT, int RING, int CMP, int XM>
 __global__ __launch_bounds__(kSB) void gram_stream_f32_kernel(GramArgs a) {
-  gram_stream_f32_body<NT, RING, CMP, XM, RS>(a);
+  gram_stream_f32_body<NT, RING, CMP, XM>(a);
 }
 
 // ---- dispatch --------------------------------------------------------------------------------
 #ifndef __HIPCC_RTC__
 constexpr int kLdsMax = 160 * 1024;
 
-// DQ4ML_GRAM_STREAM_RING=2|3 (A/B): ring depth where a 3-deep ring still fits four waves per CU
-static int ring_pref() {
-  static const int r = [] {
-    const char* e = getenv("DQ4ML_GRAM_STREAM_RING");
-    return e ? atoi(e) : 3;
-  }();
-  return r;
+// Ring depth, a compile-time fact of every instantiation: 3 where a 3-deep ring still fits four
+// waves per CU in LDS, else 2 -- and 2 for the MFMA-heavy kernels (exact f32, split bf16), whose
+// MFMA share wants the second block per CU that ring 3 costs.  Measured (1e8 x 32, 1x MI355X):
+// bf16 on f32 columns 2.24 (ring 3) vs 2.29 ms (ring 2); exact f32 3.15 vs 3.00 ms; split bf16
+// 2.81 vs 2.55 ms (two blocks per CU: one wave's split VALU overlaps the other's MFMAs)
+template <typename TX, int TF, int NT, int RS>
+constexpr int ring_for(bool mfma_heavy) {
+  return !mfma_heavy && kSW * SGeom<TX, TF, NT, RS, 3>::kWaveBytes <= kLdsMax ? 3 : 2;
 }
 
-// measured (1e8 x 32, 1x MI355X): bf16 on f32 columns 2.24 (ring 3) vs 2.29 ms (ring 2); exact
-// f32 3.15 vs 3.00 ms — its MFMA share wants the second block per CU that ring 3 costs
-template <typename G3, typename F, typename K2, typename K3>
-static void pick_ring(F&& f, K2 k2, int wb2, K3 k3, bool mfma_heavy = false) {
-  const int want = getenv("DQ4ML_GRAM_STREAM_RING") ? ring_pref() : (mfma_heavy ? 2 : 3);
-  if (want >= 3 && kSW * G3::kWaveBytes <= kLdsMax) return f(k3, G3::kWaveBytes);
-  return f(k2, wb2);
-}
-
-// f32 storage, 64 features (NT = 2): 64-row stages.  32-row stages (a deeper DMA ring, four waves
-// per CU) were measured and lost: config 4 (1.25e8 x 64, one box, one run) 6.18 ms at 64 rows /
-// ring 2, 6.45 at 32 / ring 3, 6.53 at 32 / ring 4 -- the per-stage fixed work (row scalars,
-// waits) doubles and the extra bytes in flight buy nothing.
-static int f32_rs(int) { return 64; }
-
+// f32 storage: 64-row stages at every width.  32-row stages at 64 features (a deeper DMA ring,
+// four waves per CU) were measured and lost: config 4 (1.25e8 x 64, one box, one run) 6.18 ms at
+// 64 rows / ring 2, 6.45 at 32 / ring 3, 6.53 at 32 / ring 4 -- the per-stage fixed work (row
+// scalars, waits) doubles and the extra bytes in flight buy nothing.
 template <int NT, int CMP, int XM, typename F>
-static void f32_rs32(F&& f) {
-  const char* e = getenv("DQ4ML_GRAM_STREAM_RING");
-  const int want = e ? atoi(e) : (CMP == 0 ? 2 : 4);
-  if (want >= 4 && kSW * SGeom<float, 32, NT, 32, 4>::kWaveBytes <= kLdsMax)
-    return f(gram_stream_f32_kernel<NT, 4, CMP, XM, 32>, SGeom<float, 32, NT, 32, 4>::kWaveBytes);
-  if (want == 3) return f(gram_stream_f32_kernel<NT, 3, CMP, XM, 32>, SGeom<float, 32, NT, 32, 3>::kWaveBytes);
-  return f(gram_stream_f32_kernel<NT, 2, CMP, XM, 32>, SGeom<float, 32, NT, 32, 2>::kWaveBytes);
+static void with_f32_kernel(F&& f) {
+  constexpr int R = ring_for<float, 32, NT, 64>(CMP != 1);
+  f(gram_stream_f32_kernel<NT, R, CMP, XM>, SGeom<float, 32, NT, 64, R>::kWaveBytes);
+}
+
+template <int CMP, typename F>
+static void with_f32_cmp(int d, int xm, F&& f) {
+  if ((d + 31) / 32 == 1) return xm ? with_f32_kernel<1, CMP, 1>(f) : with_f32_kernel<1, CMP, 0>(f);
+  return xm ? with_f32_kernel<2, CMP, 1>(f) : with_f32_kernel<2, CMP, 0>(f);
+}
+
+template <typename TX, int NT, int RS, typename F>
+static void with_f64_kernel(int xm, F&& f) {
+  constexpr int R = ring_for<TX, 16, NT, RS>(false);
+  constexpr int kBytes = SGeom<TX, 16, NT, RS, R>::kWaveBytes;
+  if (xm) return f(gram_stream_f64_kernel<TX, NT, RS, R, 1>, kBytes);
+  f(gram_stream_f64_kernel<TX, NT, RS, R, 0>, kBytes);
 }
 
 template <typename F>
 static void with_stream_kernel(int mode, int xdt, int d, int xm, F&& f) {
-  // split-bf16 f32 statistics: 64-row stages, ring 2 (two blocks per CU: one wave's split VALU
-  // overlaps the other's MFMAs; 1e8 x 32 same box 2.55 vs 2.81 ms at ring 3)
-  if (mode == GRAM_F32S) {
+  if (mode == GRAM_F32S) {  // split-bf16 f32 statistics
     if (xdt != DT_F32) throw std::invalid_argument("gram_stream(f32s): needs f32 features");
-#define DQ_SF32S(NTV, XMV)                                                                             \
-  return pick_ring<SGeom<float, 32, NTV, 64, 3>>(f, gram_stream_f32_kernel<NTV, 2, 2, XMV>,            \
-                                                 SGeom<float, 32, NTV, 64, 2>::kWaveBytes,              \
-                                                 gram_stream_f32_kernel<NTV, 3, 2, XMV>, true);
-    if ((d + 31) / 32 == 1) { if (xm) { DQ_SF32S(1, 1) } else { DQ_SF32S(1, 0) } }
-    if (xm) { DQ_SF32S(2, 1) } else { DQ_SF32S(2, 0) }
-#undef DQ_SF32S
+    return with_f32_cmp<2>(d, xm, f);
   }
   if (mode == GRAM_F32 || mode == GRAM_BF16) {
     if (xdt != DT_F32) throw std::invalid_argument("gram_stream(f32/bf16): needs f32 features");
-    const int NT = (d + 31) / 32;
-    if (f32_rs(d) == 32) {
-      if (NT == 1) {
-        if (mode == GRAM_F32) return xm ? f32_rs32<1, 0, 1>(f) : f32_rs32<1, 0, 0>(f);
-        return xm ? f32_rs32<1, 1, 1>(f) : f32_rs32<1, 1, 0>(f);
-      }
-      if (mode == GRAM_F32) return xm ? f32_rs32<2, 0, 1>(f) : f32_rs32<2, 0, 0>(f);
-      return xm ? f32_rs32<2, 1, 1>(f) : f32_rs32<2, 1, 0>(f);
-    }
-#define DQ_SF32(NTV, CMPV, XMV)                                                                        \
-  return pick_ring<SGeom<float, 32, NTV, 64, 3>>(f, gram_stream_f32_kernel<NTV, 2, CMPV, XMV>,         \
-                                                 SGeom<float, 32, NTV, 64, 2>::kWaveBytes,              \
-                                                 gram_stream_f32_kernel<NTV, 3, CMPV, XMV>, CMPV == 0);
-    if (mode == GRAM_F32) {
-      if (NT == 1) { if (xm) { DQ_SF32(1, 0, 1) } else { DQ_SF32(1, 0, 0) } }
-      if (xm) { DQ_SF32(2, 0, 1) } else { DQ_SF32(2, 0, 0) }
-    }
-    if (NT == 1) { if (xm) { DQ_SF32(1, 1, 1) } else { DQ_SF32(1, 1, 0) } }
-    if (xm) { DQ_SF32(2, 1, 1) } else { DQ_SF32(2, 1, 0) }
-#undef DQ_SF32
+    return mode == GRAM_F32 ? with_f32_cmp<0>(d, xm, f) : with_f32_cmp<1>(d, xm, f);
   }
   if (mode != GRAM_F64) throw std::invalid_argument("gram_stream: f64 / f32 / bf16 modes only");
   const int NT = (d + 15) / 16;
-#define DQ_SF64(TX, NTV, RSV)                                                                          \
-  if (xm) return pick_ring<SGeom<TX, 16, NTV, RSV, 3>>(f, gram_stream_f64_kernel<TX, NTV, RSV, 2, 1>,  \
-                                                       SGeom<TX, 16, NTV, RSV, 2>::kWaveBytes,          \
-                                                       gram_stream_f64_kernel<TX, NTV, RSV, 3, 1>);     \
-  return pick_ring<SGeom<TX, 16, NTV, RSV, 3>>(f, gram_stream_f64_kernel<TX, NTV, RSV, 2, 0>,           \
-                                               SGeom<TX, 16, NTV, RSV, 2>::kWaveBytes,                  \
-                                               gram_stream_f64_kernel<TX, NTV, RSV, 3, 0>);
   if (xdt == DT_F64) {
     switch (NT) {
-      case 1: DQ_SF64(double, 1, 64)
-      case 2: DQ_SF64(double, 2, 64)
-      case 3: DQ_SF64(double, 3, 32)
-      default: DQ_SF64(double, 4, 32)
+      case 1: return with_f64_kernel<double, 1, 64>(xm, f);
+      case 2: return with_f64_kernel<double, 2, 64>(xm, f);
+      case 3: return with_f64_kernel<double, 3, 32>(xm, f);
+      default: return with_f64_kernel<double, 4, 32>(xm, f);
     }
   }
   if (xdt == DT_F32) {
     switch (NT) {
-      case 1: DQ_SF64(float, 1, 64)
-      case 2: DQ_SF64(float, 2, 64)
-      case 3: DQ_SF64(float, 3, 64)
-      default: DQ_SF64(float, 4, 64)
+      case 1: return with_f64_kernel<float, 1, 64>(xm, f);
+      case 2: return with_f64_kernel<float, 2, 64>(xm, f);
+      case 3: return with_f64_kernel<float, 3, 64>(xm, f);
+      default: return with_f64_kernel<float, 4, 64>(xm, f);
     }
   }
-#undef DQ_SF64
   throw std::invalid_argument("gram_stream(f64): f64 / f32 features only");
 }
 
 static int stream_rs(int mode, int xdt, int d) {
-  if (mode == GRAM_F32S) return 64;
-  if (mode == GRAM_F32 || mode == GRAM_BF16) return f32_rs(d);
   return (mode == GRAM_F64 && xdt == DT_F64 && d > 32) ? 32 : 64;
 }
 

@@ -82,12 +82,6 @@ PYBIND11_MODULE(_dq4ml_hip, m) {
     DQ_HIP_CHECK(hipExtStreamCreateWithCUMask(&s, (uint32_t)mask.size(), mask.data()));
     return reinterpret_cast<uintptr_t>(s);
   });
-  // drain and destroy a stream this module created (runtime/streams.py releases its CU-masked
-  // streams at interpreter exit, before the HIP runtime's own teardown)
-  m.def("stream_destroy", [](uintptr_t st) {
-    DQ_HIP_CHECK(hipStreamSynchronize(as_stream(st)));
-    DQ_HIP_CHECK(hipStreamDestroy(as_stream(st)));
-  });
   m.def("device_info", []() {
     int dev = 0;
     DQ_HIP_CHECK(hipGetDevice(&dev));

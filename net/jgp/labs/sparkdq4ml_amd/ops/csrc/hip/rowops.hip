@@ -782,7 +782,7 @@ void huber_pass_dev(const void* X, int xdt, int64_t ld, int d, int64_t n, int ti
 }
 
 // Stand-in for a collective kernel of the fit tail (diagnostics / tests: models/regression.py
-// DQ4ML_TAIL_STANDIN): `blocks` workgroups that each hold a CU slot for `usec` microseconds
+// set_tail_standin): `blocks` workgroups that each hold a CU slot for `usec` microseconds
 // (s_memrealtime runs at 100 MHz), the shape of an RCCL all-reduce's channel blocks.  The wait is
 // bounded (<= 1 ms) so the grid always drains.
 namespace {

@@ -186,7 +186,7 @@ class _Shape:
         # the [y | 1] strip (sums of x y, x, y, y^2 and the count: 2 d + 3 of the gram_width slots)
         # on the VALU beside the MFMA tiles of x x^T: the strip's MFMA panel is mostly padding
         # (2 of 16 columns at d = 32, a third of the tiles)
-        self.vstrip = self.mfma and self.yfirst and os.environ.get("DQ4ML_CUT_VSTRIP", "1") != "0"
+        self.vstrip = self.mfma and self.yfirst
         self.NT16 = (d + (0 if self.vstrip else 2) + 15) // 16
         self.tiles = [(I, J) for I in range(self.NT16) for J in range(I, self.NT16)]
         if self.mfma:
@@ -549,7 +549,7 @@ def kernel_source(g, kinds, used, opts: dict, H: int, slots: dict, d: int, term:
     abl = diag.ablation("DQ4ML_CUT_ABLATE")  # (refused without DQ4ML_DIAG=1)
     # diagnostic phase clocks (DQ4ML_CUT_STAMPS=1): s_memtime after each block barrier, per-phase
     # sums of wave 0 of every block -> the dbg slot ([grid][8] u64: phases 0-5, windows)
-    stamps = os.environ.get("DQ4ML_CUT_STAMPS", "0") == "1" and "dbg" in slots
+    stamps = "dbg" in slots and diag.flag("DQ4ML_CUT_STAMPS")  # (refused without DQ4ML_DIAG=1)
     if stamps:
         stamp_decl = ("  unsigned long long dq_ph[8] = {0, 0, 0, 0, 0, 0, 0, 0};\n"
                       "  unsigned long long dq_t = __builtin_amdgcn_s_memtime();\n"
@@ -1016,9 +1016,10 @@ def _compile(nodes, rel, d: int):
     # round 5's -- lane-owned conversion without the position array, the split-half scatter --
     # are measured in profiles/r5_cutter.md and were not kept)
     quoted = not f.get("fast_only") and bool(f.get("quoted_fast"))
+    stamps = diag.flag("DQ4ML_CUT_STAMPS")
     key = (parts, udfs, tuple(rel.schema().names), tuple(f["kinds"]), repr(sorted(f["opts"].items())), H, d, term,
            crlf, min_line, int(f.get("max_line", 1 << 30)), quoted, os.environ.get("DQ4ML_CUT_ABLATE"),
-           os.environ.get("DQ4ML_CUT_STAMPS"), os.environ.get("DQ4ML_CUT_VSTRIP"))
+           stamps)
     if key in _CACHE:
         return _CACHE[key]
     base = _ScanBase(rel.schema(), 0, f["device"])
@@ -1026,8 +1027,7 @@ def _compile(nodes, rel, d: int):
     cp = None
     try:
         _, g, outputs, _ = dqvm.compile_chain(nodes, base, False, gen=g)
-        names = ("buf", "nwin", "trailing", "vflag", "gpart") + (
-            ("dbg",) if os.environ.get("DQ4ML_CUT_STAMPS", "0") == "1" else ())
+        names = ("buf", "nwin", "trailing", "vflag", "gpart") + (("dbg",) if stamps else ())
         slots = {k: g.slot(None, (k,)) for k in names}
         ml = int(f.get("max_line", 1 << 30))
         _, sh = kernel_source(g, f["kinds"], g.used, f["opts"], H, slots, d, term, crlf, min_line, 0, ml, quoted)

@@ -8,9 +8,9 @@ kernels per action: terminator counts, their scan, a materialized ``[nlines]`` l
 the parse (one typed plane per column, validity, keep flags) and the ``dq_fused`` chain kernel
 re-reading those planes.  This module generates a kernel that
 
-* takes 16 KiB byte windows per block (the ``csv_count_kernel`` windows, so the exclusive scan of
-  the per-window terminator counts gives each block its first global line index — the only
-  global intermediate, ``nb`` int64s);
+* takes 16 KiB byte windows per block (the ``csv_count_kernel`` windows); a decoupled look-back
+  over the predecessors' published line counts gives each block its first global line index —
+  the only global intermediate, ``nb`` status words;
 * stages the window plus a head region (bytes of the line that straddles into the window) in
   LDS with 16-byte granule loads, finds the terminators from the staged registers (SWAR), and
   keeps their positions in LDS (uint16, 1024-line rounds) — no line-end array in HBM;
@@ -81,42 +81,27 @@ def head_bytes(mean_line: float) -> int:
     return h
 
 
-def ticket_mode() -> str:
-    """How a look-back block picks its window (``DQ4ML_SCAN_TICKET``):
-
-    * ``xcd`` (default): one dispatch-order ticket counter per ``blockIdx.x % 8`` class (the
-      8 XCDs take workgroups round-robin), on separate cache lines; window = ticket * 8 + class.
-    * ``global``: one counter for the grid — strict dispatch order, but every block's ticket
-      is an atomic on ONE address, serialised at the memory side: 0.48 of 0.75 ms in a
-      1e8-line scan with the per-line work ablated (``scripts/scan_ablation.py``).
-    * ``none``: window = ``blockIdx.x`` (relies on in-order dispatch per XCD).
-
-    Either way a predecessor that never publishes ends in the bounded spin (vflag 4, a loud
-    fact-check failure), never a hang."""
-    m = os.environ.get("DQ4ML_SCAN_TICKET", "xcd")
-    if m not in ("xcd", "global", "none"):
-        raise ValueError(f"DQ4ML_SCAN_TICKET={m!r}: expected xcd, global or none")
-    return m
-
-
-# status words after the per-window ones: the global ticket, then 8 per-class tickets 128 B apart
+# status words after the per-window ones: one unused word, then 8 per-class tickets 128 B apart
 TICKET_WORDS = 1 + 8 * 16
 
 
-def _ticket(lookback: bool, mode: str = "xcd") -> str:
-    if not lookback:
-        return "  const long long blk = blockIdx.x;"
+def _ticket(mode: str = "xcd") -> str:
+    """How a look-back block picks its window:
+
+    * ``xcd``: one dispatch-order ticket counter per ``blockIdx.x % 8`` class (the 8 XCDs take
+      workgroups round-robin), on separate cache lines; window = ticket * 8 + class.  (One counter
+      for the whole grid serialised every block's ticket on ONE address at the memory side: 0.48
+      of 0.75 ms in a 1e8-line scan with the per-line work ablated, ``scripts/scan_ablation.py``.)
+    * ``none`` (the ablation build without tickets): window = ``blockIdx.x`` (relies on in-order
+      dispatch per XCD).
+
+    Either way a predecessor that never publishes ends in the bounded spin (vflag 4, a loud
+    fact-check failure), never a hang."""
     if mode == "none":
         return """  DQG unsigned long long* status = (DQG unsigned long long*)offs;
   const long long blk = blockIdx.x;"""
-    if mode == "global":
-        return """  // window = dispatch-order ticket: every predecessor window's block is already resident, so
-  // the look-back below always makes progress
-  DQG unsigned long long* status = (DQG unsigned long long*)offs;
-  if (tid == 0)
-    sblk = (long long)__hip_atomic_fetch_add(status + gridDim.x, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  __syncthreads();
-  const long long blk = sblk;"""
+    if mode != "xcd":
+        raise ValueError(f"ticket mode {mode!r}: expected xcd or none")
     return """  // window = per-XCD dispatch-order ticket * 8 + class: one counter per blockIdx.x % 8 class
   // (the XCD round-robin), so no single address serialises every block's ticket
   DQG unsigned long long* status = (DQG unsigned long long*)offs;
@@ -129,9 +114,7 @@ def _ticket(lookback: bool, mode: str = "xcd") -> str:
   const long long blk = sblk;"""
 
 
-def _lookback(lookback: bool) -> str:
-    if not lookback:
-        return "  const long long gl0 = offs[blockIdx.x];"
+def _lookback() -> str:
     return """  if (wave == 0) {
     // decoupled look-back, one wave: publish this window's count (flag 1), then read the 64
     // nearest predecessors at once; their values up to the nearest one carrying its inclusive
@@ -176,23 +159,13 @@ def _lookback(lookback: bool) -> str:
   const long long gl0 = sgl0;"""
 
 
-def _wpe(fast_only: bool = False) -> str:
-    """Occupancy hint (``DQ4ML_SCAN_WPE`` waves per SIMD; 0: the compiler's choice).  Default 8:
-    the byte walks are latency-bound, and 8 waves with a few spilled VGPRs beat 4 waves without
-    (lab CSV pipeline 2.16 / 1.94 / 1.91 ms per step at 4 / 6 / 8 waves, one run)."""
-    w = int(os.environ.get("DQ4ML_SCAN_WPE", "8"))
-    return f"__attribute__((amdgpu_waves_per_eu({w}))) " if w > 0 else ""
+# Occupancy hint, 8 waves per SIMD: the byte walks are latency-bound, and 8 waves with a few
+# spilled VGPRs beat 4 waves without (lab CSV pipeline 2.16 / 1.94 / 1.91 ms per step at 4 / 6 / 8
+# waves, one run)
+_WPE = "__attribute__((amdgpu_waves_per_eu(8))) "
 
 
 _VALUE = {1: "(int)fzl{c}", 2: "fzl{c}", 0: "fzd{c}", 3: "(fzd{c} != 0.0)", 5: "fzl{c}"}
-
-
-def _scan_nt() -> bool:
-    """Window loads with the non-temporal hint (default; DQ4ML_SCAN_NT=0 turns it off).  Each
-    window byte is read once, so the hint keeps the stream out of the caches' way: lab CSV action
-    0.913 -> 0.900 ms at 1e8 rows, three alternating pairs, same statistics digest
-    (profiles/r6/lab_nt_ab.log)."""
-    return os.environ.get("DQ4ML_SCAN_NT", "1") != "0"
 
 
 def gram_width(d: int) -> int:
@@ -219,8 +192,8 @@ def _gram_code(xs, yv) -> str:
 
 
 def kernel_source(g, kinds, nullable, used, opts: dict, strict: bool, head: int, slots: dict,
-                  lookback: bool = True, fast_only: bool = False, ticket: str = "xcd", gram: int = 0,
-                  nolb: bool = False, term_only: Optional[str] = None) -> str:
+                  fast_only: bool = False, ticket: str = "xcd", gram: int = 0, nolb: bool = False,
+                  term_only: Optional[str] = None) -> str:
     """Source of the fused kernel.
 
     ``g``: the dqvm generator after lowering the chain (its ``lines`` use ``f<c>`` / ``m<c>`` for
@@ -229,11 +202,12 @@ def kernel_source(g, kinds, nullable, used, opts: dict, strict: bool, head: int,
     verified null-free).  ``used``: columns the chain reads.  ``slots``: pointer-slot indices of
     the scan inputs (buf, offs, nalloc, trailing, vflag).
 
-    ``lookback``: single pass — each block takes a ticket (its window, in dispatch order),
+    One pass over the bytes: each block takes a ticket (its window, in dispatch order),
     publishes its line count and finds its first line index by decoupled look-back over its
-    predecessors' published counts (``offs`` is then the zeroed ``[nb + TICKET_WORDS]`` status
-    array, the ticket counters last; ``ticket``: see ``ticket_mode``).  Otherwise ``offs`` holds
-    the exclusive scan of ``csv_count_kernel``'s per-window counts (two passes over the bytes).
+    predecessors' published counts (``offs`` is the zeroed ``[nb + TICKET_WORDS]`` status
+    array, the ticket counters last; ``ticket``: see ``_ticket``).  The window loads carry the
+    non-temporal hint: each byte is read once, so the stream stays out of the caches' way (lab CSV
+    action 0.913 -> 0.900 ms at 1e8 rows, three alternating pairs, profiles/r6/lab_nt_ab.log).
 
     ``fast_only``: the earlier scan parsed every field on the numeric fast path (plain dialect):
     only that path is compiled in — the general parser's registers (~60 VGPRs) leave the kernel
@@ -330,7 +304,7 @@ def kernel_source(g, kinds, nullable, used, opts: dict, strict: bool, head: int,
 
     # SWAR rows: fast-only files whose separator cannot be part of a number
     sep_c = opts.get("sep", ",")
-    swar = fast_only and sep_c not in "0123456789.+-" and os.environ.get("DQ4ML_SCAN_SWAR", "1") != "0"
+    swar = fast_only and sep_c not in "0123456789.+-"
     body = ("\n".join("    " + ln.strip() for ln in g.lines).replace("P[", "p[")
             .replace("atomicOr((int*)p[", "dq_flag((unsigned int*)p["))
     stores = "".join(f"    ((DQG {t}*)p[{s}])[li] = ({t})({v});\n" for t, v, s in g.stores)
@@ -373,11 +347,10 @@ __device__ __forceinline__ void dq_row_swar(const unsigned char* B, int start, i
 {body}
 {stores}}}
 """
-    # 10^k / RN(10^-k) for the SWAR converter's decimals: an LDS table (one ds_read2_b64) or VALU
-    # selects and products (DQ4ML_SCAN_P10=valu); the kernel is VALU-issue-bound
-    p10_lds = swar and os.environ.get("DQ4ML_SCAN_P10", "lds") == "lds"
-    p10_init = P10_INIT if p10_lds else ""
-    return (prelude(p10_lds) + header_text() + f"""
+    # 10^k / RN(10^-k) for the SWAR converter's decimals: an LDS table (one ds_read2_b64), not
+    # VALU selects and products; the kernel is VALU-issue-bound
+    p10_init = P10_INIT if swar else ""
+    return (prelude(swar) + header_text() + f"""
 using namespace dq4ml_csv;
 typedef unsigned int csv_u32x4 __attribute__((ext_vector_type(4)));
 // every global access names the global address space: generic (flat) accesses count in both
@@ -429,7 +402,7 @@ __device__ __forceinline__ void dq_row(PB B, IT bias, IT start, IT end, long lon
 {body}
 {stores}}}
 {swar_row}
-{ptr_struct(ns)}extern "C" __global__ __launch_bounds__(256) {_wpe(fast_only)}void {ENTRY}(const DqPtrs P, long long n) {{
+{ptr_struct(ns)}extern "C" __global__ __launch_bounds__(256) {_WPE}void {ENTRY}(const DqPtrs P, long long n) {{
   void* p[{ns}];
 #pragma unroll
   for (int i = 0; i < {ns}; ++i) p[i] = P.v[i];
@@ -443,7 +416,7 @@ __device__ __forceinline__ void dq_row(PB B, IT bias, IT start, IT end, long lon
   __shared__ int wtot[4];
   __shared__ long long sstart0, sblk, sgl0;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-{p10_init}{"  const long long blk = blockIdx.x;  // Gram mode: no global line numbering needed" if nolb else _ticket(lookback, ticket if not abl & 16 else "none")}
+{p10_init}{"  const long long blk = blockIdx.x;  // Gram mode: no global line numbering needed" if nolb else _ticket(ticket if not abl & 16 else "none")}
   const long long a = (long long)(reinterpret_cast<unsigned long long>(b) & 15ull);
   const DQG unsigned char* ab = b - a;                     // 16-byte aligned view
   const long long wbase = blk * {W} - a;                    // buffer index of window byte 0
@@ -455,7 +428,7 @@ __device__ __forceinline__ void dq_row(PB B, IT bias, IT start, IT end, long lon
   for (int j = 0; j < 4; ++j) {{
     const long long gi = tb + 16 * j;
     csv_u32x4 v = {{0u, 0u, 0u, 0u}};
-    if (gi < n && gi + 16 > 0) v = {"__builtin_nontemporal_load(" if _scan_nt() else "*("}reinterpret_cast<const DQG csv_u32x4*>(ab + gi + a));
+    if (gi < n && gi + 16 > 0) v = __builtin_nontemporal_load(reinterpret_cast<const DQG csv_u32x4*>(ab + gi + a));
     {"if (v[0] == 0x7F7F7F7Fu && v[1] == 3u) " if abl & 32 else ""}*reinterpret_cast<csv_u32x4*>(stage + {H} + 64 * tid + 16 * j) = v;
 #pragma unroll
     for (int w = 0; w < 4; ++w) {{
@@ -533,7 +506,7 @@ __device__ __forceinline__ void dq_row(PB B, IT bias, IT start, IT end, long lon
   int before = inc - c;
   for (int w = 0; w < wave; ++w) before += wtot[w];
   const int cnt = wtot[0] + wtot[1] + wtot[2] + wtot[3];
-{_lookback(lookback) if not (abl & 4 or nolb) else "  const long long gl0 = 0;"}
+{_lookback() if not (abl & 4 or nolb) else "  const long long gl0 = 0;"}
 {"  if (cnt + m == 7777777) dq_flag(vflag, (unsigned int)gl0 + (unsigned int)sstart0); return;" if abl & 8 else ""}
   if (cnt == 0) return;  // block-uniform
   double acc[{max(1, gram_width(gram) if gram else 1)}] = {{}};
@@ -692,21 +665,16 @@ def _compile(nodes, rel, gram: int = 0):
         return None  # one thread per line: wide rows take the cutter (ops/scancut.py) or scan eagerly
     (parts, udfs), refs = dqvm.nodes_key(nodes)
     head = head_bytes(f["mean_line"])
-    lookback = os.environ.get("DQ4ML_SCAN_LOOKBACK", "1") != "0"
     # Gram mode stores no row, so it needs no global line numbering: no ticket, no look-back,
     # window = blockIdx.x (the line-count fact is a property of the same cached bytes)
-    nolb = bool(gram) and lookback and os.environ.get("DQ4ML_SCAN_GRAM_NOLB", "1") != "0"
-    ticket = ticket_mode()
+    nolb = bool(gram)
     o = f["opts"]
     from .scancut import term_of
 
-    tk = term_of(f) if os.environ.get("DQ4ML_SCAN_TERM1", "1") != "0" else None
-    term_only = {(13, False): "cr", (10, False): "lf"}.get(tk)
-    fast_only = (bool(f.get("fast_only")) and not o["null_value"] and not o["trim_lead"] and not o["trim_trail"]
-                 and os.environ.get("DQ4ML_SCAN_FASTONLY", "1") != "0")
+    term_only = {(13, False): "cr", (10, False): "lf"}.get(term_of(f))
+    fast_only = bool(f.get("fast_only")) and not o["null_value"] and not o["trim_lead"] and not o["trim_trail"]
     key = (parts, udfs, tuple(rel.schema().names), tuple(f["kinds"]), tuple(f["nullable"]),
-           repr(sorted(f["opts"].items())), f["strict"], head, lookback, fast_only, _wpe(fast_only),
-           ticket, os.environ.get("DQ4ML_SCAN_ABL", "0"), gram, _scan_nt(), nolb, os.environ.get("DQ4ML_SCAN_P10"),
+           repr(sorted(f["opts"].items())), f["strict"], head, fast_only, os.environ.get("DQ4ML_SCAN_ABL", "0"), gram,
            term_only)
     cp = _CACHE.get(key)
     if cp is None and key not in _CACHE:
@@ -716,10 +684,9 @@ def _compile(nodes, rel, gram: int = 0):
             _, g, outputs, _ = dqvm.compile_chain(nodes, base, False, gen=g)
             names = _ScanPlan.SCAN_SLOTS + (("gpart",) if gram else ())
             slots = {k: g.slot(None, (k,)) for k in names}
-            src = kernel_source(g, f["kinds"], f["nullable"], g.used, f["opts"], f["strict"], head, slots, lookback,
-                                fast_only, ticket, gram, nolb, term_only)
+            src = kernel_source(g, f["kinds"], f["nullable"], g.used, f["opts"], f["strict"], head, slots, fast_only,
+                                gram=gram, nolb=nolb, term_only=term_only)
             cp = _ScanPlan(src, g, outputs, refs, gram)
-            cp.lookback = lookback
         except dqvm.Unfusable as e:
             cp = "vector" if str(e) == "VectorAssembleExpr" else None
         except _GramNullable:  # Gram mode over nullable outputs: the row-storing scan instead
@@ -745,18 +712,16 @@ def _launch(cp, nodes, rel, extra: dict, own_stream: bool = True):
     # compute stream; the compute stream waits for this scan's event before its consumers
     # (faststream: no per-call device resolution on this per-action path, profiles/r4_host_issue.md)
     cur = faststream.current(faststream.dev_index(dev))
-    side = _scan_stream(dev) if own_stream and env(b"DQ4ML_SCAN_STREAM") != b"0" else cur
+    side = _scan_stream(dev) if own_stream else cur
     with faststream.use(side):
         stream = side.cuda_stream
         nb = int(h.csv_count_blocks(n))
         # ONE zeroed scratch allocation: [offs | err, vflag | Gram partials]; offs is the
-        # look-back status + ticket counters (single pass) or the per-window counts (two passes)
-        no = nb + TICKET_WORDS if cp.lookback else nb + 1
+        # look-back status + ticket counters
+        no = nb + TICKET_WORDS
         gw = gram_width(cp.gram) if cp.gram else 0
         z = torch.zeros(no + 1 + nb * gw, dtype=torch.int64, device=dev)
         offs = z[:no]
-        if not cp.lookback:
-            h.csv_line_ends(buf.data_ptr(), n, offs.data_ptr(), 0, stream, -1, 0)
         ev = z[no:no + 1].view(torch.int32)
         err, vflag = ev[0:1], ev[1:2]
         scalars = {"buf": buf, "offs": offs, "nalloc": nalloc, "trailing": int(f["trailing"]), "vflag": vflag}
@@ -850,7 +815,7 @@ def try_fused_gram(plan, features_col: str, label_col: str, session, route_key=N
     from ..sql.plan import CsvScanRelation, Filter, Project, output_name
     from ..sql.types import BooleanType, VectorUDT, is_numeric
 
-    if os.environ.get("DQ4ML_SCAN_GRAM", "1") == "0" or session is None:
+    if session is None:
         return None
     if str(session.conf.get("dq4ml.fit.fuseScan", "true")).lower() not in ("1", "true", "yes"):
         return None
@@ -928,10 +893,8 @@ class _Route:
 
 
 _ROUTES: dict = {}
-_ROUTE_ENV = ("DQ4ML_SCAN_GRAM", "DQ4ML_SCAN_CUT", "DQ4ML_CUT_MIN_LINE", "DQ4ML_SCAN_LOOKBACK", "DQ4ML_SCAN_GRAM_NOLB",
-              "DQ4ML_SCAN_TERM1", "DQ4ML_SCAN_FASTONLY", "DQ4ML_SCAN_ABL", "DQ4ML_SCAN_P10", "DQ4ML_CUT_ABLATE",
-              "DQ4ML_CUT_STAMPS", "DQ4ML_CUT_VSTRIP", "DQ4ML_SCAN_STREAM", "DQ4ML_SCAN_NT", "DQ4ML_SCAN_TICKET", "DQ4ML_SCAN_WPE",
-              "DQ4ML_FUSE_ROUTES")
+_ROUTE_ENV = ("DQ4ML_SCAN_CUT", "DQ4ML_CUT_MIN_LINE", "DQ4ML_SCAN_ABL", "DQ4ML_CUT_ABLATE", "DQ4ML_CUT_STAMPS",
+              "DQ4ML_DIAG", "DQ4ML_FUSE_ROUTES")
 
 
 _ENV_DATA = getattr(os.environ, "_data", None)  # the process environment as bytes (CPython)
@@ -1077,28 +1040,13 @@ class _GramLaunch:
 def _run_line_gram(cp, chain, p, d) -> "FusedGram":
     gl = getattr(cp, "_gram_launch", None)
     f = p.fused
-    if cp.gram and cp.lookback:
-        key = (f["buf"].data_ptr(), int(f["n"]), int(f["nlines"]), bool(f["trailing"]))
-        if gl is None or gl.key != key:
-            gl = cp._gram_launch = _GramLaunch(cp, p)
-        flat, err, vflag = gl()
-        checks = [_fact_check(p, vflag)] + ([_udf_error_check(chain, err)] if cp.has_raise else [])
-        STATS["fused_grams"] += 1
-        return FusedGram(flat, d, [c for c in checks if c is not None], int(f["nlines"]))
-    extra = {}
-    # on the compute stream, after the previous action's fit tail: the one-workgroup solve
-    # kernel co-running with a whole-GPU scan gets ~1/8 of a CU's issue slots (22 -> 727 us,
-    # kernel trace) and holds the pipeline longer than running alone between two scans; with
-    # nothing left to overlap, a side stream would only add cross-queue waits
-    _, _, err, vflag, side, cur = _launch(cp, chain, p, extra, own_stream=False)
-    flat = window_fold(extra["gpart"], side)
-    if side is not cur:
-        cur.wait_stream(side)
-        for t in (err, flat):
-            t.record_stream(cur)  # (err, vflag and the partials share one allocation)
+    key = (f["buf"].data_ptr(), int(f["n"]), int(f["nlines"]), bool(f["trailing"]))
+    if gl is None or gl.key != key:
+        gl = cp._gram_launch = _GramLaunch(cp, p)
+    flat, err, vflag = gl()
     checks = [_fact_check(p, vflag)] + ([_udf_error_check(chain, err)] if cp.has_raise else [])
     STATS["fused_grams"] += 1
-    return FusedGram(flat, d, [c for c in checks if c is not None], int(p.fused["nlines"]))
+    return FusedGram(flat, d, [c for c in checks if c is not None], int(f["nlines"]))
 
 
 class _ChunkRel:

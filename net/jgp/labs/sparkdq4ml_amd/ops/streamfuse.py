@@ -148,7 +148,7 @@ __device__ __forceinline__ void dq_fill_raw(const GramArgs& a, unsigned char* ra
                "typedef unsigned long uintptr_t;\n")
     wrapper = f"""
 extern "C" __global__ __launch_bounds__(256) void {ENTRY}(dq4ml::GramArgs a) {{
-  dq4ml::gram_stream_f32_body<{NT}, {RING}, {CMP}, 1, 64>(a);
+  dq4ml::gram_stream_f32_body<{NT}, {RING}, {CMP}, 1>(a);
 }}
 """
     return prelude + _device_text() + pred + _stream_text() + wrapper

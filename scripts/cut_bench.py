@@ -6,7 +6,9 @@ cache is keyed by its knobs), e.g.
 
     DQ4ML_DIAG=1 VARIANTS="base;DQ4ML_SCAN_CUT=0;DQ4ML_CUT_ABLATE=1" python scripts/cut_bench.py --features 32 --rows 2e7
 
-Prints one JSON line per variant: ms per action (median of --reps), CSV GB/s.
+Prints one JSON line per variant: ms per action (median of --reps), CSV GB/s.  The diagnostic
+builds (DQ4ML_CUT_ABLATE, and DQ4ML_CUT_STAMPS=1 for the per-phase cycle counts) need DQ4ML_DIAG=1,
+in the environment or in the variant ("DQ4ML_CUT_STAMPS=1,DQ4ML_DIAG=1").
 """
 import argparse
 import json

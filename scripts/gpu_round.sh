@@ -58,11 +58,6 @@ for s in $STEPS; do
           step f32s_b3 300 python bench.py --steps 20 --warmup 3 --dtype fp32 &&
           step f32s_b4 300 python bench.py --steps 20 --warmup 3 --dtype fp32split &&
           (export TMPDIR=/tmp; step f32spmc 300 timeout -s KILL 240 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_INSTS_VALU SQ_INSTS_LDS SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_SALU GRBM_GUI_ACTIVE -d gpurun_out/f32spmc -o run --output-format csv -- python bench.py --steps 3 --warmup 1 --dtype fp32split) || exit $? ;;
-    f32sr) step f32sr_a 300 env DQ4ML_GRAM_STREAM_RING=2 python bench.py --steps 20 --warmup 3 --dtype fp32split &&
-           step f32sr_b 300 env DQ4ML_GRAM_STREAM_RING=3 python bench.py --steps 20 --warmup 3 --dtype fp32split &&
-           step f32sr_c 300 env DQ4ML_GRAM_STREAM_RING=2 python bench.py --steps 20 --warmup 3 --dtype fp32split &&
-           step f32sr_d 300 env DQ4ML_GRAM_STREAM_RING=3 python bench.py --steps 20 --warmup 3 --dtype fp32split &&
-           step f32sr_e 300 env DQ4ML_GRAM_STREAM_RING=2 python bench.py --steps 20 --warmup 3 --dtype fp32 || exit $? ;;
     f32s2) step f32s2_t 600 python -u -m pytest tests/test_gpu_kernels.py tests/test_gpu_streamfuse.py tests/test_gpu_determinism.py -m gpu -q --timeout 120 --timeout-method thread &&
            step f32s2_a 300 python bench.py --steps 20 --warmup 3 --dtype fp32split &&
            step f32s2_b 300 python bench.py --steps 20 --warmup 3 --dtype bf16 --storage fp32 &&
@@ -83,10 +78,7 @@ for s in $STEPS; do
     persist) step persist_t 600 python -u -m pytest tests/test_gpu_scanfuse.py tests/test_gpu_scancut.py tests/test_gpu_semantics.py tests/test_gpu_dqvm.py -m gpu -q --maxfail=5 --timeout 120 --timeout-method thread &&
           for r in 1 2; do
             step persist_w8_$r 300 python benchmarks/bench_csv_pipeline.py --steps 20 --warmup 3 &&
-            step persist_w6_$r 300 env DQ4ML_SCAN_WPE=6 python benchmarks/bench_csv_pipeline.py --steps 20 --warmup 3 &&
-            step persist_pc4_$r 300 env DQ4ML_SCAN_PER_CU=4 python benchmarks/bench_csv_pipeline.py --steps 20 --warmup 3 &&
-            step persist_lb_$r 300 env DQ4ML_SCAN_GRAM_NOLB=0 python benchmarks/bench_csv_pipeline.py --steps 20 --warmup 3 || exit $?; done ;;
-    cfg4ring3) step cfg4ring3 900 env DQ4ML_GRAM_STREAM_RING=3 python benchmarks/bench_dq_pipeline.py --steps 5 --warmup 2 ;;
+            step persist_pc4_$r 300 env DQ4ML_SCAN_PER_CU=4 python benchmarks/bench_csv_pipeline.py --steps 20 --warmup 3 || exit $?; done ;;
     cfg4nodqs) step cfg4nodqs 900 env DQ4ML_DQ_STREAM=0 python benchmarks/bench_dq_pipeline.py --steps 5 --warmup 2 ;;
     gang) step gang_t 600 python -u -m pytest tests/test_gpu_wide.py -m gpu -q --maxfail=3 --timeout 120 --timeout-method thread &&
           step gang_ab 900 env N=1e7 D=4096 EB=8 REPS=5 VARIANTS="${VARIANTS:-5:morton:8:gang,4:morton:8:0:q2}" python scripts/wide_bench.py ;;
@@ -99,13 +91,6 @@ for s in $STEPS; do
        step gangpmc2 300 timeout -s KILL 240 rocprofv3 --kernel-trace --pmc TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum GRBM_GUI_ACTIVE -d gpurun_out/gangpmc2 -o run --output-format csv -- python scripts/wide_bench.py) || exit $? ;;
     cfg5) step cfg5 900 python benchmarks/bench_wide.py --steps ${CFG5_STEPS:-10} --warmup 2 --json-out gpurun_out/cfg5.json ;;
     csv) step csv 600 python benchmarks/bench_csv_pipeline.py --steps 20 --warmup 3 --json-out gpurun_out/csv.json ;;
-    p10ab) for r in 1 2; do
-         step p10_lds_$r 300 python benchmarks/bench_csv_pipeline.py --steps 20 --warmup 3 &&
-         step p10_valu_$r 300 env DQ4ML_SCAN_P10=valu python benchmarks/bench_csv_pipeline.py --steps 20 --warmup 3 || exit $?; done ;;
-    termab) for r in 1 2 3; do
-         step term_one_$r 300 python benchmarks/bench_csv_pipeline.py --steps 30 --warmup 3 &&
-         step term_gen_$r 300 env DQ4ML_SCAN_TERM1=0 python benchmarks/bench_csv_pipeline.py --steps 30 --warmup 3 || exit $?; done ;;
-    csvnogram) step csvnogram 600 env DQ4ML_SCAN_GRAM=0 python benchmarks/bench_csv_pipeline.py --steps 20 --warmup 3 ;;
     cfg1) step cfg1 300 python benchmarks/bench_cpu_small.py --json-out gpurun_out/cfg1.json ;;
     prof4) step prof4 600 env WHICH=cfg4 python scripts/step_profile.py ;;
     prof4h) step prof4h 600 env WHICH=cfg4 ROWS=1e6 REPS=50 SORT=tottime TOP=45 python scripts/step_profile.py &&
@@ -163,31 +148,17 @@ for s in $STEPS; do
        step syrkpmc2 300 timeout -s KILL 240 rocprofv3 --kernel-trace --pmc SQ_WAIT_ANY SQ_INSTS_VMEM SQ_INSTS_MFMA SQ_WAIT_INST_LDS GRBM_GUI_ACTIVE -d gpurun_out/syrkpmc2 -o run --output-format csv -- python scripts/syrk_bench.py) || exit $? ;;
     cpubase) step cpubase 600 python scripts/cpu_baseline.py --rows 2e7 --threads 16 ;;
     scangram) for v in ${SCANABL:-0}; do step scangram$v 300 env DQ4ML_DIAG=1 DQ4ML_SCAN_ABL=$v python scripts/scan_ablation.py --gram; done && step scantable 300 python scripts/scan_ablation.py ;;
-    scanabl) for v in ${SCANABL:-0 1 5 9 13 0}; do step scanabl${DQ4ML_SCAN_TICKET:-xcd}$v 300 env DQ4ML_DIAG=1 DQ4ML_SCAN_ABL=$v python scripts/scan_ablation.py; done ;;
+    scanabl) for v in ${SCANABL:-0 1 5 9 13 0}; do step scanabl$v 300 env DQ4ML_DIAG=1 DQ4ML_SCAN_ABL=$v python scripts/scan_ablation.py; done ;;
     asynctests) step asynctests 600 python -m pytest tests/test_gpu_async_fit.py -q -m gpu ;;
     fitprof) step fitprof 300 env N=1.25e7 python scripts/fit_profile.py ;;
     dist2) step dist2 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 scripts/dist_rehearsal.py ;;
     benchf32) step benchf32 600 python bench.py --steps 10 --warmup 2 --dtype fp32 ;;
-    benchf32r3) step benchf32r3 600 env DQ4ML_GRAM_STREAM_RING=3 python bench.py --steps 10 --warmup 2 --dtype fp32 ;;
     benchf64) step benchf64 600 python bench.py --steps 10 --warmup 2 --dtype fp64 ;;
-    benchf64old) step benchf64old 600 env DQ4ML_GRAM_STREAM=0 python bench.py --steps 10 --warmup 2 --dtype fp64 ;;
     benchf64s32) step benchf64s32 600 python bench.py --steps 10 --warmup 2 --dtype fp64 --storage fp32 ;;
     benchs32) step benchs32 600 python bench.py --steps 10 --warmup 2 --dtype bf16 --storage fp32 ;;
     benchcols) step benchcols 600 python bench.py --steps 10 --warmup 2 --dtype bf16 --storage f32cols ;;
-    benchring2) step benchring2 600 env DQ4ML_GRAM_STREAM_RING=2 python bench.py --steps 10 --warmup 2 --dtype fp32 ;;
-    benchring2f64) step benchring2f64 600 env DQ4ML_GRAM_STREAM_RING=2 python bench.py --steps 10 --warmup 2 --dtype fp64 ;;
-    benchring2cols) step benchring2cols 600 env DQ4ML_GRAM_STREAM_RING=2 python bench.py --steps 10 --warmup 2 --dtype bf16 --storage f32cols ;;
     kprofcols) (export TMPDIR=/tmp; step kprofcols 600 rocprofv3 --kernel-trace --stats -d gpurun_out/kprofcols -o run --output-format csv -- python bench.py --steps 5 --warmup 1 --storage f32cols) || exit $? ;;
     kprofcsv) (export TMPDIR=/tmp; step kprofcsv 600 rocprofv3 --kernel-trace --stats -d gpurun_out/kprofcsv -o run --output-format csv -- python benchmarks/bench_csv_pipeline.py --steps 5 --warmup 2) || exit $? ;;
-    csvtwopass) step csvtwopass 600 env DQ4ML_SCAN_LOOKBACK=0 python benchmarks/bench_csv_pipeline.py --steps 20 --warmup 3 ;;
-    csvnostream) step csvnostream 600 env DQ4ML_SCAN_STREAM=0 python benchmarks/bench_csv_pipeline.py --steps 20 --warmup 3 ;;
-    csvnt) step csvnt 600 env DQ4ML_SCAN_NT=1 python benchmarks/bench_csv_pipeline.py --steps 20 --warmup 3 ;;
-    csvntt) step csvntt 600 env DQ4ML_SCAN_NT=1 python -u -m pytest tests/test_gpu_scanfuse.py -q -m gpu --timeout 120 --timeout-method thread ;;
-    csvlb) step csvlb 600 env DQ4ML_SCAN_GRAM_NOLB=0 python benchmarks/bench_csv_pipeline.py --steps 20 --warmup 3 ;;
-    csvnoswar) step csvnoswar 600 env DQ4ML_SCAN_SWAR=0 python benchmarks/bench_csv_pipeline.py --steps 20 --warmup 3 ;;
-    csvwpe6) step csvwpe6 600 env DQ4ML_SCAN_WPE=6 python benchmarks/bench_csv_pipeline.py --steps 20 --warmup 3 ;;
-    csvwpe0) step csvwpe0 600 env DQ4ML_SCAN_WPE=0 python benchmarks/bench_csv_pipeline.py --steps 20 --warmup 3 ;;
-    csvwpe8) step csvwpe8 600 env DQ4ML_SCAN_WPE=8 python benchmarks/bench_csv_pipeline.py --steps 20 --warmup 3 ;;
     csvpmc) (export TMPDIR=/tmp
        step csvpmc1 300 timeout -s KILL 240 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_INSTS_VALU SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_INSTS_SALU GRBM_GUI_ACTIVE -d gpurun_out/csvpmc1 -o run --output-format csv -- python benchmarks/bench_csv_pipeline.py --steps 2 --warmup 1 --rows 2e7 &&
        step csvpmc2 300 timeout -s KILL 240 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d gpurun_out/csvpmc2 -o run --output-format csv -- python benchmarks/bench_csv_pipeline.py --steps 2 --warmup 1 --rows 2e7 &&
@@ -199,16 +170,13 @@ for s in $STEPS; do
     exitnoprof) for m in coop cumask; do step exitnoprof_$m 200 timeout -k 10 150 python scripts/prof_exit_probe.py $m || exit $?; done ;;
     qncrash) (export TMPDIR=/tmp DQ4ML_BENCH_AB=0; step qncrash 300 timeout -k 10 240 rocprofv3 --kernel-trace -d gpurun_out/qncrash -o run --output-format csv -- python benchmarks/bench_lbfgs.py --rows 2e5 --features 2048 --steps 1 --warmup 1) || exit $? ;;
     lbfgssmall) step lbfgssmall 600 python benchmarks/bench_lbfgs.py --rows 2e5 --features 8192 --steps 2 --warmup 1 ;;
-    cfg4ov) step cfg4ov_t 600 python -u -m pytest tests/test_gpu_streamfuse.py tests/test_gpu_fit_pipeline.py -m gpu -q --timeout 120 --timeout-method thread &&
-          for r in 1 2; do for m in 0 1; do
-            step cfg4ov_${m}_${r} 600 env DQ4ML_STREAM_OVERLAP=$m python benchmarks/bench_dq_pipeline.py --steps 10 --warmup 2 --json-out gpurun_out/cfg4ov_${m}_${r}.json || exit $?; done; done ;;
     cutab) (export TMPDIR=/tmp
        step cutab_t 600 python -u -m pytest tests/test_gpu_scancut.py tests/test_gpu_scanfuse.py -m gpu -q --maxfail=5 --timeout 120 --timeout-method thread &&
        step cutab_w32 900 env VARIANTS="${CUTV:-base}" python scripts/cut_bench.py --features 32 --rows ${CUT_ROWS:-1e8} --reps ${CUT_REPS:-5}) || exit $? ;;
     labab) (export TMPDIR=/tmp
        step labab_t 600 python -u -m pytest tests/test_gpu_scanfuse.py tests/test_gpu_scancut.py tests/test_gpu_dqvm.py tests/test_gpu_semantics.py -m gpu -q --maxfail=5 --timeout 120 --timeout-method thread &&
        step labab 900 env VARIANTS="${LABV:-base}" python scripts/cut_bench.py --rows ${LAB_ROWS:-1e8} --reps ${LAB_REPS:-20}) || exit $? ;;
-    cutstamps) step cutstamps 600 env VARIANTS="base;DQ4ML_CUT_STAMPS=1" python scripts/cut_bench.py --features 32 --rows 1e8 --reps 5 ;;
+    cutstamps) step cutstamps 600 env DQ4ML_DIAG=1 VARIANTS="base;DQ4ML_CUT_STAMPS=1" python scripts/cut_bench.py --features 32 --rows 1e8 --reps 5 ;;
     csvshard) step csvshard 600 python benchmarks/bench_csv_pipeline.py --rows 1.25e7 --steps 200 --warmup 20 --json-out gpurun_out/csvshard.json &&
               step csvshard2 600 python benchmarks/bench_csv_pipeline.py --rows 1.25e7 --steps 200 --warmup 20 --json-out gpurun_out/csvshard2.json || exit $? ;;
     x4) step lbfgs1 900 env DQ4ML_BENCH_AB=0 python benchmarks/bench_lbfgs.py --steps 3 --warmup 1 --json-out gpurun_out/lbfgs1.json &&

@@ -1,7 +1,7 @@
 """Fit-tail CU headroom at the 8-GPU strong-scaling shard (VERDICT r4 "next" #3).
 
 Pipelined asynchronous fits of the headline shape at one rank's share (1.25e7 x 32 bf16 by
-default).  After every fit's all-reduce a stand-in kernel (``DQ4ML_TAIL_STANDIN`` blocks:usec,
+default).  After every fit's all-reduce a stand-in kernel (``regression.set_tail_standin`` blocks:usec,
 ``rowops.hip`` standin: the shape of an RCCL all-reduce's channel blocks) runs on the tail stream;
 timing events around it give how long it waited for CUs beside the next fit's Gram pass.
 Alternates ``dq4ml.gram.reserveCUs`` 0 / 8 (or REPS x RESERVES) in one process:

@@ -54,7 +54,7 @@ def test_codegen_compiles(cpu_session, tmp_path):
         assert r.returncode == 0, r.stderr + "\n" + code
 
 
-@pytest.mark.parametrize("nullable,fast,ticket", [((False, False), True, "xcd"), ((True, True), False, "global"),
+@pytest.mark.parametrize("nullable,fast,ticket", [((False, False), True, "xcd"), ((True, True), False, "xcd"),
                                                    ((True, False), True, "none")])
 def test_scan_fused_codegen_compiles(cpu_session, tmp_path, nullable, fast, ticket):
     """The fused scan + DQ kernel (ops/scanfuse.py) of the lab chain over a CSV relation whose
@@ -96,7 +96,7 @@ def test_scan_fused_codegen_compiles(cpu_session, tmp_path, nullable, fast, tick
     _, g, outputs, _ = dqvm.compile_chain(nodes, base, False, gen=g)
     slots = {k: g.slot(None, (k,)) for k in scanfuse._ScanPlan.SCAN_SLOTS}
     src = scanfuse.kernel_source(g, fused["kinds"], fused["nullable"], g.used, fused["opts"], False, 256, slots,
-                                 True, fast, ticket)
+                                 fast, ticket)
     if not any(nullable):
         assert [t for t in g.recipe if t[0] in ("out", "outvalid", "selout")] == [("out", 0), ("out", 1), ("selout",)]
     assert ("dq_flag((unsigned int*)p[" in src) == nullable[1]  # RaiseIfNull only when price may be null
@@ -159,7 +159,7 @@ def test_scan_fused_gram_codegen_compiles(cpu_session, tmp_path, string_col):
     slots = {k: g.slot(None, (k,)) for k in scanfuse._ScanPlan.SCAN_SLOTS + ("gpart",)}
     fast = not string_col  # (a string column is never on the numeric fast path)
     src = scanfuse.kernel_source(g, fused["kinds"], fused["nullable"], g.used, fused["opts"], False, 256, slots,
-                                 True, fast, "xcd", 1)
+                                 fast, "xcd", 1)
     assert scanfuse.gram_width(1) == 6 and "gred[4][6]" in src
     assert ("= !csv_field_span(" in src) == string_col
     assert "[li] =" not in src  # no row is stored
@@ -173,7 +173,7 @@ def test_scan_fused_gram_codegen_compiles(cpu_session, tmp_path, string_col):
     assert r.returncode == 0, r.stderr
     # the default Gram-mode build: no global line numbering (no ticket, no look-back, no nalloc check)
     src2 = scanfuse.kernel_source(g, fused["kinds"], fused["nullable"], g.used, fused["opts"], False, 256, slots,
-                                  True, fast, "xcd", 1, nolb=True)
+                                  fast, "xcd", 1, nolb=True)
     assert "__hip_atomic_fetch_add" not in src2 and "sgl0 = pre" not in src2 and "li >= nalloc" not in src2
     assert "const long long blk = blockIdx.x;" in src2 and "sgl0 = pre" in src
     f2 = tmp_path / "scan_gram_nolb.hip"

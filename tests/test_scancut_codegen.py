@@ -133,6 +133,7 @@ def _cut_source(spark, d, lab, stamps=False, quoted=False, max_line=None, shape=
 def test_cut_kernel_compiles_for_gfx950(cpu_session, tmp_path, monkeypatch, d, lab, stamps, quoted):
     if stamps:  # the diagnostic phase-clock build
         monkeypatch.setenv("DQ4ML_CUT_STAMPS", "1")
+        monkeypatch.setenv("DQ4ML_DIAG", "1")
     src = _cut_source(cpu_session, d, lab, stamps, quoted)
     assert ("qany" in src) == quoted  # quoted fast-path numbers: bounds inside the quotes
     assert ("s_memtime" in src) == stamps

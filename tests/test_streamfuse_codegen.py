@@ -53,7 +53,7 @@ def test_config4_prologue_compiles_with_hiprtc(cpu_session):
     cp = streamfuse._compile(chain, rel, feat, 2)
     assert cp is not None and (cp.NT, cp.RING) == (2, 2)
     assert [r[0] for r in cp.layout] == ["v", "v", "m", "m"]
-    assert "dq_row_pred" in cp.src and "gram_stream_f32_body<2, 2, 1, 1, 64>" in cp.src
+    assert "dq_row_pred" in cp.src and "gram_stream_f32_body<2, 2, 1, 1>" in cp.src
     from net.jgp.labs.sparkdq4ml_amd.ops import native
 
     try:
