@@ -58,6 +58,11 @@ struct GramArgs {
   // aligned and allocated in whole 32-bit words (the kernel reads the aligned word around a byte).
   const uint32_t* xpack;
   const uint8_t* xdir;
+  // the all-packed ("patched") companion instead (patch_tiles below; null: none): xpack holds a
+  // slot for every entry of the full supersteps, xrec one 16-byte directory record per entry
+  // (16-byte aligned) and xovf the overflow records of entries with more than three exceptions
+  const uint32_t* xrec;
+  const uint32_t* xovf;
 };
 
 #ifndef __HIPCC_RTC__
@@ -81,6 +86,29 @@ void tile_bf16(const void* X, int xdt, int64_t ld, int d, int64_t n, void* out, 
 // caller) counts the packed entries.  One wave per entry.
 void pack_tiles(const void* tiles, int d, int64_t n, uint8_t* dir, uint32_t* slots, uint32_t* npacked,
                 hipStream_t st);
+
+// The patched companion (torch reference: ops/layout.py patch_reference): EVERY entry of the full
+// supersteps is packed (d a multiple of 32; the zero-padded ragged superstep is not covered and is
+// read raw).  base = emin where emax - emin <= 15 (the slot is then pack_tiles' bit for bit), else
+// emax - 15.  A value whose exponent field is below base is an exception: its slot code is the
+// filler 0 (it decodes to +2^(base-127)) and its 16 stored bits travel in a record
+//     lane << 21 | dword << 17 | halfword << 16 | bits
+// (dword = 4 * k-step + the dword within the lane's fragment, so record >> 16 is the halfword's
+// index among the lane-major 2048 of the entry).  The records of an entry are sorted by that
+// index: a pure function of the data.  Directory record of entry e, four dwords at rec[4 e]:
+//     word 0 = base | count << 8
+//     count <= 3: words 1.. = the records themselves (unused words 0)
+//     count >  3: word 1 = index into ovf of the entry's first record, all of them there
+// The reader decodes the slot like any packed one and then writes each record's bits over the
+// named halfword of the owning lane, which restores the raw tile bit for bit.
+// patch_tiles_count: counts[e] = exceptions of entry e, stat[0] += their total, stat[1] = max
+// (stat zeroed by the caller).  The caller accepts or rejects the table on those, turns counts
+// into ovoff (exclusive running sum of the counts above 3) and calls patch_tiles_fill with rec
+// zeroed.  One wave per entry in both.
+constexpr int kPatchInline = 3;
+void patch_tiles_count(const void* tiles, int64_t nent, uint32_t* counts, unsigned long long* stat, hipStream_t st);
+void patch_tiles_fill(const void* tiles, int64_t nent, const uint32_t* ovoff, uint32_t* slots, uint32_t* rec,
+                      uint32_t* ovf, hipStream_t st);
 
 int64_t gram_partial_stride(int mode, int d);
 int gram_default_blocks(int64_t n);

@@ -244,7 +244,9 @@ __device__ __forceinline__ void slab_put(double* p, double v) {
 // ---- 12-bit packed tiles (gram.h: pack_tiles) -------------------------------------------------
 // One lane's three 16-byte pieces of a packed entry -> its four raw fragments.  B2 = base << 7 in
 // both halfwords; code + B2 <= 0x7FFF per halfword, so the add never reaches a sign bit.
-__device__ __forceinline__ void unpack_tile(const u32x4 (&raw)[4], uint32_t B2, bf16x8 (&fr)[4]) {
+// (NP: the caller's pieces per buffer -- four where an entry may also be raw, three where not)
+template <int NP>
+__device__ __forceinline__ void unpack_tile(const u32x4 (&raw)[NP], uint32_t B2, bf16x8 (&fr)[4]) {
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const uint32_t d0 = raw[0][i], d1 = raw[1][i], d2 = raw[2][i];
@@ -261,13 +263,34 @@ __device__ __forceinline__ void unpack_tile(const u32x4 (&raw)[4], uint32_t B2, 
   }
 }
 
+// One exception record of the patched companion (gram.h: patch_tiles) into the decoded fragments:
+// the owning lane writes the record's 16 bits over the named halfword of the named dword (a
+// select on every dword; the record is wave-uniform, so the comparisons are scalar).
+__device__ __forceinline__ void patch_frags(bf16x8 (&fr)[4], uint32_t rec, int lane) {
+  const uint32_t dw = (rec >> 17) & 15u;
+  const bool hi = ((rec >> 16) & 1u) != 0;
+  const uint32_t keep = hi ? 0x0000FFFFu : 0xFFFF0000u;
+  const uint32_t val = hi ? rec << 16 : rec & 0xFFFFu;
+  const bool mine = (int)(rec >> 21) == lane;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    u32x4 u = __builtin_bit_cast(u32x4, fr[i]);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) u[j] = (mine && dw == (uint32_t)(4 * i + j)) ? ((u[j] & keep) | val) : u[j];
+    fr[i] = __builtin_bit_cast(bf16x8, u);
+  }
+}
+
 // =============================================================================================
 // bf16 MFMA kernel
 // =============================================================================================
-template <typename TX, int NT, int XMODE, bool TILED, bool HALF = false, bool PACKED = false>
+// PATCHED (tiled storage, XMODE 0, no weights, no selection, f32 label): every full superstep is
+// read from the patched companion, the ragged tail from the raw tiles.
+template <typename TX, int NT, int XMODE, bool TILED, bool HALF = false, bool PACKED = false, bool PATCHED = false>
 __global__ __launch_bounds__((BF16Geom<NT, XMODE, HALF>::kBlock), (BF16Geom<NT, XMODE, HALF>::kMinBlocks)) void
 gram_tall_bf16_kernel(GramArgs a) {
   static_assert(!PACKED || TILED, "the packed companion belongs to tiled storage");
+  static_assert(!PATCHED || (TILED && !PACKED && XMODE == 0), "the patched companion: tiled storage, XMODE 0");
   typedef BF16Geom<NT, XMODE, HALF> Geo;
   constexpr int NPAIR = NT * (NT + 1) / 2;
   // LDS: per wave 4 cols x 64 rows bf16 (W fragments) + 64 f32 row weights; reused for the
@@ -299,7 +322,8 @@ gram_tall_bf16_kernel(GramArgs a) {
 
   // (packed: the wave index as a scalar, so the superstep loop and its directory branches are
   // scalar control flow)
-  const int64_t gw = (int64_t)blockIdx.x * Geo::kWaves + (PACKED ? __builtin_amdgcn_readfirstlane(wave) : wave);
+  const int64_t gw =
+      (int64_t)blockIdx.x * Geo::kWaves + ((PACKED || PATCHED) ? __builtin_amdgcn_readfirstlane(wave) : wave);
   const int64_t total_waves = (int64_t)gridDim.x * Geo::kWaves;
   int64_t s0 = gw * a.spw;
   int64_t s1 = s0 + a.spw;
@@ -478,6 +502,96 @@ gram_tall_bf16_kernel(GramArgs a) {
       dir_bytes(a.nsuper, dv, dA);
       pk_load(a.nsuper, dA, A, lane);
       pk_compute(a.nsuper, dA, A, pk_y(a.nsuper));
+    }
+  } else if constexpr (PATCHED) {
+    // The all-packed companion: the packed loop's wave -> superstep map and buffer swap with no
+    // conditional vector load in it.  Every superstep issues three 1 KiB pieces per tile and its
+    // f32 label (s < nsuper implies row < n: no guard), so the waits in front of a decode count
+    // exactly the next superstep's loads as still in flight.  After a wave's last superstep the
+    // "next" is the packed loop's placeholder: slot 0 at lane offset 0 and the wave's own label
+    // again.  An entry's 16-byte directory record comes by a scalar load issued a whole compute
+    // ahead (the scalar counter is not the tile loads'); its exceptions are patched into the
+    // decoded fragments under a uniform branch on the count, so the MFMA operands are the raw
+    // tile's bits.
+    const int64_t step = a.interleave ? total_waves : 1;
+    const int64_t end = a.interleave ? a.nsuper : s1;
+    int64_t s = a.interleave ? gw : s0;
+    const u32x4* recs = reinterpret_cast<const u32x4*>(a.xrec);
+    const uint32_t* yp = reinterpret_cast<const uint32_t*>(a.y);
+    auto pt_dir = [&](int64_t s, u32x4 (&dr)[NT]) {
+#pragma unroll
+      for (int t = 0; t < NT; ++t) dr[t] = recs[s * NT + t];
+    };
+    // (the label first: it is the one loaded register that the loop carries under another name
+    // than it is loaded to, and a copy on the back edge then waits for the oldest load in flight,
+    // not for the tile pieces behind it)
+    auto pt_load = [&](int64_t s, u32x4 (&raw)[NT][3], uint32_t& yb, int ln, int64_t sy) {
+      yb = yp[sy * 64 + lane];
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        const u32x4* q = reinterpret_cast<const u32x4*>(a.xpack) + (s * NT + t) * 3 * 64 + ln;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) raw[t][k] = __builtin_nontemporal_load(q + k * 64);
+      }
+    };
+    auto pt_next = [&](int64_t s, u32x4 (&raw)[NT][3], uint32_t& yb) {
+      const bool more = s + step < end;
+      pt_load(more ? s + step : 0, raw, yb, more ? lane : 0, more ? s + step : s);
+      return more;
+    };
+    auto pt_compute = [&](const u32x4 (&dr)[NT], const u32x4 (&raw)[NT][3], uint32_t yb) {
+      bf16x8 fr[NT][4];
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        const uint32_t w0 = __builtin_amdgcn_readfirstlane(dr[t][0]);
+        const uint32_t cnt = (w0 >> 8) & 0xFFu;
+        unpack_tile(raw[t], (w0 & 0xFFu) * 0x00800080u, fr[t]);
+        if (cnt != 0) {
+          if (cnt <= (uint32_t)kPatchInline) {
+            patch_frags(fr[t], __builtin_amdgcn_readfirstlane(dr[t][1]), lane);
+            if (cnt > 1) patch_frags(fr[t], __builtin_amdgcn_readfirstlane(dr[t][2]), lane);
+            if (cnt > 2) patch_frags(fr[t], __builtin_amdgcn_readfirstlane(dr[t][3]), lane);
+          } else {  // rare (about 2.5e-5 of Gaussian entries): the records sit in the overflow table
+            const uint32_t* ov = a.xovf + __builtin_amdgcn_readfirstlane(dr[t][1]);
+            for (uint32_t c = 0; c < cnt; ++c) patch_frags(fr[t], __builtin_amdgcn_readfirstlane(ov[c]), lane);
+          }
+        }
+      }
+      // row_vals of a live, unweighted row: w = 1, wy = y
+      const double y = (double)__uint_as_float(yb);
+      compute_rv(RowVals{true, 1.0, y, y}, fr);
+    };
+    if (s < end) {
+      u32x4 A[NT][3], B[NT][3], dA[NT], dB[NT], dv[NT];
+      uint32_t yA, yB;
+      pt_dir(s, dA);
+      pt_load(s, A, yA, lane, s);
+#pragma unroll
+      for (int t = 0; t < NT; ++t) dv[t] = dA[t];
+      if (s + step < end) pt_dir(s + step, dv);
+      // Whole pairs of supersteps per trip and ONE exit, at the bottom: a second exit between the
+      // two computes gets merged with the back edge, and the loop head then waits for every load.
+      // A wave's odd last superstep is loaded in the last trip's second slot and computed after
+      // the loop.
+      bool left = true;  // A holds a superstep that is not computed yet
+      if (s + step < end) {
+        for (;;) {
+#pragma unroll
+          for (int t = 0; t < NT; ++t) dB[t] = dv[t];
+          pt_load(s + step, B, yB, lane, s + step);
+          if (s + 2 * step < end) pt_dir(s + 2 * step, dv);
+          pt_compute(dA, A, yA);
+          s += step;
+#pragma unroll
+          for (int t = 0; t < NT; ++t) dA[t] = dv[t];
+          left = pt_next(s, A, yA);
+          if (s + 2 * step < end) pt_dir(s + 2 * step, dv);
+          pt_compute(dB, B, yB);
+          s += step;
+          if (s + step >= end) break;
+        }
+      }
+      if (left) pt_compute(dA, A, yA);
     }
   } else
   // full supersteps: register double buffer (loads of s+1 in flight while s computes)
@@ -1358,6 +1472,101 @@ __global__ __launch_bounds__(256) void pack_tiles_kernel(const u32x4* __restrict
   if (lane == 0 && mine) atomicAdd(npacked, mine);
 }
 
+// tiles -> the patched companion (gram.h: patch_tiles); one wave per entry.  FILL = false counts
+// the exceptions (per entry, their total and the largest count); FILL = true writes slots,
+// directory records and overflow records.  An entry's records are ranked by lane (a wave scan of
+// the lanes' counts), then dword, then halfword: the order is a function of the data alone.
+template <bool FILL>
+__global__ __launch_bounds__(256) void patch_tiles_kernel(const u32x4* __restrict__ tiles, int64_t nent,
+                                                         uint32_t* __restrict__ counts,
+                                                         unsigned long long* __restrict__ stat,
+                                                         const uint32_t* __restrict__ ovoff, u32x4* __restrict__ slots,
+                                                         uint32_t* __restrict__ rec, uint32_t* __restrict__ ovf) {
+  const int lane = threadIdx.x & 63;
+  const int64_t w0 = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  const int64_t nw = (int64_t)gridDim.x * (blockDim.x >> 6);
+  unsigned long long total = 0;
+  uint32_t most = 0;
+  for (int64_t e = w0; e < nent; e += nw) {
+    u32x4 r[4];
+    uint32_t emin = 255u, emax = 0u;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      r[i] = tiles[(e * 4 + i) * 64 + lane];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const uint32_t lo = (r[i][j] >> 7) & 0xFFu, hi = (r[i][j] >> 23) & 0xFFu;
+        emin = min(emin, min(lo, hi));
+        emax = max(emax, max(lo, hi));
+      }
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+      emin = min(emin, (uint32_t)__shfl_xor((int)emin, o, 64));
+      emax = max(emax, (uint32_t)__shfl_xor((int)emax, o, 64));
+    }
+    const uint32_t base = emax - emin <= 15u ? emin : emax - 15u;
+    uint32_t c = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        c += (((r[i][j] >> 7) & 0xFFu) < base ? 1u : 0u) + (((r[i][j] >> 23) & 0xFFu) < base ? 1u : 0u);
+    uint32_t incl = c;  // inclusive scan of the lanes' counts
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const uint32_t up = (uint32_t)__shfl_up((int)incl, o, 64);
+      if (lane >= o) incl += up;
+    }
+    const uint32_t tot = (uint32_t)__shfl((int)incl, 63, 64);
+    if constexpr (!FILL) {
+      if (lane == 0) counts[e] = tot;
+      total += tot;
+      most = max(most, tot);
+    } else {
+      const bool inl = tot <= (uint32_t)kPatchInline;
+      uint32_t* dst = inl ? rec + e * 4 + 1 : ovf + ovoff[e];
+      uint32_t rank = incl - c;
+      const uint32_t fill = base << 7;  // code 0 in the window
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+          for (int hf = 0; hf < 2; ++hf) {
+            const uint32_t bits = (r[i][j] >> (16 * hf)) & 0xFFFFu;
+            if (((bits >> 7) & 0xFFu) < base) {
+              dst[rank++] = ((uint32_t)lane << 21) | ((uint32_t)(4 * i + j) << 17) | ((uint32_t)hf << 16) | bits;
+              r[i][j] = (r[i][j] & (hf ? 0x0000FFFFu : 0xFFFF0000u)) | (fill << (16 * hf));
+            }
+          }
+      if (lane == 0) {
+        rec[e * 4] = base | (tot << 8);
+        if (!inl) rec[e * 4 + 1] = ovoff[e];
+      }
+      const uint32_t B2 = base * 0x00800080u;
+      u32x4 D[3];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const uint32_t p3 = (r[i][3] & 0x7FFF7FFFu) - B2;  // 11-bit codes: no borrow between halfwords
+#pragma unroll
+        for (int k = 0; k < 3; ++k) D[k][i] = (r[i][k] & 0x80008000u) | ((r[i][k] & 0x7FFF7FFFu) - B2);
+        D[0][i] |= (p3 & 0x000F000Fu) << 11;
+        D[1][i] |= (p3 & 0x00F000F0u) << 7;
+        D[2][i] |= ((p3 & 0x07000700u) << 3) | ((r[i][3] & 0x80008000u) >> 1);
+      }
+#pragma unroll
+      for (int k = 0; k < 3; ++k) slots[(e * 3 + k) * 64 + lane] = D[k];
+    }
+  }
+  if constexpr (!FILL) {
+    if (lane == 0 && total) {
+      atomicAdd(stat, total);
+      atomicMax(stat + 1, (unsigned long long)most);
+    }
+  }
+}
+
 // Un-shift of the packed statistics (gram.h: stats_unshift).  Pass 1 rewrites the Σxxᵀ entries
 // (reading the shifted column sums and Σw, which it does not write), pass 2 the column sums.
 __global__ __launch_bounds__(256) void unshift_aa_kernel(double* __restrict__ flat, const float* __restrict__ shift,
@@ -1431,6 +1640,28 @@ void pack_tiles(const void* tiles, int d, int64_t n, uint8_t* dir, uint32_t* slo
   if (g > 16384) g = 16384;
   hipLaunchKernelGGL(pack_tiles_kernel, dim3(g), dim3(256), 0, st, reinterpret_cast<const u32x4*>(tiles), nent, dir,
                      reinterpret_cast<u32x4*>(slots), npacked);
+  DQ_HIP_CHECK(hipGetLastError());
+}
+
+static int patch_grid(int64_t nent) {
+  int64_t g = (nent + 3) / 4;
+  return (int)(g > 16384 ? 16384 : g);
+}
+
+void patch_tiles_count(const void* tiles, int64_t nent, uint32_t* counts, unsigned long long* stat, hipStream_t st) {
+  if (nent < 1) return;
+  hipLaunchKernelGGL(patch_tiles_kernel<false>, dim3(patch_grid(nent)), dim3(256), 0, st,
+                     reinterpret_cast<const u32x4*>(tiles), nent, counts, stat, (const uint32_t*)nullptr,
+                     (u32x4*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr);
+  DQ_HIP_CHECK(hipGetLastError());
+}
+
+void patch_tiles_fill(const void* tiles, int64_t nent, const uint32_t* ovoff, uint32_t* slots, uint32_t* rec,
+                      uint32_t* ovf, hipStream_t st) {
+  if (nent < 1) return;
+  hipLaunchKernelGGL(patch_tiles_kernel<true>, dim3(patch_grid(nent)), dim3(256), 0, st,
+                     reinterpret_cast<const u32x4*>(tiles), nent, (uint32_t*)nullptr, (unsigned long long*)nullptr, ovoff,
+                     reinterpret_cast<u32x4*>(slots), rec, ovf);
   DQ_HIP_CHECK(hipGetLastError());
 }
 
@@ -1619,8 +1850,12 @@ void gram_tall(int mode, GramArgs a, int xmode, int blocks, double* out, hipStre
   a.P = (int)gram_partial_stride(mode, a.d);
   const size_t lds = mode == GRAM_BF16 ? bf16_lds(a.d, xmode) : f64_lds(a.d);
   if (a.tiled && mode != GRAM_BF16) throw std::invalid_argument("gram_tall: tiled storage needs bf16 mode");
-  if ((a.xpack != nullptr) != (a.xdir != nullptr) || (a.xpack && !(a.tiled && mode == GRAM_BF16)))
-    throw std::invalid_argument("gram_tall: packed tiles come as a slot buffer plus a directory, with tiled bf16 storage");
+  if ((a.xpack != nullptr) != ((a.xdir != nullptr) != (a.xrec != nullptr)) || (a.xpack && !(a.tiled && mode == GRAM_BF16)))
+    throw std::invalid_argument("gram_tall: packed tiles come as a slot buffer plus one directory, with tiled bf16 storage");
+  if (a.xrec && (xmode != 0 || a.w || a.sel || a.ydt != DT_F32 || a.xdt != DT_BF16 || (a.d & 31) || a.nsuper < 1 ||
+                 !a.xovf || (reinterpret_cast<uintptr_t>(a.xrec) & 15) || (reinterpret_cast<uintptr_t>(a.xpack) & 15)))
+    throw std::invalid_argument("gram_tall: patched tiles need d a multiple of 32, a full superstep, an f32 label, no "
+                                "weights or selection, and 16-byte aligned slots and directory records");
   if (a.xpack && a.w && xmode != 2) throw std::invalid_argument("gram_tall: packed tiles with weights need xmode 2");
   if (a.xpack && ((a.ydt != DT_F32 && a.ydt != DT_F64) || (reinterpret_cast<uintptr_t>(a.xdir) & 3) ||
                   (reinterpret_cast<uintptr_t>(a.xpack) & 15)))
@@ -1645,6 +1880,11 @@ void gram_tall(int mode, GramArgs a, int xmode, int blocks, double* out, hipStre
     return;
   } else if (mode == GRAM_F32 || mode == GRAM_F32S) {
     throw std::invalid_argument("gram_tall(f32): needs 16-byte aligned f32 features and f32/f64 labels");
+  } else if (a.xrec) {
+    if (a.d <= 32)
+      hipLaunchKernelGGL((gram_tall_bf16_kernel<uint16_t, 1, 0, true, true, false, true>), dim3(blocks), dim3(block), lds, st, a);
+    else
+      hipLaunchKernelGGL((gram_tall_bf16_kernel<uint16_t, 2, 0, true, false, false, true>), dim3(blocks), dim3(block), lds, st, a);
   } else {
     with_kernel(mode, a.xdt, a.d, xmode, a.tiled != 0, a.xpack != nullptr,
                 [&](auto kern) { hipLaunchKernelGGL(kern, dim3(blocks), dim3(block), lds, st, a); });

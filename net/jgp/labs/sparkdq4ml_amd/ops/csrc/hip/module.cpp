@@ -144,6 +144,33 @@ PYBIND11_MODULE(_dq4ml_hip, m) {
                          uintptr_t stream) {
     pack_tiles(P<const void>(tiles), d, n, P<uint8_t>(dir), P<uint32_t>(slots), P<uint32_t>(npacked), as_stream(stream));
   });
+  // tiled bf16 storage with its patched companion (gram.h: patch_tiles): unweighted, unselected
+  // rows and an f32 label
+  m.def("gram_tall_patched",
+        [](uintptr_t X, uintptr_t xpack, uintptr_t xrec, uintptr_t xovf, int d, int64_t n, uintptr_t y, int ydt,
+           uintptr_t partials, int blocks, uintptr_t out, uintptr_t stream, bool reduce) {
+          GramArgs a{};
+          a.tiled = 1;
+          a.X = P<const void>(X);
+          a.xpack = P<const uint32_t>(xpack);
+          a.xrec = P<const uint32_t>(xrec);
+          a.xovf = P<const uint32_t>(xovf);
+          a.d = d;
+          a.n = n;
+          a.xdt = DT_BF16;
+          a.y = P<const void>(y);
+          a.ydt = ydt;
+          a.partials = P<double>(partials);
+          gram_tall(GRAM_BF16, a, 0, blocks, P<double>(out), as_stream(stream), reduce);
+        });
+  m.def("patch_tiles_count", [](uintptr_t tiles, int64_t nent, uintptr_t counts, uintptr_t stat, uintptr_t stream) {
+    patch_tiles_count(P<const void>(tiles), nent, P<uint32_t>(counts), P<unsigned long long>(stat), as_stream(stream));
+  });
+  m.def("patch_tiles_fill", [](uintptr_t tiles, int64_t nent, uintptr_t ovoff, uintptr_t slots, uintptr_t rec,
+                               uintptr_t ovf, uintptr_t stream) {
+    patch_tiles_fill(P<const void>(tiles), nent, P<const uint32_t>(ovoff), P<uint32_t>(slots), P<uint32_t>(rec),
+                     P<uint32_t>(ovf), as_stream(stream));
+  });
   m.def("gram_stream_cols",
         [](int mode, uintptr_t srcs, int d, int64_t n, int xdt, uintptr_t y, int ydt, uintptr_t w, int wdt,
            uintptr_t sel, uintptr_t partials, int blocks, uintptr_t out, uintptr_t stream, uintptr_t xshift) {

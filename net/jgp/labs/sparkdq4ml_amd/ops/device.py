@@ -125,7 +125,8 @@ def _feature_view(X: torch.Tensor, align_elems: int):
 
 
 # ------------------------------------------------------------------------------------------
-from .layout import SLOT_DWORDS, PackedTiles, TiledBF16, TiledWide  # noqa: E402
+from .layout import (PATCH_CAP, PATCH_INLINE, PATCH_SHARE, SLOT_DWORDS, PackedTiles, PatchedTiles, TiledBF16,  # noqa: E402
+                     TiledWide, patched_entries)
 from .shift import column_shift  # noqa: E402
 
 FP8_MAX = 448.0
@@ -152,8 +153,9 @@ def _unshift(h, out: torch.Tensor, shift, d: int) -> torch.Tensor:
     return out
 
 
-# Rows from which an ingested table also gets the 12-bit packed companion under pack="auto"
-# (layout.PackedTiles; DQ4ML_TILE_PACK=0 switches it off for A/B runs).
+# Rows from which an ingested table also gets a 12-bit packed companion under pack="auto": the
+# patched one (layout.PatchedTiles) where the table takes it, else the mixed one
+# (layout.PackedTiles).  DQ4ML_TILE_PACK=0 switches both off, =mixed the patched one, for A/B runs.
 PACK_MIN_ROWS = 3_000_000
 
 
@@ -174,24 +176,59 @@ def pack_tiles(T: TiledBF16) -> PackedTiles:
     return PackedTiles(dirb, slots, int(cnt.item()))
 
 
+def patch_tiles(T: TiledBF16) -> Optional[PatchedTiles]:
+    """The patched (all-packed) companion of ``T.buf``, or None where the table does not take it
+    (``layout.patch_reference`` states the rule).  A count pass, one D2H read of the exception
+    total and the largest per-entry count, then a fill pass -- ingest time, not a fit path."""
+    h = native.hip()
+    _check_dev(T.buf)
+    ne = patched_entries(T.d, T.n)
+    if ne == 0 or T.d > 64:
+        return None
+    dev = T.device
+    counts = torch.empty(ne, dtype=torch.int32, device=dev)
+    stat = torch.zeros(2, dtype=torch.int64, device=dev)
+    h.patch_tiles_count(T.buf.data_ptr(), ne, counts.data_ptr(), stat.data_ptr(), _stream())
+    nexc, most = stat.tolist()
+    if most > PATCH_CAP or nexc * PATCH_SHARE > ne * 2048:
+        return None
+    ovcnt = torch.where(counts > PATCH_INLINE, counts, torch.zeros_like(counts)).to(torch.int64)
+    ovsum = torch.cumsum(ovcnt, 0)
+    ovoff = (ovsum - ovcnt).to(torch.int32)
+    dirw = torch.zeros(ne, 4, dtype=torch.int32, device=dev)
+    slots = torch.empty(ne * SLOT_DWORDS, dtype=torch.int32, device=dev)
+    ovf = torch.zeros(int(ovsum[-1]) if nexc > PATCH_INLINE else 0, dtype=torch.int32, device=dev)
+    h.patch_tiles_fill(T.buf.data_ptr(), ne, ovoff.data_ptr(), slots.data_ptr(), dirw.data_ptr(),
+                       ovf.data_ptr() if ovf.numel() else dirw.data_ptr(), _stream())
+    return PatchedTiles(dirw, slots, ovf, nexc)
+
+
 def _maybe_pack(T: TiledBF16, pack) -> TiledBF16:
     if pack is True:
         T.packed = pack_tiles(T)
+    elif pack == "patched":
+        T.packed = patch_tiles(T)
     elif pack == "auto":
-        if os.environ.get("DQ4ML_TILE_PACK", "1") != "0" and T.n >= PACK_MIN_ROWS and T.d <= 64:
-            p = pack_tiles(T)
-            # mostly raw data (zeros, a wide dynamic range) would read a directory for nothing
-            T.packed = p if 2 * p.npacked >= p.dir.numel() else None
+        knob = os.environ.get("DQ4ML_TILE_PACK", "1")
+        if knob != "0" and T.n >= PACK_MIN_ROWS and T.d <= 64:
+            # the patched form where the table takes it (DQ4ML_TILE_PACK=mixed: never, for A/B runs)
+            T.packed = patch_tiles(T) if knob != "mixed" else None
+            if T.packed is None:
+                p = pack_tiles(T)
+                # mostly raw data (zeros, a wide dynamic range) would read a directory for nothing
+                T.packed = p if 2 * p.npacked >= p.dir.numel() else None
     elif pack is not False:
-        raise ValueError(f"pack: True, False or 'auto', not {pack!r}")
+        raise ValueError(f"pack: True, False, 'patched' or 'auto', not {pack!r}")
     return T
 
 
 def tile_bf16(X: torch.Tensor, shift="auto", pack="auto") -> TiledBF16:
     """[d, n] features -> MFMA-fragment-ordered bf16 tiles of x - s (``shift``: "auto" = the
     sampled per-column shift, None = unshifted, or an ``ops.shift.Shift``).  ``pack``: also build
-    the 12-bit packed companion the tall Gram pass reads (True / False; "auto": from
-    ``PACK_MIN_ROWS`` rows on, kept when at least half of the entries packed)."""
+    a 12-bit packed companion the tall Gram pass reads (True: the mixed one; "patched": the
+    all-packed one, or none where the table does not take it; False; "auto": from
+    ``PACK_MIN_ROWS`` rows on, the patched one if the table takes it, else the mixed one if at
+    least half of the entries packed)."""
     h = native.hip()
     _check_dev(X)
     d, n = X.shape
@@ -722,12 +759,29 @@ def _prep_rows(y, w, sel, n):
 
 
 def _tiled_pre(T: "TiledBF16", y, w, sel, xmode):
-    """Leading arguments of the tiled pass: ``gram_tall_packed`` where ``T`` carries the packed
-    companion (same grid, same wave -> superstep map, bit-identical sums), else ``gram_tall``."""
+    """The entry point of the tiled pass and its leading arguments: ``gram_tall_patched`` /
+    ``gram_tall_packed`` where ``T`` carries that companion (same grid, same wave -> superstep
+    map, bit-identical sums), else ``gram_tall``.  The patched kernel takes unweighted, unselected
+    rows with an f32 label; any other call on such a table reads the raw tiles."""
     rows = (y.data_ptr(), dtype_code(y), _ptr(w), dtype_code(w) if w is not None else 0, _ptr(sel), xmode)
-    if T.packed is not None:
-        return (T.buf.data_ptr(), T.packed.a.data_ptr(), T.packed.dir.data_ptr(), int(T.d), int(T.n)) + rows
-    return (2, T.buf.data_ptr(), 0, int(T.d), int(T.n), 2) + rows
+    if isinstance(T.packed, PatchedTiles):
+        p = T.packed
+        if xmode == 0 and w is None and sel is None and y.dtype == torch.float32:
+            ovf = p.ovf if p.ovf.numel() else p.dir
+            return "patched", (T.buf.data_ptr(), p.a.data_ptr(), p.dir.data_ptr(), ovf.data_ptr(), int(T.d), int(T.n),
+                               y.data_ptr(), dtype_code(y))
+    elif T.packed is not None:
+        return "mixed", (T.buf.data_ptr(), T.packed.a.data_ptr(), T.packed.dir.data_ptr(), int(T.d), int(T.n)) + rows
+    return None, (2, T.buf.data_ptr(), 0, int(T.d), int(T.n), 2) + rows
+
+
+def _tiled_launch(h, kind, pre, partials, nb, out, stream, reduce):
+    if kind == "patched":
+        h.gram_tall_patched(*pre, partials.data_ptr(), nb, out.data_ptr(), stream, reduce)
+    elif kind == "mixed":
+        h.gram_tall_packed(*pre, partials.data_ptr(), nb, out.data_ptr(), stream, reduce)
+    else:
+        h.gram_tall(*pre, partials.data_ptr(), nb, out.data_ptr(), stream, 1, reduce, 0)
 
 
 class TiledGramPlan:
@@ -736,7 +790,7 @@ class TiledGramPlan:
     once, so a repeated fit of the same table only allocates its outputs and launches
     (``models/regression.py`` fit replay, ~0.14 ms of device work per fit at the 8-GPU shard)."""
 
-    __slots__ = ("h", "T", "y", "w", "sel", "d", "nb", "flat_len", "part_len", "dev", "pre", "post", "packed")
+    __slots__ = ("h", "T", "y", "w", "sel", "d", "nb", "flat_len", "part_len", "dev", "pre", "post", "packed", "kind")
 
     def __init__(self, h, T: "TiledBF16", y, w, sel, x_zero_dead):
         d, n = T.d, T.n
@@ -749,7 +803,8 @@ class TiledGramPlan:
         self.nb = int(_plan_blocks(h, 2, d, n, 2, xmode))
         self.flat_len = 5 + 2 * d + d * (d + 1) // 2
         self.part_len = self.nb * int(h.gram_partial_stride(2, d))
-        self.pre = _tiled_pre(T, y, w, sel, xmode)
+        # kind: the companion this launch reads ("patched", "mixed" or None); packed: T has one
+        self.kind, self.pre = _tiled_pre(T, y, w, sel, xmode)
         self.packed = T.packed is not None
 
     def launch(self, stream: int, defer: bool):
@@ -757,10 +812,7 @@ class TiledGramPlan:
         un-shift left to the caller) or the folded, un-shifted statistics."""
         out = torch.empty(self.flat_len, dtype=torch.float64, device=self.dev)
         partials = torch.empty(self.part_len, dtype=torch.float64, device=self.dev)
-        if self.packed:
-            self.h.gram_tall_packed(*self.pre, partials.data_ptr(), self.nb, out.data_ptr(), stream, not defer)
-        else:
-            self.h.gram_tall(*self.pre, partials.data_ptr(), self.nb, out.data_ptr(), stream, 1, not defer, 0)
+        _tiled_launch(self.h, self.kind, self.pre, partials, self.nb, out, stream, not defer)
         sh = self.T.shift
         if defer:
             return DeferredGram(self.h, 2, partials, self.nb, self.d, out, sh)
@@ -781,11 +833,8 @@ def _gram_tiled(h, T: "TiledBF16", y, w, sel, x_zero_dead, blocks, defer=False):
     P = int(h.gram_partial_stride(2, d))
     partials = torch.empty(nb * P, dtype=torch.float64, device=T.device)
     # (the tiles hold x - s already: the kernel takes no shift, the statistics are un-shifted after the fold)
-    pre = _tiled_pre(T, y, w, sel, xmode)
-    if T.packed is not None:
-        h.gram_tall_packed(*pre, partials.data_ptr(), nb, out.data_ptr(), _stream(), not defer)
-    else:
-        h.gram_tall(*pre, partials.data_ptr(), nb, out.data_ptr(), _stream(), 1, not defer, 0)
+    kind, pre = _tiled_pre(T, y, w, sel, xmode)
+    _tiled_launch(h, kind, pre, partials, nb, out, _stream(), not defer)
     if defer:
         return DeferredGram(h, 2, partials, nb, d, out, T.shift)
     return _unshift(h, out, T.shift, d)

@@ -20,7 +20,8 @@ from __future__ import annotations
 
 import torch
 
-__all__ = ["TiledBF16", "tiled_offsets", "PackedTiles", "pack_reference", "unpack_reference"]
+__all__ = ["TiledBF16", "tiled_offsets", "PackedTiles", "pack_reference", "unpack_reference",
+           "PatchedTiles", "patch_reference", "unpatch_reference", "patched_entries"]
 
 
 def tiled_offsets(feats: torch.Tensor, rows: torch.Tensor, d: int) -> torch.Tensor:
@@ -69,6 +70,8 @@ class PackedTiles:
     Memory: +75 % of the tiled buffer plus one byte per entry (n/64 bytes per tile column) --
     +4.8 GB beside the 6.4 GB of a 1e8 x 32 table.  ``npacked``: entries that packed."""
 
+    kind = "mixed"
+
     def __init__(self, dir: torch.Tensor, a: torch.Tensor, npacked: int):
         assert dir.dtype == torch.uint8 and a.dtype == torch.int32 and a.numel() == dir.numel() * SLOT_DWORDS
         self.dir, self.a, self.npacked = dir, a, int(npacked)
@@ -94,13 +97,7 @@ def pack_reference(buf: torch.Tensor) -> PackedTiles:
     e = (v >> 7) & 0xFF
     emin, emax = e.amin(dim=(1, 2, 3)), e.amax(dim=(1, 2, 3))
     ok = ((emax - emin) <= 15) & (emin <= 254)
-    base = torch.where(ok, emin, torch.zeros_like(emin)).view(-1, 1, 1, 1)
-    p = (v & 0x7FFF) - (base << 7)  # 11-bit codes (sign apart) wherever the entry packs
-    sg = v & 0x8000
-    p3, s3 = p[..., 6:8], sg[..., 6:8]
-    nib = torch.stack([p3 & 0xF, (p3 >> 4) & 0xF, ((p3 >> 8) & 0x7) | (s3 >> 12)], dim=-2)  # [e, i, lane, k, half]
-    hw = (sg[..., :6] | p[..., :6]).reshape(-1, 4, 64, 3, 2) | (nib << 11)
-    hw = hw.permute(0, 3, 2, 1, 4)  # -> [entry, piece k, lane, k-step i, half]
+    hw = _encode_slots(v, torch.where(ok, emin, torch.zeros_like(emin)))
     hw = torch.where(ok.view(-1, 1, 1, 1, 1), hw, torch.zeros_like(hw))
     a = _to_i16(hw).contiguous().view(-1).view(torch.int32)
     d8 = torch.where(ok, emin, torch.full_like(emin, RAW_ENTRY)).to(torch.uint8)
@@ -110,25 +107,150 @@ def pack_reference(buf: torch.Tensor) -> PackedTiles:
 def unpack_reference(packed: PackedTiles, buf: torch.Tensor) -> torch.Tensor:
     """The tiled buffer that a reader of ``packed`` sees: packed entries decoded from their slots,
     raw entries taken from ``buf``.  Equals ``buf`` bit for bit."""
-    ne = packed.dir.numel()
-    hw = (packed.a.view(torch.int16).to(torch.int32) & 0xFFFF).view(ne, 3, 64, 4, 2).permute(0, 3, 2, 1, 4)
-    base = packed.dir.to(torch.int32).view(-1, 1, 1, 1, 1) << 7  # [entry, i, lane, k, half]
-    main = (hw & 0x87FF) + base
-    nib = (hw >> 11) & 0xF
-    p3 = nib[..., 0, :] | (nib[..., 1, :] << 4) | ((nib[..., 2, :] & 0x7) << 8)
-    r3 = (p3 | ((nib[..., 2, :] & 0x8) << 12)) + base[..., 0, :]
-    dec = torch.cat([main.reshape(ne, 4, 64, 6), r3], dim=-1)
+    dec = _decode_slots(packed.a, packed.dir)
     raw = _halfwords(buf)
     out = torch.where((packed.dir != RAW_ENTRY).view(-1, 1, 1, 1), dec, raw)
     return _to_i16(out).view(-1).view(torch.bfloat16)
 
 
+PATCH_INLINE = 3  # exception records that fit the 16-byte directory record itself
+# A table takes the patched form only if no entry has more than PATCH_CAP exceptions and the
+# exceptions are at most one value in PATCH_SHARE.  N(0, 1) data has 0.113 per 2048-value entry
+# (one value in 18000) and 1e8 x 32 of it would meet a 6-exception entry once in ~250 tables, so
+# it passes ninefold in the share and with ten more records in the cap; an entry with a zero in
+# every 64th value (32 exceptions) or a table with one zero per 2000 values fails, and takes
+# today's mixed companion or none.  The cap also bounds the reader's overflow loop and fits the
+# record's 8-bit count.
+PATCH_CAP = 16
+PATCH_SHARE = 2048
+
+
+class PatchedTiles:
+    """The all-packed companion of a ``TiledBF16`` buffer with ``d`` a multiple of 32
+    (csrc/hip/gram.h ``patch_tiles``): every entry of the FULL supersteps has a 12-bit slot, so
+    the tall Gram pass reads 3 KiB per entry, always, in a loop without a conditional load.  The
+    zero-padded ragged superstep is not covered (the pass reads it from the raw tiles).
+
+    Entry base: ``emin`` where ``emax - emin <= 15`` (slot bits as in :class:`PackedTiles`), else
+    ``emax - 15``.  A value whose exponent field is below the base is an *exception*: its slot
+    code is the filler 0 (decoding to ``base << 7``) and its 16 stored bits travel in a record
+    ``lane << 21 | dword << 17 | halfword << 16 | bits`` -- ``record >> 16`` is the value's index
+    in the entry taken lane-major (``lane * 32 + k-step * 8 + element``), and an entry's records
+    are sorted by it.  ``dir`` (int32 ``[entries, 4]``) holds per entry ``base | count << 8`` and
+    then, for ``count <= PATCH_INLINE``, the records themselves (unused words 0); for more, word 1
+    is the index of the entry's first record in ``ovf`` (int32), where all of them sit in order.
+
+    Memory: +75 % of the tiled buffer plus 16 bytes per entry (+0.4 % of it) and the overflow
+    table (a few hundred bytes for Gaussian data).  ``nexc``: exceptions in all."""
+
+    kind = "patched"
+
+    def __init__(self, dir: torch.Tensor, a: torch.Tensor, ovf: torch.Tensor, nexc: int):
+        assert dir.dtype == torch.int32 and a.dtype == torch.int32 and ovf.dtype == torch.int32
+        assert dir.dim() == 2 and dir.shape[1] == 4 and a.numel() == dir.shape[0] * SLOT_DWORDS
+        self.dir, self.a, self.ovf, self.nexc = dir, a, ovf, int(nexc)
+
+    @property
+    def npacked(self) -> int:
+        return self.dir.shape[0]
+
+    @property
+    def fraction(self) -> float:
+        return 1.0
+
+    @property
+    def counts(self) -> torch.Tensor:
+        return (self.dir[:, 0] >> 8) & 0xFF
+
+
+def _encode_slots(v: torch.Tensor, base: torch.Tensor) -> torch.Tensor:
+    """Halfwords ``[entries, 4, 64, 8]`` inside their entry's window -> slot halfwords
+    ``[entry, piece, lane, k-step, half]`` (the arithmetic of :func:`pack_reference`)."""
+    p = (v & 0x7FFF) - (base.view(-1, 1, 1, 1) << 7)
+    sg = v & 0x8000
+    p3, s3 = p[..., 6:8], sg[..., 6:8]
+    nib = torch.stack([p3 & 0xF, (p3 >> 4) & 0xF, ((p3 >> 8) & 0x7) | (s3 >> 12)], dim=-2)
+    hw = (sg[..., :6] | p[..., :6]).reshape(-1, 4, 64, 3, 2) | (nib << 11)
+    return hw.permute(0, 3, 2, 1, 4)
+
+
+def _decode_slots(a: torch.Tensor, base: torch.Tensor) -> torch.Tensor:
+    """Slots + bases -> halfwords ``[entries, 4, 64, 8]`` (the arithmetic of :func:`unpack_reference`)."""
+    ne = base.numel()
+    hw = (a.view(torch.int16).to(torch.int32) & 0xFFFF).view(ne, 3, 64, 4, 2).permute(0, 3, 2, 1, 4)
+    b7 = base.to(torch.int32).view(-1, 1, 1, 1, 1) << 7
+    main = (hw & 0x87FF) + b7
+    nib = (hw >> 11) & 0xF
+    p3 = nib[..., 0, :] | (nib[..., 1, :] << 4) | ((nib[..., 2, :] & 0x7) << 8)
+    r3 = (p3 | ((nib[..., 2, :] & 0x8) << 12)) + b7[..., 0, :]
+    return torch.cat([main.reshape(ne, 4, 64, 6), r3], dim=-1)
+
+
+def patched_entries(d: int, n: int) -> int:
+    """Entries the patched companion covers: the full supersteps of a ``d % 32 == 0`` table."""
+    return (n // 64) * (d // 32) if d % 32 == 0 and d > 0 else 0
+
+
+def patch_reference(buf: torch.Tensor, d: int, n: int, cap: int = PATCH_CAP, share: int = PATCH_SHARE):
+    """The :class:`PatchedTiles` of a tiled bf16 buffer in plain torch (CPU or GPU), or None where
+    the table does not take the patched form (``d`` not a multiple of 32, no full superstep, an
+    entry with more than ``cap`` exceptions, or more than one exception per ``share`` values):
+    the specification of the layout and the oracle of the device packer."""
+    ne = patched_entries(d, n)
+    if ne == 0:
+        return None
+    v = _halfwords(buf[: ne * 2048])
+    e = (v >> 7) & 0xFF
+    emin, emax = e.amin(dim=(1, 2, 3)), e.amax(dim=(1, 2, 3))
+    base = torch.where(emax - emin <= 15, emin, emax - 15)
+    exc = (e < base.view(-1, 1, 1, 1)).permute(0, 2, 1, 3).reshape(ne, 2048)  # lane-major
+    cnt = exc.sum(dim=1)
+    nexc = int(cnt.sum())
+    if int(cnt.max()) > cap or nexc * share > ne * 2048:
+        return None
+    slots = _encode_slots(torch.where(e < base.view(-1, 1, 1, 1), base.view(-1, 1, 1, 1) << 7, v), base)
+    a = _to_i16(slots).contiguous().view(-1).view(torch.int32)
+    # records in (entry, lane-major index) order: nonzero() is row-major
+    ent, pos = exc.nonzero(as_tuple=True)
+    bits = v.permute(0, 2, 1, 3).reshape(ne, 2048)[ent, pos]
+    rec = ((pos << 16) | bits).to(torch.int32)
+    start = torch.cumsum(cnt, 0) - cnt
+    rank = torch.arange(ent.numel(), device=buf.device) - start[ent]
+    big = cnt > PATCH_INLINE
+    ovcnt = torch.where(big, cnt, torch.zeros_like(cnt))
+    ovoff = torch.cumsum(ovcnt, 0) - ovcnt
+    dirw = torch.zeros(ne, 4, dtype=torch.int32, device=buf.device)
+    dirw[:, 0] = (base | (cnt << 8)).to(torch.int32)
+    dirw[:, 1] = torch.where(big, ovoff, torch.zeros_like(ovoff)).to(torch.int32)
+    inl = ~big[ent]
+    dirw[ent[inl], 1 + rank[inl]] = rec[inl]
+    ovf = torch.zeros(int(ovcnt.sum()), dtype=torch.int32, device=buf.device)
+    ovf[ovoff[ent[~inl]] + rank[~inl]] = rec[~inl]
+    return PatchedTiles(dirw, a, ovf, nexc)
+
+
+def unpatch_reference(p: PatchedTiles) -> torch.Tensor:
+    """The tiled buffer of the full supersteps as a reader of ``p`` sees it: slots decoded, then
+    every exception record written over its halfword.  Equals that part of the raw tiles bit for
+    bit."""
+    ne = p.dir.shape[0]
+    hw = _decode_slots(p.a, p.dir[:, 0] & 0xFF).permute(0, 2, 1, 3).reshape(ne, 2048).clone()  # lane-major
+    cnt = p.counts.tolist()
+    for e in (i for i, c in enumerate(cnt) if c):
+        w = p.dir[e].tolist()
+        recs = w[1 : 1 + cnt[e]] if cnt[e] <= PATCH_INLINE else p.ovf[w[1] : w[1] + cnt[e]].tolist()
+        for r in recs:
+            hw[e, r >> 16] = r & 0xFFFF
+    return _to_i16(hw.view(ne, 64, 4, 8).permute(0, 2, 1, 3).contiguous()).view(-1).view(torch.bfloat16)
+
+
 class TiledBF16:
-    def __init__(self, buf: torch.Tensor, d: int, n: int, shift=None, packed: "PackedTiles" = None):
+    def __init__(self, buf: torch.Tensor, d: int, n: int, shift=None, packed=None):
         assert buf.dtype == torch.bfloat16 and buf.dim() == 1
         self.buf, self.d, self.n = buf, int(d), int(n)
         self.shift = shift
-        self.packed = packed  # optional 12-bit companion (only the tall Gram pass reads it)
+        # optional 12-bit companion, a PackedTiles (mixed) or a PatchedTiles (only the tall Gram pass reads it)
+        self.packed = packed
 
     @property
     def shape(self):
