@@ -26,7 +26,7 @@ struct GramArgs {
   const uint8_t* sel;  // selection [n] (bool) or null
   double* partials;    // [blocks][P]
   int P;
-  int64_t spw;         // supersteps (64 rows) per wave
+  int64_t spw;         // supersteps (64 rows) per wave, one contiguous range (the tall bf16 kernel has its own map)
   int64_t nsuper;      // n / 64
   int tiled;           // X is MFMA-fragment-ordered bf16 (tile_bf16 layout)
   // columnar skinny f64 mode (cols = d <= 8, X unused): feature f is the source column colp[f]
@@ -37,11 +37,9 @@ struct GramArgs {
   // stream kernels over source columns (gram_stream_cols): [2 * d] int64 device table of
   // (column pointer, dtype) pairs — feature f is column srcs[2 f] (all of X's dtype xdt)
   const int64_t* srcs;
-  // bf16 + stream kernels: 1 = wave w takes supersteps (stages) w, w + W, w + 2W, ... (W = total waves) instead of
-  // one contiguous range (both orders are fixed, so run-to-run deterministic).  gram_tall sets 1 for the tall
-  // bf16 / f64 kernels: every wave sweeps the whole row range in step with the others, measured ~1 % faster
-  // at 1e8 rows and ~2.5 % at the 1.25e7-row 8-GPU shard (the waves' drain is more even).  The stream
-  // kernels always keep contiguous ranges (their interleaved A/B lost and was removed)
+  // stream kernels only: 1 = wave w takes stages w, w + W, w + 2W, ... (W = total waves) instead of
+  // one contiguous range.  gram_stream always sets 0 (the interleaved order lost its A/B there);
+  // the tall bf16 kernel takes the interleaved order unconditionally and does not read this
   int interleave;
   // stream kernels compiled with a DQ row predicate (ops/streamfuse.py, hipRTC): per-lane DMA
   // sources of the stage's row-scalar area — [64 lanes][(base, bytes per row) x 2 instructions]
@@ -111,7 +109,6 @@ void patch_tiles_fill(const void* tiles, int64_t nent, const uint32_t* ovoff, ui
                       uint32_t* ovf, hipStream_t st);
 
 int64_t gram_partial_stride(int mode, int d);
-int gram_default_blocks(int64_t n);
 // grid that exactly fills the chip for the kernel instantiation (occupancy-sized, persistent-style)
 int gram_plan_blocks(int mode, int d, int64_t n, int xdt, int xmode);
 // xmode: 0 = X already zero on dead rows (or no sel/w), 1 = binary mask from sel, 2 = general weights

@@ -33,19 +33,23 @@ namespace {
 
 constexpr int kBlock = 256;  // f64 kernel: 4 waves
 constexpr int kWavesPerBlock = kBlock / kWave;
-// bf16 kernel: 8 waves per block -- two co-resident per CU at <= 128 VGPRs for d <= 32 (HALF
-// below), one per CU at <= 256 VGPRs for d <= 64; the round-4 16-wave block filled a CU alone
-// HALF (d <= 32 unmasked; since round 5 -- the 16-wave block lost): 8-wave blocks, two resident per CU, so one block's ramp and reduction overlap the other's
-// stream and the next pass's blocks start beside this pass's last ones.  Same box, two reps
-// (profiles/r5_shard_drain.md): 1.25e7-row shard 0.1297 / 0.1292 vs 0.1347 / 0.1365 ms per fit,
-// 1e8 headline 0.987 / 0.989 vs 0.994 / 0.992 ms.
-template <int NT, int XMODE, bool HALF = false>
+// bf16 kernel: 8 waves per block -- one per CU at <= 256 VGPRs for d <= 64, and for d <= 32
+// unmasked (NT 1, XMODE 0) two co-resident per CU at <= 128 VGPRs (since round 5 -- the 16-wave
+// block lost), so one block's ramp and reduction overlap the other's stream and the next pass's
+// blocks start beside this pass's last ones.  Same box, two reps (profiles/r5_shard_drain.md):
+// 1.25e7-row shard 0.1297 / 0.1292 vs 0.1347 / 0.1365 ms per fit, 1e8 headline 0.987 / 0.989 vs
+// 0.994 / 0.992 ms.
+constexpr int kBf16Block = 512;
+template <int NT, int XMODE>
 struct BF16Geom {
-  static constexpr int kBlock = (NT == 1 && XMODE == 0 && !HALF) ? 1024 : 512;
+  static constexpr int kBlock = kBf16Block;
   static constexpr int kWaves = kBlock / kWave;
-  static constexpr int kMinBlocks = HALF ? 2 : 1;
+  static constexpr int kMinBlocks = (NT == 1 && XMODE == 0) ? 2 : 1;
 };
-static int bf16_block(int, int) { return 512; }  // (HALF at d <= 32, the 8-wave block elsewhere)
+
+// The 12-bit companion of the tiled storage that a bf16 kernel reads (gram.h: pack_tiles /
+// patch_tiles; GramArgs::xpack with xdir or with xrec + xovf)
+enum class Companion { kRaw, kMixed, kPatched };
 
 __device__ __forceinline__ double load_as_f64(const void* p, int dt, int64_t i) {
   switch (dt) {
@@ -284,14 +288,15 @@ __device__ __forceinline__ void patch_frags(bf16x8 (&fr)[4], uint32_t rec, int l
 // =============================================================================================
 // bf16 MFMA kernel
 // =============================================================================================
-// PATCHED (tiled storage, XMODE 0, no weights, no selection, f32 label): every full superstep is
-// read from the patched companion, the ragged tail from the raw tiles.
-template <typename TX, int NT, int XMODE, bool TILED, bool HALF = false, bool PACKED = false, bool PATCHED = false>
-__global__ __launch_bounds__((BF16Geom<NT, XMODE, HALF>::kBlock), (BF16Geom<NT, XMODE, HALF>::kMinBlocks)) void
+// COMP kPatched (tiled storage, XMODE 0, no weights, no selection, f32 label): every full
+// superstep is read from the patched companion, the ragged tail from the raw tiles.
+template <typename TX, int NT, int XMODE, bool TILED, Companion COMP = Companion::kRaw>
+__global__ __launch_bounds__((BF16Geom<NT, XMODE>::kBlock), (BF16Geom<NT, XMODE>::kMinBlocks)) void
 gram_tall_bf16_kernel(GramArgs a) {
-  static_assert(!PACKED || TILED, "the packed companion belongs to tiled storage");
-  static_assert(!PATCHED || (TILED && !PACKED && XMODE == 0), "the patched companion: tiled storage, XMODE 0");
-  typedef BF16Geom<NT, XMODE, HALF> Geo;
+  constexpr bool PACKED = COMP == Companion::kMixed, PATCHED = COMP == Companion::kPatched;
+  static_assert(COMP == Companion::kRaw || TILED, "a packed companion belongs to tiled storage");
+  static_assert(!PATCHED || XMODE == 0, "the patched companion: XMODE 0");
+  typedef BF16Geom<NT, XMODE> Geo;
   constexpr int NPAIR = NT * (NT + 1) / 2;
   // LDS: per wave 4 cols x 64 rows bf16 (W fragments) + 64 f32 row weights; reused for the
   // block reduction afterwards.
@@ -325,9 +330,6 @@ gram_tall_bf16_kernel(GramArgs a) {
   const int64_t gw =
       (int64_t)blockIdx.x * Geo::kWaves + ((PACKED || PATCHED) ? __builtin_amdgcn_readfirstlane(wave) : wave);
   const int64_t total_waves = (int64_t)gridDim.x * Geo::kWaves;
-  int64_t s0 = gw * a.spw;
-  int64_t s1 = s0 + a.spw;
-  if (s1 > a.nsuper) s1 = a.nsuper;
   const bool do_tail = (gw == total_waves - 1) && (a.n > a.nsuper * 64);
 
   // One superstep of compute on already-loaded feature fragments (rv: the row scalars of row
@@ -459,9 +461,9 @@ gram_tall_bf16_kernel(GramArgs a) {
     // them would make every wait drain them): after a wave's last superstep the "next" is a
     // placeholder, three 16-byte loads from slot 0 (the same word for every lane) and the wave's
     // own label again, which nobody reads.
-    const int64_t step = a.interleave ? total_waves : 1;
-    const int64_t end = a.interleave ? a.nsuper : s1;
-    int64_t s = a.interleave ? gw : s0;
+    const int64_t step = total_waves;
+    const int64_t end = a.nsuper;
+    int64_t s = gw;
     auto pk_next = [&](int64_t s, const uint32_t (&dv)[NT], int (&db)[NT], u32x4 (&raw)[NT][4], LabelBits& yb) {
       const bool more = s + step < end;
       dir_bytes(s + step, dv, db);
@@ -513,9 +515,9 @@ gram_tall_bf16_kernel(GramArgs a) {
     // ahead (the scalar counter is not the tile loads'); its exceptions are patched into the
     // decoded fragments under a uniform branch on the count, so the MFMA operands are the raw
     // tile's bits.
-    const int64_t step = a.interleave ? total_waves : 1;
-    const int64_t end = a.interleave ? a.nsuper : s1;
-    int64_t s = a.interleave ? gw : s0;
+    const int64_t step = total_waves;
+    const int64_t end = a.nsuper;
+    int64_t s = gw;
     const u32x4* recs = reinterpret_cast<const u32x4*>(a.xrec);
     const uint32_t* yp = reinterpret_cast<const uint32_t*>(a.y);
     auto pt_dir = [&](int64_t s, u32x4 (&dr)[NT]) {
@@ -594,25 +596,16 @@ gram_tall_bf16_kernel(GramArgs a) {
       if (left) pt_compute(dA, A, yA);
     }
   } else
-  // full supersteps: register double buffer (loads of s+1 in flight while s computes)
-  if (a.interleave) {
-    if (gw < a.nsuper) {
-      bf16x8 cur[NT][4], nxt[NT][4];
-      load(gw * 64, 64, cur);
-      for (int64_t s = gw; s < a.nsuper; s += total_waves) {
-        if (s + total_waves < a.nsuper) load((s + total_waves) * 64, 64, nxt);
-        compute(s * 64, cur);
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-          for (int i = 0; i < 4; ++i) cur[t][i] = nxt[t][i];
-      }
-    }
-  } else if (s0 < s1) {
+  // full supersteps: register double buffer (loads of the wave's next superstep in flight while
+  // this one computes).  Wave gw takes supersteps gw, gw + W, gw + 2W, ... (W = total waves), so
+  // the whole grid sweeps the rows in step; same-box A/B against one contiguous range per wave
+  // (5 alternations): 1e8 rows 1.011-1.015 vs 1.020-1.026 ms, 1.25e7 rows 0.1426-0.1441 vs
+  // 0.1471-0.1476 ms per fit.  The packed and patched loops above keep the same map.
+  if (gw < a.nsuper) {
     bf16x8 cur[NT][4], nxt[NT][4];
-    load(s0 * 64, 64, cur);
-    for (int64_t s = s0; s < s1; ++s) {
-      if (s + 1 < s1) load((s + 1) * 64, 64, nxt);
+    load(gw * 64, 64, cur);
+    for (int64_t s = gw; s < a.nsuper; s += total_waves) {
+      if (s + total_waves < a.nsuper) load((s + total_waves) * 64, 64, nxt);
       compute(s * 64, cur);
 #pragma unroll
       for (int t = 0; t < NT; ++t)
@@ -1674,15 +1667,6 @@ int64_t gram_partial_stride(int mode, int d) {
   return 5 + 2 * (int64_t)d + (int64_t)NT * (NT + 1) / 2 * 1024;
 }
 
-int gram_default_blocks(int64_t n) {
-  const int64_t nsuper = (n + 63) / 64;
-  // aim: >= 16 waves per CU on 256 CUs, but >= 8 supersteps per wave
-  int64_t blocks = (nsuper + 8 * kWavesPerBlock - 1) / (8 * kWavesPerBlock);
-  if (blocks > 1024) blocks = 1024;
-  if (blocks < 1) blocks = 1;
-  return (int)blocks;
-}
-
 template <typename K>
 static int occupancy_blocks(K kern, size_t lds, int block) {
   int per = 0, dev = 0, cus = 0;
@@ -1693,8 +1677,8 @@ static int occupancy_blocks(K kern, size_t lds, int block) {
   return per * cus;
 }
 
-static size_t bf16_lds(int d, int xmode) {
-  const int W = bf16_block(d, xmode) / kWave;
+static size_t bf16_lds(int d) {
+  const int W = kBf16Block / kWave;
   const int NT = (d + 31) / 32;
   const size_t stripes = (size_t)W * (4 * 64 * 2 + 64 * 4);
   const size_t tree = (size_t)(W / 2) * ((NT * (NT + 1) / 2 + NT) * 16) * 64 * sizeof(float) + (size_t)W * 5 * 8;
@@ -1707,23 +1691,27 @@ static size_t f64_lds(int d) {
   return red > lds ? red : lds;
 }
 
-// Dispatch table: call F with the kernel instantiation for (mode, xdt, d, xmode).
+// Dispatch table: call F with the kernel instantiation for (mode, xdt, d, xmode, storage, companion).
 template <typename F>
-static void with_kernel(int mode, int xdt, int d, int xmode, bool tiled, bool packed, F&& f) {
+static void with_kernel(int mode, int xdt, int d, int xmode, bool tiled, Companion comp, F&& f) {
   if (mode == GRAM_BF16) {
     const int NT = (d + 31) / 32;
-#define DQ_BF16_CASE(TX, NTV, TL, PK)                                                    \
-    if (xmode == 0 && NTV == 1) return f(gram_tall_bf16_kernel<TX, 1, 0, TL, true, PK>); \
-    if (xmode == 0) return f(gram_tall_bf16_kernel<TX, NTV, 0, TL, false, PK>);          \
-    if (xmode == 1) return f(gram_tall_bf16_kernel<TX, NTV, 1, TL, false, PK>);          \
-    return f(gram_tall_bf16_kernel<TX, NTV, 2, TL, false, PK>);
-    if (packed && !(xdt == DT_BF16 && tiled)) throw std::invalid_argument("gram_tall: packed tiles need tiled bf16 storage");
-    if (packed) { if (NT == 1) { DQ_BF16_CASE(uint16_t, 1, true, true) } else { DQ_BF16_CASE(uint16_t, 2, true, true) } }
-    if (xdt == DT_BF16 && tiled) { if (NT == 1) { DQ_BF16_CASE(uint16_t, 1, true, false) } else { DQ_BF16_CASE(uint16_t, 2, true, false) } }
+    constexpr Companion kRaw = Companion::kRaw, kMixed = Companion::kMixed, kPatched = Companion::kPatched;
+#define DQ_BF16_CASE(TX, NTV, TL, CO)                                    \
+    if (xmode == 0) return f(gram_tall_bf16_kernel<TX, NTV, 0, TL, CO>); \
+    if (xmode == 1) return f(gram_tall_bf16_kernel<TX, NTV, 1, TL, CO>); \
+    return f(gram_tall_bf16_kernel<TX, NTV, 2, TL, CO>);
+    if (comp != kRaw && !(xdt == DT_BF16 && tiled)) throw std::invalid_argument("gram_tall: packed tiles need tiled bf16 storage");
+    if (comp == kPatched) {  // (XMODE 0 only: check_companion)
+      if (NT == 1) return f(gram_tall_bf16_kernel<uint16_t, 1, 0, true, kPatched>);
+      return f(gram_tall_bf16_kernel<uint16_t, 2, 0, true, kPatched>);
+    }
+    if (comp == kMixed) { if (NT == 1) { DQ_BF16_CASE(uint16_t, 1, true, kMixed) } else { DQ_BF16_CASE(uint16_t, 2, true, kMixed) } }
+    if (xdt == DT_BF16 && tiled) { if (NT == 1) { DQ_BF16_CASE(uint16_t, 1, true, kRaw) } else { DQ_BF16_CASE(uint16_t, 2, true, kRaw) } }
     if (tiled) throw std::invalid_argument("gram_tall: tiled storage must be bf16");
-    if (xdt == DT_BF16) { if (NT == 1) { DQ_BF16_CASE(uint16_t, 1, false, false) } else { DQ_BF16_CASE(uint16_t, 2, false, false) } }
-    if (xdt == DT_F32) { if (NT == 1) { DQ_BF16_CASE(float, 1, false, false) } else { DQ_BF16_CASE(float, 2, false, false) } }
-    if (xdt == DT_F64) { if (NT == 1) { DQ_BF16_CASE(double, 1, false, false) } else { DQ_BF16_CASE(double, 2, false, false) } }
+    if (xdt == DT_BF16) { if (NT == 1) { DQ_BF16_CASE(uint16_t, 1, false, kRaw) } else { DQ_BF16_CASE(uint16_t, 2, false, kRaw) } }
+    if (xdt == DT_F32) { if (NT == 1) { DQ_BF16_CASE(float, 1, false, kRaw) } else { DQ_BF16_CASE(float, 2, false, kRaw) } }
+    if (xdt == DT_F64) { if (NT == 1) { DQ_BF16_CASE(double, 1, false, kRaw) } else { DQ_BF16_CASE(double, 2, false, kRaw) } }
 #undef DQ_BF16_CASE
     throw std::invalid_argument("gram_tall(bf16): unsupported feature dtype");
   }
@@ -1808,10 +1796,10 @@ int gram_plan_blocks(int mode, int d, int64_t n, int xdt, int xmode) {
     if (want < 1) want = 1;
     return (int)(want < full ? want : full);
   }
-  const size_t lds = mode == GRAM_BF16 ? bf16_lds(d, xmode) : f64_lds(d);
+  const size_t lds = mode == GRAM_BF16 ? bf16_lds(d) : f64_lds(d);
   int full = 1;
-  const int block = mode == GRAM_BF16 ? bf16_block(d, xmode) : kBlock;
-  with_kernel(mode, xdt, d, xmode, false, false, [&](auto kern) { full = occupancy_blocks(kern, lds, block); });
+  const int block = mode == GRAM_BF16 ? kBf16Block : kBlock;
+  with_kernel(mode, xdt, d, xmode, false, Companion::kRaw, [&](auto kern) { full = occupancy_blocks(kern, lds, block); });
   // at least ~4 supersteps per wave, at most one full residency wave of blocks
   const int64_t nsuper = (n + 63) / 64;
   const int wpb = block / kWave;
@@ -1835,31 +1823,43 @@ void gram_reduce(int mode, const double* partials, int blocks, int d, double* ou
   DQ_HIP_CHECK(hipGetLastError());
 }
 
+// The companion that the pointers of ``a`` name, after checking that the launch can read it.
+static Companion check_companion(int mode, const GramArgs& a, int xmode) {
+  auto bad = [](const char* what) { throw std::invalid_argument(std::string("gram_tall: ") + what); };
+  if (!a.xpack && !a.xdir && !a.xrec) return Companion::kRaw;
+  if (!a.xpack) bad("a companion directory without its slot buffer");
+  if (!a.xdir && !a.xrec) bad("companion slots without a directory");
+  if (a.xdir && a.xrec) bad("companion slots with two directories (mixed and patched)");
+  if (!(a.tiled && mode == GRAM_BF16)) bad("packed tiles belong to tiled bf16 storage");
+  if (!aligned16(a.xpack)) bad("packed tiles need 16-byte aligned slots");
+  if (a.xrec) {
+    if (xmode != 0 || a.w || a.sel) bad("patched tiles take unweighted, unselected rows (xmode 0)");
+    if (a.ydt != DT_F32) bad("patched tiles need an f32 label");
+    if (a.xdt != DT_BF16) bad("patched tiles belong to bf16 storage");
+    if (a.d % 32 != 0) bad("patched tiles need d a multiple of 32");
+    if (a.nsuper < 1) bad("patched tiles need at least one full superstep");
+    if (!a.xovf) bad("patched tiles need an overflow table (any valid pointer when it is empty)");
+    if (!aligned16(a.xrec)) bad("patched tiles need 16-byte aligned directory records");
+    return Companion::kPatched;
+  }
+  if (a.w && xmode != 2) bad("packed tiles with weights need xmode 2");
+  if (a.ydt != DT_F32 && a.ydt != DT_F64) bad("packed tiles need an f32 / f64 label");
+  if (reinterpret_cast<uintptr_t>(a.xdir) & 3) bad("packed tiles need a word-aligned directory");
+  return Companion::kMixed;
+}
+
 void gram_tall(int mode, GramArgs a, int xmode, int blocks, double* out, hipStream_t st, bool reduce) {
   if (a.d < 1 || a.d > 64) throw std::invalid_argument("gram_tall: d must be in [1, 64]");
   if (blocks < 1) throw std::invalid_argument("gram_tall: blocks must be >= 1");
   a.nsuper = a.n / 64;
-  const int block = mode == GRAM_BF16 ? bf16_block(a.d, xmode) : kBlock;
+  const int block = mode == GRAM_BF16 ? kBf16Block : kBlock;
   const int64_t total_waves = (int64_t)blocks * (block / kWave);
   a.spw = (a.nsuper + total_waves - 1) / total_waves;
   if (a.spw < 1) a.spw = 1;
-  // interleaved supersteps: same-box A/B against contiguous ranges (5 alternations) 1e8 rows
-  // 1.011-1.015 vs 1.020-1.026 ms, 1.25e7 rows 0.1426-0.1441 vs 0.1471-0.1476 ms per fit (tall
-  // bf16 kernel); the stream kernels set their own (contiguous ranges)
-  a.interleave = 1;
   a.P = (int)gram_partial_stride(mode, a.d);
-  const size_t lds = mode == GRAM_BF16 ? bf16_lds(a.d, xmode) : f64_lds(a.d);
+  const size_t lds = mode == GRAM_BF16 ? bf16_lds(a.d) : f64_lds(a.d);
   if (a.tiled && mode != GRAM_BF16) throw std::invalid_argument("gram_tall: tiled storage needs bf16 mode");
-  if ((a.xpack != nullptr) != ((a.xdir != nullptr) != (a.xrec != nullptr)) || (a.xpack && !(a.tiled && mode == GRAM_BF16)))
-    throw std::invalid_argument("gram_tall: packed tiles come as a slot buffer plus one directory, with tiled bf16 storage");
-  if (a.xrec && (xmode != 0 || a.w || a.sel || a.ydt != DT_F32 || a.xdt != DT_BF16 || (a.d & 31) || a.nsuper < 1 ||
-                 !a.xovf || (reinterpret_cast<uintptr_t>(a.xrec) & 15) || (reinterpret_cast<uintptr_t>(a.xpack) & 15)))
-    throw std::invalid_argument("gram_tall: patched tiles need d a multiple of 32, a full superstep, an f32 label, no "
-                                "weights or selection, and 16-byte aligned slots and directory records");
-  if (a.xpack && a.w && xmode != 2) throw std::invalid_argument("gram_tall: packed tiles with weights need xmode 2");
-  if (a.xpack && ((a.ydt != DT_F32 && a.ydt != DT_F64) || (reinterpret_cast<uintptr_t>(a.xdir) & 3) ||
-                  (reinterpret_cast<uintptr_t>(a.xpack) & 15)))
-    throw std::invalid_argument("gram_tall: packed tiles need f32 / f64 labels, a word-aligned directory and 16-byte aligned slots");
+  const Companion comp = check_companion(mode, a, xmode);
   if (a.xshift) {
     // only the f32 stream kernels subtract a shift (tiled storage is shifted when it is tiled)
     if (!((mode == GRAM_F32 || mode == GRAM_BF16 || mode == GRAM_F32S) && a.xdt == DT_F32 && !a.tiled && a.cols == 0 &&
@@ -1880,13 +1880,8 @@ void gram_tall(int mode, GramArgs a, int xmode, int blocks, double* out, hipStre
     return;
   } else if (mode == GRAM_F32 || mode == GRAM_F32S) {
     throw std::invalid_argument("gram_tall(f32): needs 16-byte aligned f32 features and f32/f64 labels");
-  } else if (a.xrec) {
-    if (a.d <= 32)
-      hipLaunchKernelGGL((gram_tall_bf16_kernel<uint16_t, 1, 0, true, true, false, true>), dim3(blocks), dim3(block), lds, st, a);
-    else
-      hipLaunchKernelGGL((gram_tall_bf16_kernel<uint16_t, 2, 0, true, false, false, true>), dim3(blocks), dim3(block), lds, st, a);
   } else {
-    with_kernel(mode, a.xdt, a.d, xmode, a.tiled != 0, a.xpack != nullptr,
+    with_kernel(mode, a.xdt, a.d, xmode, a.tiled != 0, comp,
                 [&](auto kern) { hipLaunchKernelGGL(kern, dim3(blocks), dim3(block), lds, st, a); });
   }
   DQ_HIP_CHECK(hipGetLastError());

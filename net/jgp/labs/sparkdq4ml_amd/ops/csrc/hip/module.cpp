@@ -31,6 +31,17 @@ static T* P(uintptr_t p) {
   return reinterpret_cast<T*>(p);
 }
 
+// The row operands of a Gram pass (label, optional weights and selection; 0 = none) and its
+// per-block partial slabs
+static void set_rows(GramArgs& a, uintptr_t y, int ydt, uintptr_t w, int wdt, uintptr_t sel, uintptr_t partials) {
+  a.y = P<const void>(y);
+  a.ydt = ydt;
+  a.w = P<const void>(w);
+  a.wdt = wdt;
+  a.sel = P<const uint8_t>(sel);
+  a.partials = P<double>(partials);
+}
+
 // Reusable event rings for stream ordering on the asynchronous fit's issue path: torch's
 // wait_stream / Event create a Python Event object (and a HIP event) per call.  One ring per
 // (device, key): key 0 serves stream_wait (the wait is enqueued right after the record and keeps
@@ -98,71 +109,33 @@ PYBIND11_MODULE(_dq4ml_hip, m) {
 
   // ---- Gram (K5) ---------------------------------------------------------------------------
   m.def("gram_partial_stride", &gram_partial_stride);
-  m.def("gram_default_blocks", &gram_default_blocks);
   m.def("gram_plan_blocks", &gram_plan_blocks);
+  // Arguments: what is fixed for a table (storage, its 12-bit companion: xpack with xdir = mixed,
+  // gram.h pack_tiles; xpack with xrec + xovf = patched, patch_tiles; 0 = none), the row operands,
+  // then the per-launch values
   m.def("gram_tall",
-        [](int mode, uintptr_t X, int64_t ld, int d, int64_t n, int xdt, uintptr_t y, int ydt, uintptr_t w, int wdt,
-           uintptr_t sel, int xmode, uintptr_t partials, int blocks, uintptr_t out, uintptr_t stream, int tiled,
-           bool reduce, uintptr_t xshift) {
+        [](int mode, uintptr_t X, int64_t ld, int d, int64_t n, int xdt, int tiled, uintptr_t xshift, uintptr_t xpack,
+           uintptr_t xdir, uintptr_t xrec, uintptr_t xovf, uintptr_t y, int ydt, uintptr_t w, int wdt, uintptr_t sel,
+           int xmode, uintptr_t partials, int blocks, uintptr_t out, uintptr_t stream, bool reduce) {
           GramArgs a{};
-          a.tiled = tiled;
-          a.xshift = P<const float>(xshift);
           a.X = P<const void>(X);
           a.ld = ld;
           a.d = d;
           a.n = n;
           a.xdt = xdt;
-          a.y = P<const void>(y);
-          a.ydt = ydt;
-          a.w = P<const void>(w);
-          a.wdt = wdt;
-          a.sel = P<const uint8_t>(sel);
-          a.partials = P<double>(partials);
-          gram_tall(mode, a, xmode, blocks, P<double>(out), as_stream(stream), reduce);
-        });
-  // tiled bf16 storage with its 12-bit companion (gram.h: pack_tiles); xmode etc. as gram_tall
-  m.def("gram_tall_packed",
-        [](uintptr_t X, uintptr_t xpack, uintptr_t xdir, int d, int64_t n, uintptr_t y, int ydt, uintptr_t w, int wdt,
-           uintptr_t sel, int xmode, uintptr_t partials, int blocks, uintptr_t out, uintptr_t stream, bool reduce) {
-          GramArgs a{};
-          a.tiled = 1;
-          a.X = P<const void>(X);
+          a.tiled = tiled;
+          a.xshift = P<const float>(xshift);
           a.xpack = P<const uint32_t>(xpack);
           a.xdir = P<const uint8_t>(xdir);
-          a.d = d;
-          a.n = n;
-          a.xdt = DT_BF16;
-          a.y = P<const void>(y);
-          a.ydt = ydt;
-          a.w = P<const void>(w);
-          a.wdt = wdt;
-          a.sel = P<const uint8_t>(sel);
-          a.partials = P<double>(partials);
-          gram_tall(GRAM_BF16, a, xmode, blocks, P<double>(out), as_stream(stream), reduce);
+          a.xrec = P<const uint32_t>(xrec);
+          a.xovf = P<const uint32_t>(xovf);
+          set_rows(a, y, ydt, w, wdt, sel, partials);
+          gram_tall(mode, a, xmode, blocks, P<double>(out), as_stream(stream), reduce);
         });
   m.def("pack_tiles", [](uintptr_t tiles, int d, int64_t n, uintptr_t dir, uintptr_t slots, uintptr_t npacked,
                          uintptr_t stream) {
     pack_tiles(P<const void>(tiles), d, n, P<uint8_t>(dir), P<uint32_t>(slots), P<uint32_t>(npacked), as_stream(stream));
   });
-  // tiled bf16 storage with its patched companion (gram.h: patch_tiles): unweighted, unselected
-  // rows and an f32 label
-  m.def("gram_tall_patched",
-        [](uintptr_t X, uintptr_t xpack, uintptr_t xrec, uintptr_t xovf, int d, int64_t n, uintptr_t y, int ydt,
-           uintptr_t partials, int blocks, uintptr_t out, uintptr_t stream, bool reduce) {
-          GramArgs a{};
-          a.tiled = 1;
-          a.X = P<const void>(X);
-          a.xpack = P<const uint32_t>(xpack);
-          a.xrec = P<const uint32_t>(xrec);
-          a.xovf = P<const uint32_t>(xovf);
-          a.d = d;
-          a.n = n;
-          a.xdt = DT_BF16;
-          a.y = P<const void>(y);
-          a.ydt = ydt;
-          a.partials = P<double>(partials);
-          gram_tall(GRAM_BF16, a, 0, blocks, P<double>(out), as_stream(stream), reduce);
-        });
   m.def("patch_tiles_count", [](uintptr_t tiles, int64_t nent, uintptr_t counts, uintptr_t stat, uintptr_t stream) {
     patch_tiles_count(P<const void>(tiles), nent, P<uint32_t>(counts), P<unsigned long long>(stat), as_stream(stream));
   });
@@ -180,12 +153,7 @@ PYBIND11_MODULE(_dq4ml_hip, m) {
           a.d = d;
           a.n = n;
           a.xdt = xdt;
-          a.y = P<const void>(y);
-          a.ydt = ydt;
-          a.w = P<const void>(w);
-          a.wdt = wdt;
-          a.sel = P<const uint8_t>(sel);
-          a.partials = P<double>(partials);
+          set_rows(a, y, ydt, w, wdt, sel, partials);
           gram_stream(mode, a, (w || sel || xshift) ? 1 : 0, blocks, P<double>(out), as_stream(stream), true);
         });
   m.def("gram_stream_blocks", &gram_stream_blocks);
@@ -217,12 +185,7 @@ PYBIND11_MODULE(_dq4ml_hip, m) {
           a.d = d;
           a.n = n;
           a.xdt = DT_F64;
-          a.y = P<const void>(y);
-          a.ydt = ydt;
-          a.w = P<const void>(w);
-          a.wdt = wdt;
-          a.sel = P<const uint8_t>(sel);
-          a.partials = P<double>(partials);
+          set_rows(a, y, ydt, w, wdt, sel, partials);
           gram_tall(GRAM_F64, a, w ? 2 : (sel ? 1 : 0), blocks, P<double>(out), as_stream(stream), true);
         });
   m.def("gram_reduce", [](int mode, uintptr_t partials, int blocks, int d, uintptr_t out, uintptr_t stream) {
@@ -247,10 +210,7 @@ PYBIND11_MODULE(_dq4ml_hip, m) {
     a.d = d;
     a.n = n;
     a.xdt = xdt;
-    a.y = P<const void>(y);
-    a.ydt = ydt;
-    a.sel = P<const uint8_t>(sel);
-    a.partials = P<double>(partials);
+    set_rows(a, y, ydt, 0, 0, sel, partials);
     gram_folds(a, fold_rule(thr, seed), blocks, P<double>(out), as_stream(stream));
   });
   m.def("fold_ids", [fold_rule](int64_t n, int64_t granule, const std::vector<uint32_t>& thr, uint64_t seed,
@@ -358,10 +318,7 @@ PYBIND11_MODULE(_dq4ml_hip, m) {
     a.d = d;
     a.n = n;
     a.xdt = DT_F32;
-    a.y = P<const void>(y);
-    a.ydt = ydt;
-    a.sel = P<const uint8_t>(sel);
-    a.partials = P<double>(partials);
+    set_rows(a, y, ydt, 0, 0, sel, partials);
     gram_cols(a, P<const PackSrcG>(srcs), sdt, blocks, P<double>(out), as_stream(stream));
   });
   m.def("tiled_elems", &tiled_elems);

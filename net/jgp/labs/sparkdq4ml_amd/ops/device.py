@@ -111,6 +111,28 @@ def _check_dev(*ts):
             raise ValueError(f"tensors on different devices: {dev} vs {t.device}")
 
 
+def _wdt(w: Optional[torch.Tensor]) -> int:
+    """dtype code of the optional weights (0 without)."""
+    return 0 if w is None else dtype_code(w)
+
+
+def _xmode(w, sel, x_zero_dead: bool = False) -> int:
+    """Row mode of the Gram kernels: 2 = general weights, 1 = binary mask from ``sel``, 0 = neither
+    (or X already zero on the dead rows)."""
+    if w is not None:
+        return 2
+    return 1 if sel is not None and not x_zero_dead else 0
+
+
+def _rebase16(y, w, sel):
+    """The LDS-DMA stream kernels (gram_stream.hip) read labels / weights as 16-B chunks and the
+    selection as 4-B words: re-base unaligned views (an n-element copy, far below the pass)."""
+    y = y if y.data_ptr() % 16 == 0 else y.clone()
+    w = w if w is None or w.data_ptr() % 16 == 0 else w.clone()
+    sel = sel if sel is None or sel.data_ptr() % 4 == 0 else sel.clone()
+    return y, w, sel
+
+
 def _feature_view(X: torch.Tensor, align_elems: int):
     """(base tensor, ld): a feature-major view whose rows are ``align_elems``-aligned."""
     if X.dim() != 2:
@@ -126,7 +148,7 @@ def _feature_view(X: torch.Tensor, align_elems: int):
 
 # ------------------------------------------------------------------------------------------
 from .layout import (PATCH_CAP, PATCH_INLINE, PATCH_SHARE, SLOT_DWORDS, PackedTiles, PatchedTiles, TiledBF16,  # noqa: E402
-                     TiledWide, patched_entries)
+                     TiledWide, gram_layout_size, patched_entries)
 from .shift import column_shift  # noqa: E402
 
 FP8_MAX = 448.0
@@ -280,7 +302,7 @@ def gram_stats(X, y, w, sel, compute: str = "fp64", x_zero_dead: bool = False, b
     _check_dev(X, y, w, sel)
     d, n = X.shape
     mode = GRAM_MODES[compute]
-    out = torch.empty(5 + 2 * d + d * (d + 1) // 2, dtype=torch.float64, device=X.device)
+    out = torch.empty(gram_layout_size(d), dtype=torch.float64, device=X.device)
     if n == 0:
         out.zero_()
         return out
@@ -317,39 +339,18 @@ def gram_stats(X, y, w, sel, compute: str = "fp64", x_zero_dead: bool = False, b
             X = X.to(torch.float32).contiguous()
     align = 16 // X.element_size()
     Xv, ld = _feature_view(X, align)
-    y = y.contiguous()
-    if y.dtype not in (torch.float64, torch.float32):
-        y = y.to(torch.float64)
-    if w is not None:
-        w = w.contiguous()
-        if w.dtype not in (torch.float64, torch.float32):
-            w = w.to(torch.float64)
-    if sel is not None:
-        sel = sel.contiguous()
-        if sel.dtype != torch.bool:
-            sel = sel.to(torch.bool)
-    if y.numel() != n or (w is not None and w.numel() != n) or (sel is not None and sel.numel() != n):
-        raise ValueError("gram_stats: row-count mismatch")
+    y, w, sel = _prep_rows(y, w, sel, n)
     if mode in (0, 1, 4) or X.dtype == torch.float32:
-        # the LDS-DMA stream kernels (gram_stream.hip) read labels / weights as 16-B chunks and the
-        # selection as 4-B words: re-base unaligned views (an n-element copy, far below the pass)
-        y = y if y.data_ptr() % 16 == 0 else y.clone()
-        w = w if w is None or w.data_ptr() % 16 == 0 else w.clone()
-        sel = sel if sel is None or sel.data_ptr() % 4 == 0 else sel.clone()
-    if w is not None:
-        xmode = 2
-    elif sel is not None and not x_zero_dead:
-        xmode = 1
-    else:
-        xmode = 0
+        y, w, sel = _rebase16(y, w, sel)  # (these go to the stream kernels)
+    xmode = _xmode(w, sel, x_zero_dead)
     if shift is not None:
         xmode = max(xmode, 1)  # dead / padding rows must weigh 0: their stored zeros are -s after the shift
     nb = int(blocks or _plan_blocks(h, mode, d, n, dtype_code(Xv), xmode))
     P = int(h.gram_partial_stride(mode, d))
     partials = torch.empty(nb * P, dtype=torch.float64, device=X.device)
-    h.gram_tall(mode, Xv.data_ptr(), int(ld), int(d), int(n), dtype_code(Xv), y.data_ptr(), dtype_code(y),
-                _ptr(w), dtype_code(w) if w is not None else 0, _ptr(sel), xmode, partials.data_ptr(), nb,
-                out.data_ptr(), _stream(), 0, True, _sptr(shift))
+    h.gram_tall(mode, Xv.data_ptr(), int(ld), int(d), int(n), dtype_code(Xv), 0, _sptr(shift), 0, 0, 0, 0,
+                y.data_ptr(), dtype_code(y), _ptr(w), _wdt(w), _ptr(sel), xmode, partials.data_ptr(), nb,
+                out.data_ptr(), _stream(), True)
     return _unshift(h, out, shift, d)
 
 
@@ -427,7 +428,7 @@ def gram_stats_folds(X, y, sel, k_or_weights, seed: int, granule: int, compute: 
     nb = int(nb)
     P = int(h.gram_partial_stride(0, d))
     partials = torch.empty(k * nb * P, dtype=torch.float64, device=X.device)
-    out = torch.empty(k, 5 + 2 * d + d * (d + 1) // 2, dtype=torch.float64, device=X.device)
+    out = torch.empty(k, gram_layout_size(d), dtype=torch.float64, device=X.device)
     h.gram_folds(Xv.data_ptr(), int(ld), d, n, dtype_code(Xv), y.data_ptr(), dtype_code(y), _ptr(sel),
                  [int(t) for t in thr], int(seed64), partials.data_ptr(), nb, out.data_ptr(), _stream())
     return out
@@ -630,17 +631,15 @@ def gram_skinny_cols(parts: List[torch.Tensor], y, w, sel, blocks: Optional[int]
             raise ValueError("gram_skinny_cols: columns of different lengths")
     dev = rows[0].device
     y, w, sel = _prep_rows(y, w, sel, n)
-    out = torch.empty(5 + 2 * d + d * (d + 1) // 2, dtype=torch.float64, device=dev)
+    out = torch.empty(gram_layout_size(d), dtype=torch.float64, device=dev)
     if n == 0:
         out.zero_()
         return out
-    xmode = 2 if w is not None else (1 if sel is not None else 0)
-    nb = int(blocks or _plan_blocks(h, 0, d, n, 0, xmode))
+    nb = int(blocks or _plan_blocks(h, 0, d, n, 0, _xmode(w, sel)))
     P = int(h.gram_partial_stride(0, d))
     partials = torch.empty(nb * P, dtype=torch.float64, device=dev)
     h.gram_skinny_cols([r.data_ptr() for r in rows], [dtype_code(r) for r in rows], int(n), y.data_ptr(),
-                       dtype_code(y), _ptr(w), dtype_code(w) if w is not None else 0, _ptr(sel),
-                       partials.data_ptr(), nb, out.data_ptr(), _stream())
+                       dtype_code(y), _ptr(w), _wdt(w), _ptr(sel), partials.data_ptr(), nb, out.data_ptr(), _stream())
     return out
 
 
@@ -669,7 +668,7 @@ def gram_cols(parts: List[torch.Tensor], y, sel, blocks: Optional[int] = None):
     nb = int(blocks or _cols_blocks(h, d, n))
     P = int(h.gram_partial_stride(2, d))
     partials = torch.empty(nb * P, dtype=torch.float64, device=dev)
-    out = torch.empty(5 + 2 * d + d * (d + 1) // 2, dtype=torch.float64, device=dev)
+    out = torch.empty(gram_layout_size(d), dtype=torch.float64, device=dev)
     codes = {dtype_code(r) for r in rows}
     sdt = codes.pop() if len(codes) == 1 else -1
     if sdt not in (0, 1, 2) or any(r.data_ptr() % 16 for r in rows):
@@ -706,11 +705,8 @@ def gram_stream_cols(parts, y, w, sel, compute: str):
         return None
     h = native.hip()
     dev = rows[0].device
-    y, w, sel = _prep_rows(y, w, sel, n)
-    y = y if y.data_ptr() % 16 == 0 else y.clone()
-    w = w if w is None or w.data_ptr() % 16 == 0 else w.clone()
-    sel = sel if sel is None or sel.data_ptr() % 4 == 0 else sel.clone()
-    out = torch.empty(5 + 2 * d + d * (d + 1) // 2, dtype=torch.float64, device=dev)
+    y, w, sel = _rebase16(*_prep_rows(y, w, sel, n))
+    out = torch.empty(gram_layout_size(d), dtype=torch.float64, device=dev)
     if n == 0:
         return out.zero_()
     desc = _srcw_desc(h, rows, dev)
@@ -722,9 +718,8 @@ def gram_stream_cols(parts, y, w, sel, compute: str):
     P = int(h.gram_partial_stride(mode, d))
     partials = torch.empty(nb * P, dtype=torch.float64, device=dev)
     shift = column_shift(rows) if mode in (1, 2, 4) else None  # rounded / f32-accumulated modes
-    h.gram_stream_cols(mode, desc.data_ptr(), d, n, xc, y.data_ptr(), dtype_code(y), _ptr(w),
-                       dtype_code(w) if w is not None else 0, _ptr(sel), partials.data_ptr(), nb, out.data_ptr(),
-                       _stream(), _sptr(shift))
+    h.gram_stream_cols(mode, desc.data_ptr(), d, n, xc, y.data_ptr(), dtype_code(y), _ptr(w), _wdt(w), _ptr(sel),
+                       partials.data_ptr(), nb, out.data_ptr(), _stream(), _sptr(shift))
     return _unshift(h, out, shift, d)
 
 
@@ -759,49 +754,41 @@ def _prep_rows(y, w, sel, n):
 
 
 def _tiled_pre(T: "TiledBF16", y, w, sel, xmode):
-    """The entry point of the tiled pass and its leading arguments: ``gram_tall_patched`` /
-    ``gram_tall_packed`` where ``T`` carries that companion (same grid, same wave -> superstep
-    map, bit-identical sums), else ``gram_tall``.  The patched kernel takes unweighted, unselected
-    rows with an f32 label; any other call on such a table reads the raw tiles."""
-    rows = (y.data_ptr(), dtype_code(y), _ptr(w), dtype_code(w) if w is not None else 0, _ptr(sel), xmode)
-    if isinstance(T.packed, PatchedTiles):
-        p = T.packed
+    """``(kind, args)`` of the tiled pass: the companion it reads ("patched", "mixed" or None: the
+    raw tiles; same grid, same wave -> superstep map, bit-identical sums) and ``gram_tall``'s
+    arguments up to the per-launch ones.  The patched kernel takes unweighted, unselected rows with
+    an f32 label; any other call on such a table reads the raw tiles."""
+    kind, comp = None, (0, 0, 0, 0)  # xpack, xdir, xrec, xovf
+    p = T.packed
+    if isinstance(p, PatchedTiles):
         if xmode == 0 and w is None and sel is None and y.dtype == torch.float32:
             ovf = p.ovf if p.ovf.numel() else p.dir
-            return "patched", (T.buf.data_ptr(), p.a.data_ptr(), p.dir.data_ptr(), ovf.data_ptr(), int(T.d), int(T.n),
-                               y.data_ptr(), dtype_code(y))
-    elif T.packed is not None:
-        return "mixed", (T.buf.data_ptr(), T.packed.a.data_ptr(), T.packed.dir.data_ptr(), int(T.d), int(T.n)) + rows
-    return None, (2, T.buf.data_ptr(), 0, int(T.d), int(T.n), 2) + rows
-
-
-def _tiled_launch(h, kind, pre, partials, nb, out, stream, reduce):
-    if kind == "patched":
-        h.gram_tall_patched(*pre, partials.data_ptr(), nb, out.data_ptr(), stream, reduce)
-    elif kind == "mixed":
-        h.gram_tall_packed(*pre, partials.data_ptr(), nb, out.data_ptr(), stream, reduce)
-    else:
-        h.gram_tall(*pre, partials.data_ptr(), nb, out.data_ptr(), stream, 1, reduce, 0)
+            kind, comp = "patched", (p.a.data_ptr(), 0, p.dir.data_ptr(), ovf.data_ptr())
+    elif p is not None:
+        kind, comp = "mixed", (p.a.data_ptr(), p.dir.data_ptr(), 0, 0)
+    # (mode bf16; ld unused; the tiles hold x - s already: the kernel takes no shift)
+    return kind, (2, T.buf.data_ptr(), 0, int(T.d), int(T.n), 2, 1, 0) + comp + (
+        y.data_ptr(), dtype_code(y), _ptr(w), _wdt(w), _ptr(sel), xmode)
 
 
 class TiledGramPlan:
-    """The resolved launch of one tiled bf16 Gram pass (``gram_tall`` mode 2 with the fold left to
-    the fit's side stream): row operands prepared, block count planned and argument tuple built
-    once, so a repeated fit of the same table only allocates its outputs and launches
-    (``models/regression.py`` fit replay, ~0.14 ms of device work per fit at the 8-GPU shard)."""
+    """The resolved launch of one tiled bf16 Gram pass (``gram_tall`` mode 2): row operands
+    prepared, block count planned (or ``blocks``) and argument tuple built once, so a repeated fit
+    of the same table only allocates its outputs and launches (``models/regression.py`` fit replay,
+    ~0.14 ms of device work per fit at the 8-GPU shard)."""
 
-    __slots__ = ("h", "T", "y", "w", "sel", "d", "nb", "flat_len", "part_len", "dev", "pre", "post", "packed", "kind")
+    __slots__ = ("h", "T", "y", "w", "sel", "d", "nb", "flat_len", "part_len", "dev", "pre", "packed", "kind")
 
-    def __init__(self, h, T: "TiledBF16", y, w, sel, x_zero_dead):
+    def __init__(self, h, T: "TiledBF16", y, w, sel, x_zero_dead, blocks: Optional[int] = None):
         d, n = T.d, T.n
         if d > 64:
             raise ValueError("tiled Gram supports d <= 64")
         _check_dev(T.buf, y, w, sel)
         y, w, sel = _prep_rows(y, w, sel, n)
-        xmode = 2 if w is not None else (1 if (sel is not None and not x_zero_dead) else 0)
+        xmode = _xmode(w, sel, x_zero_dead)
         self.h, self.T, self.y, self.w, self.sel, self.d, self.dev = h, T, y, w, sel, d, T.device
-        self.nb = int(_plan_blocks(h, 2, d, n, 2, xmode))
-        self.flat_len = 5 + 2 * d + d * (d + 1) // 2
+        self.nb = int(blocks or _plan_blocks(h, 2, d, n, 2, xmode))
+        self.flat_len = gram_layout_size(d)
         self.part_len = self.nb * int(h.gram_partial_stride(2, d))
         # kind: the companion this launch reads ("patched", "mixed" or None); packed: T has one
         self.kind, self.pre = _tiled_pre(T, y, w, sel, xmode)
@@ -812,7 +799,7 @@ class TiledGramPlan:
         un-shift left to the caller) or the folded, un-shifted statistics."""
         out = torch.empty(self.flat_len, dtype=torch.float64, device=self.dev)
         partials = torch.empty(self.part_len, dtype=torch.float64, device=self.dev)
-        _tiled_launch(self.h, self.kind, self.pre, partials, self.nb, out, stream, not defer)
+        self.h.gram_tall(*self.pre, partials.data_ptr(), self.nb, out.data_ptr(), stream, not defer)
         sh = self.T.shift
         if defer:
             return DeferredGram(self.h, 2, partials, self.nb, self.d, out, sh)
@@ -822,22 +809,7 @@ class TiledGramPlan:
 
 
 def _gram_tiled(h, T: "TiledBF16", y, w, sel, x_zero_dead, blocks, defer=False):
-    d, n = T.d, T.n
-    if d > 64:
-        raise ValueError("tiled Gram supports d <= 64")
-    _check_dev(T.buf, y, w, sel)
-    y, w, sel = _prep_rows(y, w, sel, n)
-    out = torch.empty(5 + 2 * d + d * (d + 1) // 2, dtype=torch.float64, device=T.device)
-    xmode = 2 if w is not None else (1 if (sel is not None and not x_zero_dead) else 0)
-    nb = int(blocks or _plan_blocks(h, 2, d, n, 2, xmode))
-    P = int(h.gram_partial_stride(2, d))
-    partials = torch.empty(nb * P, dtype=torch.float64, device=T.device)
-    # (the tiles hold x - s already: the kernel takes no shift, the statistics are un-shifted after the fold)
-    kind, pre = _tiled_pre(T, y, w, sel, xmode)
-    _tiled_launch(h, kind, pre, partials, nb, out, _stream(), not defer)
-    if defer:
-        return DeferredGram(h, 2, partials, nb, d, out, T.shift)
-    return _unshift(h, out, T.shift, d)
+    return TiledGramPlan(h, T, y, w, sel, x_zero_dead, blocks).launch(_stream(), defer)
 
 
 _syrk_pairs = {}
@@ -860,7 +832,7 @@ def _gram_syrk(h, X, y, w, sel, compute_f64: bool):
     row factor applied in-kernel -- one pass, no library GEMM, no dense copies of X."""
     d, n = X.shape
     dev = X.device
-    out = torch.empty(5 + 2 * d + d * (d + 1) // 2, dtype=torch.float64, device=dev)
+    out = torch.empty(gram_layout_size(d), dtype=torch.float64, device=dev)
     if n == 0:
         return out.zero_()
     if X.dtype not in (torch.float64, torch.float32, torch.bfloat16):
@@ -1863,7 +1835,7 @@ def _gram_wide(h, T: TiledWide, y, w, sel, x_zero_dead, defer: bool = False):
     nsup = max(1, (n + 63) // 64)
     sc = _wide_schedule(h, P, nsup, eb, dev)
     splitk = sc.splitk
-    out = torch.empty(5 + 2 * d + d * (d + 1) // 2, dtype=torch.float64, device=dev)
+    out = torch.empty(gram_layout_size(d), dtype=torch.float64, device=dev)
     part = torch.empty(sc.tiles * 256 * 256, dtype=torch.float32, device=dev)
     # data-parallel fit over RCCL: fold band by band and all-reduce each band while the next folds
     banded = comm.collectives_active() and comm.backend() == "nccl"

@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import native
+from .layout import gram_layout_size
 from .groupby import group_agg, group_encode, group_encode_columns, group_limits, group_scale  # noqa: F401  (K5g)
 
 __all__ = ["selected_indices", "pack_columns", "gram_stats", "predict", "regression_metrics",
@@ -104,10 +105,6 @@ def pack_wide(parts: Sequence[torch.Tensor], eb: int, sel: Optional[torch.Tensor
 # ------------------------------------------------------------------------------------------
 # K5 — Gram / WLS statistics
 # ------------------------------------------------------------------------------------------
-def gram_layout_size(d: int) -> int:
-    return 5 + 2 * d + d * (d + 1) // 2
-
-
 _upper_idx = {}
 
 

@@ -21,7 +21,13 @@ from __future__ import annotations
 import torch
 
 __all__ = ["TiledBF16", "tiled_offsets", "PackedTiles", "pack_reference", "unpack_reference",
-           "PatchedTiles", "patch_reference", "unpatch_reference", "patched_entries"]
+           "PatchedTiles", "patch_reference", "unpatch_reference", "patched_entries", "gram_layout_size"]
+
+
+def gram_layout_size(d: int) -> int:
+    """Length of the flat WLS statistics of d features: count, Σw, Σw², Σwy, Σwy², Σw·x (d),
+    Σw·x·y (d), packed upper Σw·x·xᵀ."""
+    return 5 + 2 * d + d * (d + 1) // 2
 
 
 def tiled_offsets(feats: torch.Tensor, rows: torch.Tensor, d: int) -> torch.Tensor:
