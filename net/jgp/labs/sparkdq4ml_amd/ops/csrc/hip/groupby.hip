@@ -23,103 +23,14 @@
 #include <stdexcept>
 
 #include "common.h"
+#include "keys.h"
 
 namespace dq4ml {
 namespace {
 
-typedef __attribute__((ext_vector_type(2))) long long i64x2;
-typedef __attribute__((ext_vector_type(4))) int i32x4;
-typedef unsigned long long u64;
+static_assert(kGroupRun == kRawRun, "the run loaders of keys.h read kGroupRun rows");
 
-constexpr u64 kSign = 0x8000000000000000ull;
-constexpr u64 kNaNBits = 0x7ff8000000000000ull;
-constexpr u64 kInfBits = 0x7ff0000000000000ull;
 constexpr u64 kEmpty = ~0ull;
-
-__device__ __forceinline__ bool is_float_dt(int dt) { return dt == DT_F64 || dt == DT_F32; }
-
-// kGroupRun consecutive rows [r0, r0 + 4) of a typed column widened to 64 bits (floats: the bits of
-// the value as a double; integers and booleans: the value as an i64; 0 past n).  16-byte loads when
-// the run is complete and aligned (r0 is a multiple of 4), else a guarded scalar tail.
-template <int DT>
-__device__ __forceinline__ void load_run_raw(const void* p, int64_t r0, int64_t n, u64 x[kGroupRun]) {
-  const bool aligned = (reinterpret_cast<uintptr_t>(p) & 15) == 0;
-  if (aligned && r0 + kGroupRun <= n) {
-    if constexpr (DT == DT_F64) {
-      const f64x2 a = *gptr<f64x2>(reinterpret_cast<const double*>(p) + r0);
-      const f64x2 b = *gptr<f64x2>(reinterpret_cast<const double*>(p) + r0 + 2);
-      x[0] = (u64)__double_as_longlong(a[0]), x[1] = (u64)__double_as_longlong(a[1]);
-      x[2] = (u64)__double_as_longlong(b[0]), x[3] = (u64)__double_as_longlong(b[1]);
-    } else if constexpr (DT == DT_I64) {
-      const i64x2 a = *gptr<i64x2>(reinterpret_cast<const long long*>(p) + r0);
-      const i64x2 b = *gptr<i64x2>(reinterpret_cast<const long long*>(p) + r0 + 2);
-      x[0] = (u64)a[0], x[1] = (u64)a[1], x[2] = (u64)b[0], x[3] = (u64)b[1];
-    } else if constexpr (DT == DT_F32) {
-      const f32x4 a = *gptr<f32x4>(reinterpret_cast<const float*>(p) + r0);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) x[j] = (u64)__double_as_longlong((double)a[j]);
-    } else if constexpr (DT == DT_I32) {
-      const i32x4 a = *gptr<i32x4>(reinterpret_cast<const int*>(p) + r0);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) x[j] = (u64)(long long)a[j];
-    } else {
-      const uint32_t w = *gptr<uint32_t>(reinterpret_cast<const uint8_t*>(p) + r0);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) x[j] = ((w >> (8 * j)) & 0xffu) ? 1ull : 0ull;
-    }
-    return;
-  }
-#pragma unroll
-  for (int j = 0; j < kGroupRun; ++j) {
-    const int64_t r = r0 + j;
-    u64 v = 0;
-    if (r < n) {
-      if constexpr (DT == DT_F64) v = (u64)__double_as_longlong(gptr<double>(p)[r]);
-      else if constexpr (DT == DT_I64) v = (u64)gptr<long long>(p)[r];
-      else if constexpr (DT == DT_F32) v = (u64)__double_as_longlong((double)gptr<float>(p)[r]);
-      else if constexpr (DT == DT_I32) v = (u64)(long long)gptr<int>(p)[r];
-      else v = gptr<uint8_t>(p)[r] != 0 ? 1ull : 0ull;
-    }
-    x[j] = v;
-  }
-}
-
-// (the switch is block-uniform)
-__device__ __forceinline__ void load_run(const void* p, int dt, int64_t r0, int64_t n, u64 x[kGroupRun]) {
-  switch (dt) {
-    case DT_F64: load_run_raw<DT_F64>(p, r0, n, x); break;
-    case DT_F32: load_run_raw<DT_F32>(p, r0, n, x); break;
-    case DT_I32: load_run_raw<DT_I32>(p, r0, n, x); break;
-    case DT_I64: load_run_raw<DT_I64>(p, r0, n, x); break;
-    default: load_run_raw<DT_U8>(p, r0, n, x); break;
-  }
-}
-
-// bit j: row r0 + j is inside n and its 0/1 byte is set (null mask: every row inside n)
-__device__ __forceinline__ unsigned mask_run(const uint8_t* m, int64_t r0, int64_t n) {
-  unsigned out = 0;
-  if (m != nullptr && r0 + kGroupRun <= n && ((reinterpret_cast<uintptr_t>(m + r0) & 3) == 0)) {
-    const uint32_t w = *gptr<uint32_t>(m + r0);
-#pragma unroll
-    for (int j = 0; j < kGroupRun; ++j) out |= ((w >> (8 * j)) & 0xffu) ? (1u << j) : 0u;
-    return out;
-  }
-#pragma unroll
-  for (int j = 0; j < kGroupRun; ++j) {
-    const int64_t r = r0 + j;
-    if (r < n && (m == nullptr || gptr<uint8_t>(m)[r] != 0)) out |= 1u << j;
-  }
-  return out;
-}
-
-// order key of a widened value; fold: the grouping rule (-0.0 == +0.0), else -0.0 < +0.0 (MIN / MAX)
-__device__ __forceinline__ u64 order_key(u64 raw, bool isf, bool fold) {
-  if (!isf) return raw ^ kSign;
-  u64 b = raw;
-  if ((b & ~kSign) > kInfBits) b = kNaNBits;  // every NaN: one canonical NaN above +inf
-  if (fold && b == kSign) b = 0;
-  return (b & kSign) ? ~b : (b | kSign);
-}
 
 __device__ __forceinline__ int word_kind(int op, int w) {
   switch (op) {

@@ -16,6 +16,7 @@
 #include "gram_folds.h"
 #include "quantile.h"
 #include "groupby.h"
+#include "sort.h"
 #include "gram_wide.h"
 #include "gram_syrk.h"
 #include "wls_small.h"
@@ -303,6 +304,29 @@ PYBIND11_MODULE(_dq4ml_hip, m) {
     a.S = (int)S;
     a.words = words;
     group_agg(a, P<unsigned long long>(acc), blocks, as_stream(stream));
+  });
+  m.def("sort_blocks", &sort_blocks);
+  // threads per block, keys per thread, tile in rows, digit width
+  m.def("sort_limits", []() { return py::make_tuple(kSortThreads, kSortRun, kSortTile, kSortBits); });
+  // keys / idx: [m] u64 / u32; hist: [9][256] u64, zeroed (the 8 key bytes, then the null digit)
+  m.def("sort_keys", [](uintptr_t col, int dt, uintptr_t valid, uintptr_t perm, int64_t n, int64_t m_, bool descending,
+                        uintptr_t keys, uintptr_t idx, uintptr_t hist, int blocks, uintptr_t stream) {
+    SortKeyCol a{};
+    a.col = P<const void>(col);
+    a.valid = P<const uint8_t>(valid);
+    a.perm = P<const unsigned>(perm);
+    a.n = n;
+    a.m = m_;
+    a.dt = dt;
+    a.descending = descending ? 1 : 0;
+    sort_keys(a, P<unsigned long long>(keys), P<unsigned>(idx), P<unsigned long long>(hist), blocks, as_stream(stream));
+  });
+  // one stable pass on `digit` (8: the null digit): count, scan, scatter
+  m.def("sort_pass", [](uintptr_t keys_in, uintptr_t idx_in, uintptr_t keys_out, uintptr_t idx_out, int64_t m_, int digit,
+                        uintptr_t counts, int64_t stride, uintptr_t hist_row, uintptr_t base, int blocks, uintptr_t stream) {
+    sort_pass(P<const unsigned long long>(keys_in), P<const unsigned>(idx_in), P<unsigned long long>(keys_out),
+              P<unsigned>(idx_out), m_, digit, P<unsigned>(counts), stride, P<const unsigned long long>(hist_row),
+              P<const unsigned>(base), blocks, as_stream(stream));
   });
   m.def("gram_window_fold", [](uintptr_t part, int64_t rows, int gw, uintptr_t flat, uintptr_t stream) {
     gram_window_fold(P<const double>(part), rows, gw, P<double>(flat), as_stream(stream));

@@ -615,6 +615,72 @@ def group_encode_hash(col, valid, sel, capacity: int, max_capacity: int, union=N
     return gid, keys, cap
 
 
+# ------------------------------------------------------------------------------------------
+# stable radix sort (csrc/hip/sort.hip); the algorithm and its numpy twin are in ops/sort.py
+# ------------------------------------------------------------------------------------------
+def sort_permutation(cols, valids, sel, ascending, nulls_first, blocks: Optional[int] = None,
+                     stats: Optional[list] = None) -> torch.Tensor:
+    """Device form of ``ops.sort.sort_permutation`` (flags already one per column).  Owns the
+    buffers: two key arrays (u64) and two index arrays (u32) of the live count for the ping-pong,
+    the ``[256][tiles]`` counts table, and one ``[9][256]`` histogram per sort column, which is
+    read back once per column to pick the live digits and their bin bases."""
+    h = native.hip()
+    from . import sort as so
+
+    assert tuple(h.sort_limits()) == so.sort_limits(), "sort.py / sort.h constants differ"
+    _check_dev(*cols, *valids, sel)
+    n = int(cols[0].numel())
+    cols = [_group_col(c, n, "sort") for c in cols]
+    valids = [_mask_u8(v, n, "a validity mask", "sort") for v in valids]
+    sel = _mask_u8(sel, n, "the selection", "sort")
+    if blocks is not None and int(blocks) < 1:
+        raise ValueError("blocks must be >= 1")
+    dev = cols[0].device
+    perm = None
+    m = n
+    if sel is not None:
+        perm = compact_indices(sel).to(torch.int32)
+        m = int(perm.numel())
+    if m == 0:
+        if stats is not None:
+            stats.extend({"live": []} for _ in cols)
+        return torch.empty(0, dtype=torch.int64, device=dev)
+    tile, bins = so.SORT_TILE, 1 << so.SORT_BITS
+    tiles = (m + tile - 1) // tile
+    stride = (tiles + 3) & ~3  # 16-byte rows for the scan's vector loads
+    keys = [torch.empty(m, dtype=torch.int64, device=dev) for _ in range(2)]
+    idx = [torch.empty(m, dtype=torch.int32, device=dev) for _ in range(2)]
+    counts = torch.empty(bins * stride, dtype=torch.int32, device=dev)
+    nb = int(blocks) if blocks else int(h.sort_blocks(m))
+    st = _stream()
+    cur = 0
+    for c, v, asc, nf in reversed(list(zip(cols, valids, ascending, nulls_first))):
+        hist = torch.zeros(so.SORT_DIGITS + 1, bins, dtype=torch.int64, device=dev)
+        # (reads perm[i] and writes idx[cur][i] in the same thread: in place after the first column)
+        h.sort_keys(c.data_ptr(), dtype_code(c), _ptr(v), _ptr(perm), n, m, not asc, keys[cur].data_ptr(),
+                    idx[cur].data_ptr(), hist.data_ptr(), nb, st)
+        H = hist.cpu().numpy()  # the one host read of this column
+        seen = H[:so.SORT_DIGITS].copy()
+        seen[:, 0] -= H[so.NULL_DIGIT, 1]  # the nulls (key 0) never make a digit live; they stay in the bases
+        live = [d for d in range(so.SORT_DIGITS) if np.count_nonzero(seen[d]) > 1]
+        if H[so.NULL_DIGIT, 0] > 0 and H[so.NULL_DIGIT, 1] > 0:
+            live.append(so.NULL_DIGIT)
+        for d in live:
+            if d == so.NULL_DIGIT:  # bin 1 holds the nulls
+                base = np.array([H[d, 1], 0] if nf else [0, H[d, 0]], dtype=np.int64)
+                base = np.concatenate([base, np.zeros(bins - 2, dtype=np.int64)])
+            else:
+                base = np.cumsum(H[d]) - H[d]
+            base_d = _h2d(base.astype(np.int32), dev)
+            h.sort_pass(keys[cur].data_ptr(), idx[cur].data_ptr(), keys[1 - cur].data_ptr(), idx[1 - cur].data_ptr(), m, d,
+                        counts.data_ptr(), stride, hist[d].data_ptr(), base_d.data_ptr(), nb, st)
+            cur = 1 - cur
+        perm = idx[cur]
+        if stats is not None:
+            stats.append({"live": live})
+    return idx[cur].to(torch.int64) & 0x7FFFFFFF  # (the top bit carried the last column's null flag)
+
+
 def gram_skinny_cols(parts: List[torch.Tensor], y, w, sel, blocks: Optional[int] = None):
     """f64 WLS statistics of a narrow (d <= 8) VectorAssembler output straight from its SOURCE
     columns (any of f64/f32/bf16/int32/int64/bool, mixed): the assembled [d, n] f64 matrix is

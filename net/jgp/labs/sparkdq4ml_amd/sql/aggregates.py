@@ -21,7 +21,8 @@ from .expressions import Alias, AnalysisException, ColRef, Expr, Lit, to_expr
 from .table import ColumnData, Table
 from .types import (BooleanType, DoubleType, LongType, StringType, StructField, StructType, VectorUDT, is_numeric)
 
-__all__ = ["AggExpr", "GroupedData", "build_aggregate", "contains_aggregate", "aggregate_table", "dedupe_table"]
+__all__ = ["AggExpr", "GroupedData", "build_aggregate", "contains_aggregate", "aggregate_table", "dedupe_table",
+           "sort_table"]
 
 _FNS = ("count", "sum", "avg", "min", "max")
 _I64_MIN = -(1 << 63)
@@ -323,6 +324,27 @@ def dedupe_table(t: Table, subset: Sequence[str], sharded: bool) -> Table:
     keep = torch.zeros(t.nrows, dtype=torch.bool, device=t.device)
     keep[first] = True
     return Table(t.schema, t.columns, t.nrows, keep, t.device)
+
+
+def sort_table(t: Table, orders) -> Table:
+    """The result table of ``Sort``: the live rows of ``t`` in the stable sorted order of
+    ``orders`` = ``(column, ascending, nulls_first)``, compact (every column gathered by the
+    permutation of ``ops.kernels.sort_permutation``, no selection vector).  A string column sorts
+    by its host dictionary codes; the selection vector goes to the sort as it is."""
+    from ..ops import kernels
+
+    _pending(t)
+    cols, valids = [], []
+    for name, _, _ in orders:
+        c = t.column(name)
+        if isinstance(c.dtype, VectorUDT):
+            raise AnalysisException(f"cannot sort by '{name}': {c.dtype.simpleString()} is not an orderable data type")
+        vals, valid, _ = _key_column(c, t.device, False)
+        cols.append(vals)
+        valids.append(valid)
+    perm = kernels.sort_permutation(cols, valids, t.sel, [o[1] for o in orders], [o[2] for o in orders])
+    perm = perm.to(t.device)
+    return Table(t.schema, [c.index(perm) for c in t.columns], int(perm.numel()), None, t.device)
 
 
 # ------------------------------------------------------------------------------------------

@@ -390,6 +390,51 @@ class DataFrame:
 
     drop_duplicates = dropDuplicates
 
+    # ---- ordering -------------------------------------------------------------------------
+    def _sorted(self, cols, ascending, global_sort: bool) -> "DataFrame":
+        from .expressions import SortOrder
+        from .plan import build_sort
+
+        if len(cols) == 1 and isinstance(cols[0], (list, tuple)):
+            cols = cols[0]
+        if not cols:
+            raise ValueError("should sort by at least one column")
+        exprs = [ColRef(c) if isinstance(c, str) else to_expr(c) for c in cols]
+        schema = self.schema
+        for e in exprs:
+            base = e.child if isinstance(e, SortOrder) else e
+            if isinstance(base, ColRef) and schema.resolve_ci(base.name) is None:
+                raise AnalysisException(f'Cannot resolve column name "{base.name}" among ({", ".join(schema.names)});')
+        if ascending is not None:
+            if isinstance(ascending, (bool, int)):
+                flags = [bool(ascending)] * len(exprs)
+            elif isinstance(ascending, (list, tuple)):
+                flags = [bool(a) for a in ascending]
+                if len(flags) != len(exprs):
+                    raise ValueError(f"ascending must be a boolean or a list of {len(exprs)} booleans, one per sort column; "
+                                     f"got {len(flags)}")
+            else:
+                raise TypeError(f"ascending can only be boolean or list, but got {type(ascending)}")
+            # (pyspark: a true flag keeps the column's own order, a false one makes it descending)
+            exprs = [e if a else SortOrder(e.child if isinstance(e, SortOrder) else e, False) for e, a in zip(exprs, flags)]
+        orders = [e if isinstance(e, SortOrder) else SortOrder(e, True) for e in exprs]
+        return self._with(build_sort(self._plan, orders, global_sort))
+
+    def orderBy(self, *cols, ascending=None) -> "DataFrame":
+        """The rows in the stable sorted order of ``cols`` (names, Columns -- ``col.desc()``,
+        ``asc_nulls_last(...)``, expressions -- or one list), the first the most significant.
+        ``ascending``: a boolean, or a list of booleans of the same length.  Ascending puts nulls
+        first and descending last unless the order says otherwise; doubles order as in Spark
+        (``-0.0 = 0.0``, NaN above ``+inf``); rows that compare equal keep their order.  A global
+        sort across data-parallel ranks is not implemented: see ``sortWithinPartitions``."""
+        return self._sorted(cols, ascending, True)
+
+    sort = orderBy
+
+    def sortWithinPartitions(self, *cols, ascending=None) -> "DataFrame":
+        """``orderBy`` of every partition on its own: on a data-parallel plan, of every rank's rows."""
+        return self._sorted(cols, ascending, False)
+
     # ---- persistence -----------------------------------------------------------------------
     def cache(self):
         execute(self._plan, self.sparkSession)

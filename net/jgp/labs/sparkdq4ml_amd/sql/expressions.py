@@ -24,7 +24,7 @@ from .types import (BooleanType, DataType, DecimalType, DoubleType, FloatType, I
                     is_numeric, parse_type_name, wider_numeric)
 
 __all__ = [
-    "Expr", "ColRef", "Lit", "BinOp", "Not", "Neg", "Cast", "Alias", "IsNull", "IsNotNull",
+    "Expr", "ColRef", "Lit", "BinOp", "Not", "Neg", "Cast", "Alias", "SortOrder", "IsNull", "IsNotNull",
     "If", "CaseWhen", "Coalesce", "UdfCall", "RaiseIfNull", "AnalysisException", "EvalContext",
     "to_expr",
 ]
@@ -565,6 +565,32 @@ class Alias(Expr):
 
     def eval(self, ctx):
         return self.child.eval(ctx)
+
+
+class SortOrder(Expr):
+    """``child ASC|DESC NULLS FIRST|LAST``: one order of ``orderBy`` / ``ORDER BY``.  Spark's
+    defaults: ascending puts nulls first, descending puts them last.  Only a sort evaluates it."""
+
+    def __init__(self, child, ascending: bool = True, nulls_first: Optional[bool] = None):
+        self.child = to_expr(child)
+        self.ascending = bool(ascending)
+        self.nulls_first = self.ascending if nulls_first is None else bool(nulls_first)
+
+    def children(self):
+        return [self.child]
+
+    def data_type(self, schema):
+        return self.child.data_type(schema)
+
+    def nullable(self, schema):
+        return self.child.nullable(schema)
+
+    def sql_name(self):
+        return (f"{self.child.sql_name()} {'ASC' if self.ascending else 'DESC'} "
+                f"NULLS {'FIRST' if self.nulls_first else 'LAST'}")
+
+    def eval(self, ctx):
+        raise AnalysisException(f"sort order {self.sql_name()} is only allowed in orderBy() / sort() or ORDER BY")
 
 
 class IsNull(Expr):

@@ -6,7 +6,8 @@ from .column import Column
 from .expressions import CaseWhen, Coalesce, ColRef, IsNull, Lit, UdfCall, to_expr
 
 __all__ = ["col", "column", "lit", "callUDF", "call_udf", "udf", "when", "coalesce", "isnull", "expr",
-           "count", "sum", "avg", "mean", "min", "max"]
+           "count", "sum", "avg", "mean", "min", "max", "asc", "desc", "asc_nulls_first", "asc_nulls_last",
+           "desc_nulls_first", "desc_nulls_last"]
 
 
 def col(name: str) -> Column:
@@ -70,6 +71,36 @@ def min(c) -> Column:  # noqa: A001
 
 def max(c) -> Column:  # noqa: A001
     return _agg("max", c)
+
+
+def _order_col(c) -> Column:
+    return c if isinstance(c, Column) else col(c)
+
+
+def asc(c) -> Column:
+    """Ascending sort order of a column (name or Column), nulls first."""
+    return _order_col(c).asc()
+
+
+def desc(c) -> Column:
+    """Descending sort order, nulls last."""
+    return _order_col(c).desc()
+
+
+def asc_nulls_first(c) -> Column:
+    return _order_col(c).asc_nulls_first()
+
+
+def asc_nulls_last(c) -> Column:
+    return _order_col(c).asc_nulls_last()
+
+
+def desc_nulls_first(c) -> Column:
+    return _order_col(c).desc_nulls_first()
+
+
+def desc_nulls_last(c) -> Column:
+    return _order_col(c).desc_nulls_last()
 
 
 def expr(text: str) -> Column:

@@ -5,8 +5,8 @@
 
 (``DataQuality4MachineLearningApp.java:77-78,89-90``) — projections with ``CAST``, aliases with or
 without ``AS``, single-table ``FROM`` of a temp view, ``WHERE`` with arithmetic / comparisons /
-boolean logic / ``IS [NOT] NULL`` / ``BETWEEN`` / ``IN``, ``CASE WHEN``, ``LIMIT``, UDF and
-built-in function calls.  It produces the same plan nodes as the DataFrame API.
+boolean logic / ``IS [NOT] NULL`` / ``BETWEEN`` / ``IN``, ``CASE WHEN``, ``GROUP BY``,
+``ORDER BY expr [ASC|DESC] [NULLS FIRST|NULLS LAST]``, ``LIMIT``, UDF and built-in function calls.  It produces the same plan nodes as the DataFrame API.
 """
 from __future__ import annotations
 
@@ -14,10 +14,10 @@ import re
 from typing import List, Optional, Tuple
 
 from .expressions import (Alias, AnalysisException, BinOp, CaseWhen, Cast, ColRef, Coalesce,
-                          Expr, If, IsNotNull, IsNull, Lit, Neg, Not, UdfCall)
+                          Expr, If, IsNotNull, IsNull, Lit, Neg, Not, SortOrder, UdfCall)
 from .aggregates import AggExpr, build_aggregate, contains_aggregate
 from .fn import MathFn, BUILTIN_MATH
-from .plan import Aggregate, Filter, Limit, Project, output_name
+from .plan import Aggregate, Filter, Limit, Project, build_sort, output_name
 from .skey import expr_key
 
 __all__ = ["parse_expression", "parse_select_item", "plan_sql", "ParseException"]
@@ -37,7 +37,7 @@ _TOKEN = re.compile(r"""
 """, re.VERBOSE)
 
 _KEYWORDS = {"select", "from", "where", "as", "and", "or", "not", "cast", "is", "null", "true", "false",
-             "case", "when", "then", "else", "end", "limit", "between", "in", "distinct", "like", "group", "by"}
+             "case", "when", "then", "else", "end", "limit", "between", "in", "distinct", "like", "group", "by", "order"}
 
 
 def _tokenize(text: str) -> List[Tuple[str, str]]:
@@ -94,8 +94,9 @@ class _Parser:
         return _bind_query(self.query_syntax(), self.text, session)
 
     def query_syntax(self):
-        """The statement's syntax: (select items, view name, alias, WHERE, LIMIT) -- nothing of
-        the catalog is read here, so the result is cached per text (``plan_sql``)."""
+        """The statement's syntax: (select items, view name, WHERE, LIMIT, DISTINCT, GROUP BY,
+        ORDER BY) -- nothing of the catalog is read here, so the result is cached per text
+        (``plan_sql``)."""
         self.expect("kw", "select")
         distinct = bool(self.accept("kw", "distinct"))
         items = self.select_list()
@@ -115,6 +116,12 @@ class _Parser:
             group = [self.expr()]
             while self.accept("op", ","):
                 group.append(self.expr())
+        order = None
+        if self.accept("kw", "order"):
+            self.expect("kw", "by")
+            order = [self.order_item()]
+            while self.accept("op", ","):
+                order.append(self.order_item())
         limit = None
         if self.accept("kw", "limit"):
             limit = int(self.expect("num")[1])
@@ -125,7 +132,25 @@ class _Parser:
             where = _strip_qual(where, quals)
         if group is not None:
             group = [_strip_qual(e, quals) for e in group]
-        return items, tname, where, limit, distinct, group
+        if order is not None:
+            order = [(_strip_qual(e, quals), asc, nf) for e, asc, nf in order]
+        return items, tname, where, limit, distinct, group, order
+
+    def order_item(self):
+        """``expr [ASC|DESC] [NULLS FIRST|NULLS LAST]`` -> (expr, ascending, nulls_first or None)."""
+        e = self.expr()
+        asc = True
+        if self.accept("ident", "desc"):
+            asc = False
+        else:
+            self.accept("ident", "asc")
+        nf = None
+        if self.accept("ident", "nulls"):
+            t = self.expect("ident")
+            if t[1].lower() not in ("first", "last"):
+                raise ParseException(f"\nmismatched input '{t[1]}' expecting FIRST or LAST")
+            nf = t[1].lower() == "first"
+        return e, asc, nf
 
     def select_list(self):
         items = [self.select_item()]
@@ -351,7 +376,7 @@ def _bind_query(syntax, text: str, session):
     replaced between two runs of the same text binds to the new plan).  Expression trees are
     immutable once parsed, so plans may share them; a statement bound over a view of the same
     structure (sql/skey.py) reuses the analyzed nodes (fresh copies: no result is shared)."""
-    items, tname, where, limit, distinct, group = syntax
+    items, tname, where, limit, distinct, group, order = syntax
     plan = session.catalog._views.get(tname.lower())
     if plan is None:
         raise AnalysisException(f"Table or view not found: {tname}; line 1 pos {text.lower().find(tname.lower())}")
@@ -362,7 +387,7 @@ def _bind_query(syntax, text: str, session):
         for t in tmpl:
             plan = t.fresh(plan)
         return plan
-    out = _bind_new(items, where, limit, plan, distinct, group)
+    out = _bind_new(items, where, limit, plan, distinct, group, order)
     if key is not None and out.skey() is not None:
         nodes, p = [], out
         while p is not plan:
@@ -380,7 +405,7 @@ def _bind_query(syntax, text: str, session):
     return out
 
 
-def _bind_new(items, where, limit, plan, distinct=False, group=None):
+def _bind_new(items, where, limit, plan, distinct=False, group=None, order=None):
     if where is not None:
         if contains_aggregate(where):
             raise AnalysisException("Aggregate/Window/Generate expressions are not valid in where clause of the query.")
@@ -391,7 +416,8 @@ def _bind_new(items, where, limit, plan, distinct=False, group=None):
             exprs += [ColRef(n) for n in plan.schema().names]
         else:
             exprs.append(e)
-    if group is not None or any(contains_aggregate(e) for e in exprs):
+    grouped = group is not None or any(contains_aggregate(e) for e in exprs)
+    if grouped:
         plan = _bind_grouped(exprs, group or [], plan)
     else:
         plan = Project(plan, exprs)
@@ -400,9 +426,42 @@ def _bind_new(items, where, limit, plan, distinct=False, group=None):
             e.data_type(cs)
     if distinct:  # the distinct rows of the select list
         plan = Aggregate(plan, plan.schema().names, [])
+    if order:
+        plan = _bind_order(order, plan, grouped or distinct)
     if limit is not None:
         plan = Limit(plan, limit)
     return plan
+
+
+def _bind_order(order, plan, closed: bool):
+    """``ORDER BY`` over ``plan``, the node that produces the select list.  An item resolves against
+    the select list's output names first; then, as a positive integer literal, it is an ordinal
+    into the select list; then, unless the query is ``closed`` (GROUP BY / aggregates / DISTINCT),
+    against the columns of the FROM view, which are carried through the select list's Project as
+    hidden columns and dropped above the sort."""
+    schema = plan.schema()
+    names = schema.names
+    orders, hidden = [], []
+    for i, (e, asc, nf) in enumerate(order):
+        if contains_aggregate(e):
+            raise AnalysisException(f"aggregate functions are not supported in ORDER BY, but found {e.sql_name()}: select "
+                                    f"it under an alias and order by the alias")
+        if isinstance(e, Lit) and isinstance(e.value, int) and not isinstance(e.value, bool):
+            if not 1 <= e.value <= len(names):
+                raise AnalysisException(f"ORDER BY position {e.value} is not in select list (valid range is [1, {len(names)}])")
+            orders.append(SortOrder(ColRef(names[e.value - 1]), asc, nf))
+        elif all(schema.resolve_ci(r) is not None for r in e.references()):
+            orders.append(SortOrder(e, asc, nf))
+        elif closed:
+            raise AnalysisException(f"cannot resolve '{e.sql_name()}' given input columns: [{', '.join(names)}]")
+        else:
+            e.data_type(plan.child.schema())  # (raises on a column the view does not have either)
+            name = f"_order_by_{i}: {e.sql_name()}"  # (the fused-chain cache keys a Project by its output names)
+            hidden.append(Alias(e, name))
+            orders.append(SortOrder(ColRef(name), asc, nf))
+    if not hidden:
+        return build_sort(plan, orders)
+    return Project(build_sort(Project(plan.child, plan.exprs + hidden), orders), [ColRef(n) for n in names])
 
 
 def _bind_grouped(exprs, group, plan):

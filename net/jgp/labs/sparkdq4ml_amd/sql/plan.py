@@ -13,13 +13,13 @@ from typing import List, Optional, Sequence, Tuple
 
 import torch
 
-from .expressions import (Alias, AnalysisException, ColRef, EvalContext, Expr, UdfCall)
+from .expressions import (Alias, AnalysisException, ColRef, EvalContext, Expr, SortOrder, UdfCall)
 from .skey import expr_key, exprs_key, intern
 from .table import ColumnData, Table
-from .types import BooleanType, StructField, StructType
+from .types import BooleanType, StructField, StructType, VectorUDT
 
 __all__ = ["LogicalPlan", "LocalRelation", "CsvScanRelation", "Project", "Filter", "Limit", "Union", "Aggregate", "Deduplicate",
-           "execute", "prune_columns"]
+           "Sort", "build_sort", "execute", "prune_columns"]
 
 
 class LogicalPlan:
@@ -418,10 +418,90 @@ class Deduplicate(LogicalPlan):
         return f"Deduplicate [{', '.join(self.subset)}]"
 
 
+class Sort(LogicalPlan):
+    """``ORDER BY orders``: the child's live rows in the stable sorted order of ``orders``
+    (``SortOrder`` over column references of the child; ``build_sort`` puts a Project underneath
+    for anything else), the first order the most significant.  Doubles order as Spark orders them
+    (``-0.0 = 0.0``, every NaN one value above ``+inf``), strings by their dictionary codes.  The
+    result is compact: every column gathered by the permutation, no selection vector.  On a
+    data-parallel plan the node sorts this rank's rows."""
+
+    def __init__(self, child: LogicalPlan, orders: Sequence[SortOrder]):
+        self.child = child
+        cs = child.schema()
+        self.orders = []
+        for o in orders:
+            if not isinstance(o, SortOrder) or not isinstance(o.child, ColRef):
+                raise AnalysisException(f"Sort takes orders over column references, got {o.sql_name()}")
+            f = o.child._field(cs)
+            _orderable(o, f.dataType)
+            self.orders.append(SortOrder(ColRef(f.name), o.ascending, o.nulls_first))
+
+    def children(self):
+        return [self.child]
+
+    def skey(self):
+        k = self._skey
+        if k == 0:
+            ck = self.child.skey()
+            ek = exprs_key(self.orders) if ck is not None else None
+            k = self._skey = intern(("Sort", ck, ek)) if ek is not None else None
+        return k
+
+    def schema(self):
+        return self.child.schema()
+
+    def references(self) -> set:
+        return {o.child.name for o in self.orders}
+
+    def _compute(self, session):
+        from .aggregates import sort_table
+
+        return sort_table(execute(self.child, session), [(o.child.name, o.ascending, o.nulls_first) for o in self.orders])
+
+    def _label(self):
+        return "Sort [" + ", ".join(o.sql_name() for o in self.orders) + "]"
+
+
+def _orderable(o: SortOrder, dt) -> None:
+    if isinstance(dt, VectorUDT):
+        raise AnalysisException(f"cannot resolve '{o.sql_name()}' due to data type mismatch: cannot sort data type "
+                                f"{dt.simpleString()}: it is not an orderable data type")
+
+
+def build_sort(child: LogicalPlan, orders: Sequence[SortOrder], global_sort: bool = True) -> LogicalPlan:
+    """``Sort`` over ``child``.  An order that is not a plain column reference is computed by a
+    ``Project`` underneath, under a hidden name, and dropped again above the ``Sort``.
+    ``global_sort``: the total order of ``orderBy`` / ``ORDER BY``, which a data-parallel (sharded)
+    input does not have yet; ``sortWithinPartitions`` sorts every rank's rows."""
+    from .aggregates import contains_aggregate
+
+    if global_sort and is_sharded(child):
+        raise AnalysisException("orderBy / ORDER BY over a data-parallel (sharded) input: a global sort across ranks is "
+                                "not implemented; sortWithinPartitions sorts the rows of every rank")
+    cs = child.schema()
+    names = cs.names
+    hidden, out = [], []
+    for i, o in enumerate(orders):
+        if contains_aggregate(o.child):
+            raise AnalysisException(f"aggregate functions are not allowed in a sort order, but found {o.child.sql_name()}")
+        _orderable(o, o.child.data_type(cs))
+        if isinstance(o.child, ColRef):
+            out.append(o)
+        else:
+            name = f"_sort_key_{i}: {o.child.sql_name()}"  # (the fused-chain cache keys a Project by its output names)
+            hidden.append(Alias(o.child, name))
+            out.append(SortOrder(ColRef(name), o.ascending, o.nulls_first))
+    if not hidden:
+        return Sort(child, out)
+    return Project(Sort(Project(child, [ColRef(n) for n in names] + hidden), out), [ColRef(n) for n in names])
+
+
 def prune_columns(plan: LogicalPlan, required) -> LogicalPlan:
     """Catalyst-style ColumnPruning: a plan whose Projects compute only the output columns some
     consumer needs (``required``: column names, case-insensitive; None = all).  Filters keep
-    what their condition references; leaves, Limit and Union are not pruned through.  Unchanged
+    what their condition references, Sorts what their orders reference; leaves, Limit and Union are
+    not pruned through.  Unchanged
     subtrees are returned as-is, so their memoized tables are reused.
 
     Spark's ``LinearRegression.train`` selects (label, features, weight) before aggregating and the
@@ -448,6 +528,13 @@ def prune_columns(plan: LogicalPlan, required) -> LogicalPlan:
             # Project/Filter chain evaluates them in registers and never stores them
             return Project(f, [ColRef(n) for n in names if n.lower() in req])
         return f
+    if isinstance(plan, Sort):
+        child = prune_columns(plan.child, req | {r.lower() for r in plan.references()})
+        srt = plan if child is plan.child else Sort(child, plan.orders)
+        names = srt.schema().names
+        if any(n.lower() not in req for n in names):  # columns only the orders need
+            return Project(srt, [ColRef(n) for n in names if n.lower() in req])
+        return srt
     if isinstance(plan, Aggregate):
         # exactly the key and input references pass through, whatever the consumer asks for
         child = prune_columns(plan.child, plan.references())
