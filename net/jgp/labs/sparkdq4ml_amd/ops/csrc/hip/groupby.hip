@@ -23,14 +23,13 @@
 #include <stdexcept>
 
 #include "common.h"
+#include "hashtable.h"
 #include "keys.h"
 
 namespace dq4ml {
 namespace {
 
 static_assert(kGroupRun == kRawRun, "the run loaders of keys.h read kGroupRun rows");
-
-constexpr u64 kEmpty = ~0ull;
 
 __device__ __forceinline__ int word_kind(int op, int w) {
   switch (op) {
@@ -247,32 +246,6 @@ __global__ __launch_bounds__(kGroupThreads) void group_direct_kernel(GroupKeyCol
     }
     store_gids(gid, r0, a.n, g);
   }
-}
-
-__device__ __forceinline__ u64 home_slot(u64 key, u64 mask) { return ((key * 0x9E3779B97F4A7C15ull) >> 20) & mask; }
-
-__device__ __forceinline__ u64 load_slot(const u64* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// state: [0] occupied slots, [1] overflow, [2] a null key was seen, [3] the all-ones key was seen
-__device__ __forceinline__ void table_insert(u64* table, u64 mask, u64* state, u64 key) {
-  u64 slot = home_slot(key, mask);
-  // a slot only ever changes from empty to a key, so a stale read costs one failed CAS at most;
-  // the bound ends the probe of a table that other waves filled after the overflow check
-  for (u64 i = 0; i <= mask; ++i) {
-    const u64 cur = load_slot(table + slot);
-    if (cur == key) return;
-    if (cur == kEmpty) {
-      const u64 old = atomicCAS(table + slot, kEmpty, key);
-      if (old == key) return;
-      if (old == kEmpty) {
-        const u64 c = atomicAdd(state, 1ull) + 1;
-        if (c > (mask + 1) / 2) atomicOr(state + 1, 1ull);
-        return;
-      }
-    }
-    slot = (slot + 1) & mask;
-  }
-  atomicOr(state + 1, 1ull);
 }
 
 __global__ __launch_bounds__(kGroupThreads) void group_hash_insert_kernel(GroupKeyCol a, u64* table, u64 mask, u64* state) {

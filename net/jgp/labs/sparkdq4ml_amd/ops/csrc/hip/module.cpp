@@ -17,6 +17,7 @@
 #include "quantile.h"
 #include "groupby.h"
 #include "sort.h"
+#include "join.h"
 #include "gram_wide.h"
 #include "gram_syrk.h"
 #include "wls_small.h"
@@ -327,6 +328,40 @@ PYBIND11_MODULE(_dq4ml_hip, m) {
     sort_pass(P<const unsigned long long>(keys_in), P<const unsigned>(idx_in), P<unsigned long long>(keys_out),
               P<unsigned>(idx_out), m_, digit, P<unsigned>(counts), stride, P<const unsigned long long>(hist_row),
               P<const unsigned>(base), blocks, as_stream(stream));
+  });
+  m.def("join_blocks", &join_blocks);
+  m.def("join_expand_blocks", &join_expand_blocks);
+  // rows per trip, output positions per expansion tile, left rows of a tile staged in LDS, largest table
+  m.def("join_limits", []() { return py::make_tuple(kJoinTrip, kJoinTile, kJoinLdsRows, kJoinMaxCapacity); });
+  auto join_key = [](uintptr_t col, int dt, uintptr_t valid, uintptr_t sel, int64_t n) {
+    JoinKeyCol a{};
+    a.col = P<const void>(col);
+    a.valid = P<const uint8_t>(valid);
+    a.sel = P<const uint8_t>(sel);
+    a.n = n;
+    a.dt = dt;
+    return a;
+  };
+  // table [capacity] u64 all ones; cnt / first [capacity + 1] u32 zeroed / i32 INT32_MAX; state [4] u64 zeroed
+  m.def("join_build", [join_key](uintptr_t col, int dt, uintptr_t valid, uintptr_t sel, int64_t n, uintptr_t table,
+                                 int64_t capacity, uintptr_t cnt, uintptr_t first, uintptr_t bslot, uintptr_t state, int blocks,
+                                 uintptr_t stream) {
+    join_build(join_key(col, dt, valid, sel, n), P<unsigned long long>(table), capacity, P<unsigned>(cnt), P<int>(first),
+               P<int>(bslot), P<unsigned long long>(state), blocks, as_stream(stream));
+  });
+  // mode: 0 inner, 1 outer, 2 full (marks matched [capacity + 1] u8), 3 semi (writes only mask [n] u8)
+  m.def("join_probe", [join_key](uintptr_t col, int dt, uintptr_t valid, uintptr_t sel, int64_t n, uintptr_t table,
+                                 int64_t capacity, uintptr_t cnt, int mode, uintptr_t pslot, uintptr_t pcnt, uintptr_t matched,
+                                 uintptr_t mask, int blocks, uintptr_t stream) {
+    join_probe(join_key(col, dt, valid, sel, n), P<const unsigned long long>(table), capacity, P<const unsigned>(cnt), mode,
+               P<int>(pslot), P<int>(pcnt), P<uint8_t>(matched), P<uint8_t>(mask), blocks, as_stream(stream));
+  });
+  // offsets [n_left + 1] i64; start [capacity + 1] / brow [nbrow] i32, or both 0 for unique right keys
+  m.def("join_expand", [](uintptr_t offsets, int64_t n_left, int64_t total, uintptr_t pslot, uintptr_t start, uintptr_t brow,
+                          int64_t nbrow, uintptr_t first, int64_t capacity, uintptr_t li, uintptr_t ri, int blocks,
+                          uintptr_t stream) {
+    join_expand(P<const int64_t>(offsets), n_left, total, P<const int>(pslot), P<const int>(start), P<const int>(brow), nbrow,
+                P<const int>(first), capacity, P<int64_t>(li), P<int64_t>(ri), blocks, as_stream(stream));
   });
   m.def("gram_window_fold", [](uintptr_t part, int64_t rows, int gw, uintptr_t flat, uintptr_t stream) {
     gram_window_fold(P<const double>(part), rows, gw, P<double>(flat), as_stream(stream));

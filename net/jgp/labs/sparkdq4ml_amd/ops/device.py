@@ -681,6 +681,126 @@ def sort_permutation(cols, valids, sel, ascending, nulls_first, blocks: Optional
     return idx[cur].to(torch.int64) & 0x7FFFFFFF  # (the top bit carried the last column's null flag)
 
 
+# ------------------------------------------------------------------------------------------
+# hash equi-join (csrc/hip/join.hip); the contract and its numpy twin are in ops/join.py
+# ------------------------------------------------------------------------------------------
+_JOIN_MODES = {"inner": 0, "left_outer": 1, "full_outer": 2, "semi": 3}
+
+
+class _JoinBuild:
+    """The build side of one join: the table, ``cnt`` / ``first`` per slot (the extra slot
+    ``capacity`` belongs to the out-of-band INT64_MAX key), ``bslot`` per right row, and the one
+    host read of the state vector."""
+
+    def __init__(self, h, rkey, rvalid, rsel, capacity: Optional[int], blocks: Optional[int]):
+        from . import join as jo
+
+        assert tuple(h.join_limits()) == jo.join_limits(), "join.py / join.h constants differ"
+        nr = int(rkey.numel())
+        dev = rkey.device
+        self.n = nr
+        self.capacity = cap = int(capacity) if capacity else jo.join_capacity(nr)
+        self.table = torch.full((cap,), -1, dtype=torch.int64, device=dev)
+        self.cnt = torch.zeros(cap + 1, dtype=torch.int32, device=dev)
+        self.first = torch.full((cap + 1,), (1 << 31) - 1, dtype=torch.int32, device=dev)
+        self.bslot = torch.empty(nr, dtype=torch.int32, device=dev)
+        state = torch.zeros(4, dtype=torch.int64, device=dev)
+        nb = int(blocks) if blocks else int(h.join_blocks(nr))
+        h.join_build(rkey.data_ptr(), dtype_code(rkey), _ptr(rvalid), _ptr(rsel), nr, self.table.data_ptr(), cap,
+                     self.cnt.data_ptr(), self.first.data_ptr(), self.bslot.data_ptr(), state.data_ptr(), nb, _stream())
+        in_table, inserted, overflow, has_top = (int(v) for v in state.tolist())  # also tells whether a sort is needed
+        if overflow or in_table >= cap:
+            raise RuntimeError(f"join: a hash table of {cap} slots cannot hold the right side's distinct keys plus one "
+                               f"empty slot")
+        self.distinct = in_table + (1 if has_top else 0)
+        self.inserted = inserted
+        self.unique = inserted == self.distinct  # every right key is unique: first[slot] is the slot's only row
+        self.start = self.brow = None
+
+    def layout(self, blocks: Optional[int]) -> None:
+        """General case: ``brow``, the right rows grouped by slot and stable in row order (the
+        stable radix sort of ``bslot`` over its non-negative entries), and ``start``, the exclusive
+        prefix sum of ``cnt``."""
+        if self.unique or self.brow is not None:
+            return
+        self.start = (torch.cumsum(self.cnt, 0, dtype=torch.int64) - self.cnt).to(torch.int32)
+        self.brow = sort_permutation([self.bslot], [None], self.bslot >= 0, [True], [True], blocks).to(torch.int32)
+
+
+def _join_sides(lkey, rkey, lvalid, rvalid, lsel, rsel):
+    _check_dev(lkey, rkey, lvalid, rvalid, lsel, rsel)
+    nl, nr = int(lkey.numel()), int(rkey.numel())
+    lkey, rkey = _group_col(lkey, nl, "join"), _group_col(rkey, nr, "join")
+    lvalid, lsel = _mask_u8(lvalid, nl, "the left validity mask", "join"), _mask_u8(lsel, nl, "the left selection", "join")
+    rvalid, rsel = _mask_u8(rvalid, nr, "the right validity mask", "join"), _mask_u8(rsel, nr, "the right selection", "join")
+    return lkey, rkey, lvalid, rvalid, lsel, rsel
+
+
+def join_pairs(lkey, rkey, lvalid, rvalid, lsel, rsel, how: str, capacity: Optional[int] = None, blocks: Optional[int] = None,
+               stats: Optional[list] = None):
+    """Device form of ``ops.join.join_pairs`` (arguments already checked).  Two host reads: the
+    build's state vector, and the total of the output offsets, which sizes the result."""
+    h = native.hip()
+    lkey, rkey, lvalid, rvalid, lsel, rsel = _join_sides(lkey, rkey, lvalid, rvalid, lsel, rsel)
+    nl, dev = int(lkey.numel()), lkey.device
+    b = _JoinBuild(h, rkey, rvalid, rsel, capacity, blocks)
+    b.layout(blocks)
+    st = _stream()
+    mode = _JOIN_MODES[how]
+    pslot = torch.empty(nl, dtype=torch.int32, device=dev)
+    pcnt = torch.empty(nl, dtype=torch.int32, device=dev)
+    matched = torch.zeros(b.capacity + 1, dtype=torch.uint8, device=dev) if how == "full_outer" else None
+    nb = int(blocks) if blocks else int(h.join_blocks(nl))
+    h.join_probe(lkey.data_ptr(), dtype_code(lkey), _ptr(lvalid), _ptr(lsel), nl, b.table.data_ptr(), b.capacity,
+                 b.cnt.data_ptr(), mode, pslot.data_ptr(), pcnt.data_ptr(), _ptr(matched), 0, nb, st)
+    offsets = torch.zeros(nl + 1, dtype=torch.int64, device=dev)
+    if nl > 0:
+        torch.cumsum(pcnt, 0, dtype=torch.int64, out=offsets[1:])
+    extra = None
+    if how == "full_outer":  # the live right rows that no left row matched (a null key: bslot < 0), in row order
+        un = (b.bslot < 0) | (matched[b.bslot.clamp(min=0).to(torch.int64)] == 0)
+        if rsel is not None:
+            un &= rsel.to(torch.bool)
+        extra = compact_indices(un) if b.n > 0 else torch.empty(0, dtype=torch.int64, device=dev)
+    total = int(offsets[nl].item())  # the one host read that sizes the output
+    pairs = total + (0 if extra is None else int(extra.numel()))
+    if pairs >= 1 << 31:
+        from .join import _too_many
+
+        raise _too_many(pairs)
+    li = torch.empty(total, dtype=torch.int64, device=dev)
+    ri = torch.empty(total, dtype=torch.int64, device=dev)
+    if total > 0:
+        nbe = int(blocks) if blocks else int(h.join_expand_blocks(total))
+        h.join_expand(offsets.data_ptr(), nl, total, pslot.data_ptr(), _ptr(b.start), _ptr(b.brow),
+                      0 if b.brow is None else int(b.brow.numel()), b.first.data_ptr(), b.capacity, li.data_ptr(),
+                      ri.data_ptr(), nbe, st)
+    if extra is not None and extra.numel():
+        li = torch.cat([li, torch.full_like(extra, -1)])
+        ri = torch.cat([ri, extra])
+    if stats is not None:
+        stats.append({"distinct": b.distinct, "unique_build": b.unique, "capacity": b.capacity, "pairs": pairs})
+    return li, ri
+
+
+def join_mask(lkey, rkey, lvalid, rvalid, lsel, rsel, capacity: Optional[int] = None, blocks: Optional[int] = None,
+              stats: Optional[list] = None) -> torch.Tensor:
+    """Device form of ``ops.join.join_mask``: the build pass and a probe pass that writes only the
+    mask (no layout, no expansion)."""
+    h = native.hip()
+    lkey, rkey, lvalid, rvalid, lsel, rsel = _join_sides(lkey, rkey, lvalid, rvalid, lsel, rsel)
+    nl, dev = int(lkey.numel()), lkey.device
+    b = _JoinBuild(h, rkey, rvalid, rsel, capacity, blocks)
+    mask = torch.empty(nl, dtype=torch.uint8, device=dev)
+    nb = int(blocks) if blocks else int(h.join_blocks(nl))
+    h.join_probe(lkey.data_ptr(), dtype_code(lkey), _ptr(lvalid), _ptr(lsel), nl, b.table.data_ptr(), b.capacity,
+                 b.cnt.data_ptr(), _JOIN_MODES["semi"], 0, 0, 0, mask.data_ptr(), nb, _stream())
+    mask = mask.view(torch.bool)
+    if stats is not None:
+        stats.append({"distinct": b.distinct, "unique_build": b.unique, "capacity": b.capacity, "pairs": int(mask.sum().item())})
+    return mask
+
+
 def gram_skinny_cols(parts: List[torch.Tensor], y, w, sel, blocks: Optional[int] = None):
     """f64 WLS statistics of a narrow (d <= 8) VectorAssembler output straight from its SOURCE
     columns (any of f64/f32/bf16/int32/int64/bool, mixed): the assembled [d, n] f64 matrix is

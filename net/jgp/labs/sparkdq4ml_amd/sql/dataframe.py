@@ -333,6 +333,49 @@ class DataFrame:
 
     unionAll = union
 
+    def join(self, other: "DataFrame", on=None, how: str = "inner") -> "DataFrame":
+        """Equi-join with ``other``.  ``on``: a column name or a list of names both frames have
+        (Spark's USING join: the key columns come out once, then this frame's other columns, then
+        ``other``'s), or a Column that is a conjunction of equalities between one column of each
+        side (both sides keep their columns; a name must resolve on one side only, since ``df.a``
+        carries no lineage here).  ``how``: inner, left / leftouter / left_outer, right / rightouter
+        / right_outer, outer / full / fullouter / full_outer, semi / leftsemi / left_semi, anti /
+        leftanti / left_anti (case and underscores ignored).
+
+        ``other`` is the build side of the hash join: put the smaller frame there.  Keys follow
+        Spark (``-0.0 = 0.0``, NaN joins NaN, null matches nothing; int with long compares as long,
+        anything with float or double as double).  The row order is defined: this frame's rows in
+        row order, the matches of one row in ``other``'s row order, then (full) ``other``'s
+        unmatched rows; a right join is the left join of the swapped sides, so its order is
+        right-major.  Semi and anti joins only narrow the selection vector.
+
+        Deviation from Spark: a non-key column name on both sides raises ``AnalysisException``
+        (rename one with ``withColumnRenamed``); cross joins, other ``on`` conditions and joins
+        that need a shuffle across data-parallel ranks are not implemented."""
+        from .joins import condition_keys, normalize_how, using_keys
+        from .plan import Join
+
+        if not isinstance(other, DataFrame):
+            raise TypeError("join: other must be a DataFrame")
+        how = normalize_how(how)
+        if on is None:
+            raise AnalysisException("cross joins are not implemented: pass the join key(s) as on=")
+        ls, rs = self.schema, other.schema
+        if isinstance(on, Column):
+            keys, using = condition_keys(ls, rs, to_expr(on)), False
+        else:
+            names = [on] if isinstance(on, str) else list(on)
+            if names and all(isinstance(c, Column) for c in names):
+                keys, using = [k for c in names for k in condition_keys(ls, rs, to_expr(c))], False
+            elif all(isinstance(c, str) for c in names):
+                keys, using = using_keys(ls, rs, names), True
+            else:
+                raise TypeError("join: on must be a column name, a list of names, or a Column")
+        return self._with(Join(self._plan, other._plan, keys, how, using))
+
+    def crossJoin(self, other: "DataFrame") -> "DataFrame":
+        raise AnalysisException("cross joins are not implemented")
+
     @property
     def na(self):
         return DataFrameNaFunctions(self)

@@ -6,7 +6,9 @@
 (``DataQuality4MachineLearningApp.java:77-78,89-90``) — projections with ``CAST``, aliases with or
 without ``AS``, single-table ``FROM`` of a temp view, ``WHERE`` with arithmetic / comparisons /
 boolean logic / ``IS [NOT] NULL`` / ``BETWEEN`` / ``IN``, ``CASE WHEN``, ``GROUP BY``,
-``ORDER BY expr [ASC|DESC] [NULLS FIRST|NULLS LAST]``, ``LIMIT``, UDF and built-in function calls.  It produces the same plan nodes as the DataFrame API.
+``ORDER BY expr [ASC|DESC] [NULLS FIRST|NULLS LAST]``, ``LIMIT``,
+``FROM a [INNER | LEFT [OUTER] | RIGHT [OUTER] | FULL [OUTER] | LEFT SEMI | LEFT ANTI] JOIN b USING (c1, ...)``
+(chainable, left-associative), UDF and built-in function calls.  It produces the same plan nodes as the DataFrame API.
 """
 from __future__ import annotations
 
@@ -17,7 +19,7 @@ from .expressions import (Alias, AnalysisException, BinOp, CaseWhen, Cast, ColRe
                           Expr, If, IsNotNull, IsNull, Lit, Neg, Not, SortOrder, UdfCall)
 from .aggregates import AggExpr, build_aggregate, contains_aggregate
 from .fn import MathFn, BUILTIN_MATH
-from .plan import Aggregate, Filter, Limit, Project, build_sort, output_name
+from .plan import Aggregate, Filter, Join, Limit, Project, build_sort, output_name
 from .skey import expr_key
 
 __all__ = ["parse_expression", "parse_select_item", "plan_sql", "ParseException"]
@@ -38,6 +40,12 @@ _TOKEN = re.compile(r"""
 
 _KEYWORDS = {"select", "from", "where", "as", "and", "or", "not", "cast", "is", "null", "true", "false",
              "case", "when", "then", "else", "end", "limit", "between", "in", "distinct", "like", "group", "by", "order"}
+
+
+_JOIN_WORDS = {"inner", "left", "right", "full", "outer", "semi", "anti", "cross", "join", "on", "using"}
+_JOIN_TYPES = {(): "inner", ("inner",): "inner", ("left",): "left_outer", ("left", "outer"): "left_outer",
+               ("right",): "right_outer", ("right", "outer"): "right_outer", ("full",): "full_outer",
+               ("full", "outer"): "full_outer", ("left", "semi"): "left_semi", ("left", "anti"): "left_anti"}
 
 
 def _tokenize(text: str) -> List[Tuple[str, str]]:
@@ -101,12 +109,23 @@ class _Parser:
         distinct = bool(self.accept("kw", "distinct"))
         items = self.select_list()
         self.expect("kw", "from")
-        tname = self.expect("ident")[1]
-        alias = None
-        if self.accept("kw", "as"):
-            alias = self.expect("ident")[1]
-        elif self.peek()[0] == "ident":
-            alias = self.next()[1]
+        tname, alias = self.relation()
+        joins = []
+        while True:
+            how = self.join_type()
+            if how is None:
+                break
+            jname, jalias = self.relation()
+            if self.accept("ident", "on"):
+                raise AnalysisException("JOIN ... ON is not implemented; use USING (c1, ...) with the key columns' names")
+            if not self.accept("ident", "using"):
+                raise AnalysisException("cross joins are not implemented: a JOIN takes USING (c1, ...)")
+            self.expect("op", "(")
+            cols = [self.expect("ident")[1]]
+            while self.accept("op", ","):
+                cols.append(self.expect("ident")[1])
+            self.expect("op", ")")
+            joins.append((how, jname, jalias, cols))
         where = None
         if self.accept("kw", "where"):
             where = self.expr()
@@ -127,6 +146,8 @@ class _Parser:
             limit = int(self.expect("num")[1])
         self.expect("eof")
         quals = {tname.lower()} | ({alias.lower()} if alias else set())
+        for _, jname, jalias, _ in joins:  # every name of the joined schema is unambiguous (a duplicate raises)
+            quals |= {jname.lower()} | ({jalias.lower()} if jalias else set())
         items = [(_strip_qual(e, quals)) for e in items]
         if where is not None:
             where = _strip_qual(where, quals)
@@ -134,7 +155,34 @@ class _Parser:
             group = [_strip_qual(e, quals) for e in group]
         if order is not None:
             order = [(_strip_qual(e, quals), asc, nf) for e, asc, nf in order]
-        return items, tname, where, limit, distinct, group, order
+        return items, tname, where, limit, distinct, group, order, joins
+
+    def relation(self):
+        """``view [[AS] alias]`` (a join word is never an alias)."""
+        name = self.expect("ident")[1]
+        alias = None
+        if self.accept("kw", "as"):
+            alias = self.expect("ident")[1]
+        elif self.peek()[0] == "ident" and self.peek()[1].lower() not in _JOIN_WORDS:
+            alias = self.next()[1]
+        return name, alias
+
+    def join_type(self):
+        """``[INNER | LEFT [OUTER] | RIGHT [OUTER] | FULL [OUTER] | LEFT SEMI | LEFT ANTI | CROSS]
+        JOIN`` -> the canonical join type, or None when no JOIN follows."""
+        t = self.peek()
+        if t[0] != "ident" or t[1].lower() not in _JOIN_WORDS or t[1].lower() in ("on", "using"):
+            return None
+        words = []
+        while self.peek()[0] == "ident" and self.peek()[1].lower() in _JOIN_WORDS and self.peek()[1].lower() != "join":
+            words.append(self.next()[1].lower())
+        self.expect("ident", "join")
+        how = _JOIN_TYPES.get(tuple(words))
+        if how is None:
+            if words == ["cross"]:
+                raise AnalysisException("cross joins are not implemented")
+            raise ParseException(f"\nmismatched input '{' '.join(words)} join': not a join type")
+        return how
 
     def order_item(self):
         """``expr [ASC|DESC] [NULLS FIRST|NULLS LAST]`` -> (expr, ascending, nulls_first or None)."""
@@ -376,10 +424,22 @@ def _bind_query(syntax, text: str, session):
     replaced between two runs of the same text binds to the new plan).  Expression trees are
     immutable once parsed, so plans may share them; a statement bound over a view of the same
     structure (sql/skey.py) reuses the analyzed nodes (fresh copies: no result is shared)."""
-    items, tname, where, limit, distinct, group, order = syntax
-    plan = session.catalog._views.get(tname.lower())
-    if plan is None:
-        raise AnalysisException(f"Table or view not found: {tname}; line 1 pos {text.lower().find(tname.lower())}")
+    items, tname, where, limit, distinct, group, order, joins = syntax
+
+    def view(name):
+        p = session.catalog._views.get(name.lower())
+        if p is None:
+            raise AnalysisException(f"Table or view not found: {name}; line 1 pos {text.lower().find(name.lower())}")
+        return p
+
+    plan = view(tname)
+    if joins:  # (the template cache below walks a single .child chain: a statement with a JOIN is bound anew)
+        from .joins import using_keys
+
+        for how, jname, _, cols in joins:  # left-associative
+            right = view(jname)
+            plan = Join(plan, right, using_keys(plan.schema(), right.schema(), cols), how, True)
+        return _bind_new(items, where, limit, plan, distinct, group, order)
     vk = plan.skey()
     key = (text, vk) if vk is not None else None
     tmpl = _BOUND.get(key) if key is not None else None

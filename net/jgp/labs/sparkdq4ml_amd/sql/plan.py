@@ -18,7 +18,7 @@ from .skey import expr_key, exprs_key, intern
 from .table import ColumnData, Table
 from .types import BooleanType, StructField, StructType, VectorUDT
 
-__all__ = ["LogicalPlan", "LocalRelation", "CsvScanRelation", "Project", "Filter", "Limit", "Union", "Aggregate", "Deduplicate",
+__all__ = ["LogicalPlan", "LocalRelation", "CsvScanRelation", "Project", "Filter", "Limit", "Union", "Join", "Aggregate", "Deduplicate",
            "Sort", "build_sort", "execute", "prune_columns"]
 
 
@@ -335,6 +335,56 @@ class Union(LogicalPlan):
         return Table(a.schema, cols, a.nrows + b.nrows, None, a.device)
 
 
+class Join(LogicalPlan):
+    """Equi-join of ``left`` and ``right`` on ``keys`` = ``(left column, right column)`` pairs;
+    ``how`` one of inner / left_outer / right_outer / full_outer / left_semi / left_anti
+    (``sql/joins.py``).  ``using``: the key columns come out once (Spark's USING join), else both
+    sides keep all their columns.  The right child is the build side of the hash join: the smaller
+    table belongs there.  The result rows come in a defined order: left rows in row order, the
+    matches of one left row in right row order (``right_outer``: right-major).  On a data-parallel
+    plan a sharded left joins a right that every rank holds whole (an ``Aggregate`` result, a
+    replicated relation) for inner / left_outer / left_semi / left_anti, and the result is sharded
+    like the left; anything else would need a shuffle across ranks and raises."""
+
+    def __init__(self, left: LogicalPlan, right: LogicalPlan, keys: Sequence[Tuple[str, str]], how: str = "inner",
+                 using: bool = True):
+        from .joins import join_schema
+
+        self.left, self.right = left, right
+        self.keys = [(str(l), str(r)) for l, r in keys]
+        self.how, self.using = how, bool(using)
+        self._schema = join_schema(left.schema(), right.schema(), self.keys, how, self.using)
+        ls, rs = is_sharded(left), is_sharded(right)
+        if rs or (ls and how not in ("inner", "left_outer", "left_semi", "left_anti")):
+            raise AnalysisException(f"a {how} join of a {'sharded' if ls else 'replicated'} left with a "
+                                    f"{'sharded' if rs else 'replicated'} right over data-parallel ranks: a shuffle join across "
+                                    f"ranks is not implemented (a sharded left joins a right that every rank holds whole, for "
+                                    f"inner / left / semi / anti)")
+
+    def children(self):
+        return [self.left, self.right]
+
+    def skey(self):
+        k = self._skey
+        if k == 0:
+            lk, rk = self.left.skey(), self.right.skey()
+            k = self._skey = (intern(("Join", lk, rk, tuple(self.keys), self.how, self.using))
+                              if lk is not None and rk is not None else None)
+        return k
+
+    def schema(self):
+        return self._schema
+
+    def _compute(self, session):
+        from .joins import join_table
+
+        return join_table(execute(self.left, session), execute(self.right, session), self.keys, self.how, self.using,
+                          self._schema)
+
+    def _label(self):
+        return f"Join {self.how} [{', '.join(l if l == r else f'{l} = {r}' for l, r in self.keys)}]"
+
+
 class Aggregate(LogicalPlan):
     """``GROUP BY keys`` with the aggregates ``aggs`` = ``(fn, input column or None, output name)``
     (``fn`` one of count / sum / avg / min / max; input None: ``count(*)``).  Keys and inputs are
@@ -500,7 +550,7 @@ def build_sort(child: LogicalPlan, orders: Sequence[SortOrder], global_sort: boo
 def prune_columns(plan: LogicalPlan, required) -> LogicalPlan:
     """Catalyst-style ColumnPruning: a plan whose Projects compute only the output columns some
     consumer needs (``required``: column names, case-insensitive; None = all).  Filters keep
-    what their condition references, Sorts what their orders reference; leaves, Limit and Union are
+    what their condition references, Sorts what their orders reference; leaves, Limit, Union and Join are
     not pruned through.  Unchanged
     subtrees are returned as-is, so their memoized tables are reused.
 
