@@ -30,6 +30,23 @@ constexpr int kWave = 64;  // CDNA wavefront
   } while (0)
 
 inline hipStream_t as_stream(uintptr_t s) { return reinterpret_cast<hipStream_t>(s); }
+
+// occupancy-sized grid of a grid-strided kernel: per_cu blocks on every CU, capped by the `want`
+// blocks that the work can fill (at least 1)
+inline int grid_for(int per_cu, int64_t want) {
+  int dev = 0, cus = 0;
+  DQ_HIP_CHECK(hipGetDevice(&dev));
+  DQ_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+  const int64_t full = (int64_t)per_cu * (cus < 1 ? 1 : cus);
+  if (want < 1) want = 1;
+  return (int)(want < full ? want : full);
+}
+
+// launcher-side check of an open-addressing table's capacity (hashtable.h): a power of two in
+// [2, max]; the caller words the message, since each names its own bound
+inline void check_table(int64_t capacity, int64_t max, const char* msg) {
+  if (capacity < 2 || (capacity & (capacity - 1)) != 0 || capacity > max) throw std::invalid_argument(msg);
+}
 #endif
 
 // dtype codes shared with the python side (ops/device.py)

@@ -7,6 +7,8 @@
 
 #include <cstdint>
 
+#include "keys.h"
+
 namespace dq4ml {
 
 constexpr int kGroupRun = 4;  // consecutive rows per thread and trip
@@ -49,15 +51,6 @@ struct GroupAggArgs {
   int G, S, words;
 };
 
-// one key column
-struct GroupKeyCol {
-  const void* col;
-  const uint8_t* valid;
-  const uint8_t* sel;
-  int64_t n;
-  int dt;
-};
-
 __host__ __device__ constexpr int group_op_words(int op) { return op == GOP_SUM_F ? kGroupSumWords : 1; }
 
 // occupancy-sized grid for n rows
@@ -65,12 +58,12 @@ int group_blocks(int64_t n);
 // acc is [G, words] u64, initialised by the caller to each word's identity
 void group_agg(const GroupAggArgs& a, unsigned long long* acc, int blocks, hipStream_t st);
 // gid[r] = -1 (dead), 0 (null key) or key - base + 1; values outside [base, base + span) are dead
-void group_encode_direct(const GroupKeyCol& a, int64_t base, int64_t span, int* gid, int blocks, hipStream_t st);
+void group_encode_direct(const KeyCol& a, int64_t base, int64_t span, int* gid, int blocks, hipStream_t st);
 // table: capacity u64 slots, all ones on entry; state: [occupied, overflow, has_null, has_top] zeroed
-void group_hash_insert(const GroupKeyCol& a, unsigned long long* table, int64_t capacity, unsigned long long* state,
+void group_hash_insert(const KeyCol& a, unsigned long long* table, int64_t capacity, unsigned long long* state,
                        int blocks, hipStream_t st);
 // row -> slot -> slot_gid[slot]; null keys get 0, the all-ones key (out of band) gets top_gid
-void group_hash_lookup(const GroupKeyCol& a, const unsigned long long* table, int64_t capacity, const int* slot_gid,
+void group_hash_lookup(const KeyCol& a, const unsigned long long* table, int64_t capacity, const int* slot_gid,
                        int top_gid, int* gid, int blocks, hipStream_t st);
 
 }  // namespace dq4ml

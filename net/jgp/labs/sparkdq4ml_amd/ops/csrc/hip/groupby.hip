@@ -163,13 +163,12 @@ __global__ __launch_bounds__(kGroupThreads) void group_agg_kernel(GroupAggArgs a
           case GOP_MAX: emit(acc, a.words, on, g[j], w0, GK_MAX, order_key(raw[j], isf, false), lane); break;
           case GOP_FIRST: emit(acc, a.words, on, g[j], w0, GK_MIN, (u64)(a.row_offset + r0 + j), lane); break;
           case GOP_ABSMAX: {
-            const double x = isf ? __longlong_as_double((long long)raw[j]) : (double)(long long)raw[j];
-            const u64 b = (u64)__double_as_longlong(x) & ~kSign;
+            const u64 b = (u64)__double_as_longlong(raw_as_f64(raw[j], isf)) & ~kSign;
             emit(acc, a.words, on && b < kInfBits, g[j], w0, GK_MAX, b, lane);
             break;
           }
           default: {  // GOP_SUM_F
-            const double x = isf ? __longlong_as_double((long long)raw[j]) : (double)(long long)raw[j];
+            const double x = raw_as_f64(raw[j], isf);
             const u64 b = (u64)__double_as_longlong(x);
             const bool finite = (b & ~kSign) < kInfBits;
             const u64 flag = finite ? 0ull : ((b & ~kSign) > kInfBits ? 1ull : ((b & kSign) ? 4ull : 2ull));
@@ -197,39 +196,7 @@ __global__ __launch_bounds__(kGroupThreads) void group_agg_kernel(GroupAggArgs a
   }
 }
 
-// the key of row j of a run: `ins` rows carry a key that lives in the table
-struct KeyRun {
-  u64 key[kGroupRun];
-  unsigned live, valid;
-};
-
-__device__ __forceinline__ KeyRun load_keys(const GroupKeyCol& a, int64_t r0) {
-  KeyRun k;
-  u64 raw[kGroupRun];
-  load_run(a.col, a.dt, r0, a.n, raw);
-  const bool isf = is_float_dt(a.dt);
-#pragma unroll
-  for (int j = 0; j < kGroupRun; ++j) k.key[j] = order_key(raw[j], isf, true);
-  k.live = mask_run(a.sel, r0, a.n);
-  k.valid = k.live;
-  if (a.valid != nullptr) k.valid &= mask_run(a.valid, r0, a.n);
-  return k;
-}
-
-__device__ __forceinline__ void store_gids(int* gid, int64_t r0, int64_t n, const int g[kGroupRun]) {
-  if (r0 + kGroupRun <= n && ((reinterpret_cast<uintptr_t>(gid) & 15) == 0)) {
-    i32x4 v;
-#pragma unroll
-    for (int j = 0; j < kGroupRun; ++j) v[j] = g[j];
-    *reinterpret_cast<i32x4*>(gid + r0) = v;
-    return;
-  }
-#pragma unroll
-  for (int j = 0; j < kGroupRun; ++j)
-    if (r0 + j < n) gid[r0 + j] = g[j];
-}
-
-__global__ __launch_bounds__(kGroupThreads) void group_direct_kernel(GroupKeyCol a, int64_t base, int64_t span, int* gid) {
+__global__ __launch_bounds__(kGroupThreads) void group_direct_kernel(KeyCol a, int64_t base, int64_t span, int* gid) {
   const int64_t trips = (a.n + kGroupTrip - 1) / kGroupTrip;
   for (int64_t t = blockIdx.x; t < trips; t += gridDim.x) {
     const int64_t r0 = t * kGroupTrip + (int64_t)threadIdx.x * kGroupRun;
@@ -244,11 +211,11 @@ __global__ __launch_bounds__(kGroupThreads) void group_direct_kernel(GroupKeyCol
       const u64 off = raw[j] - (u64)base;  // (unsigned: a value below base wraps far past span)
       g[j] = !((live >> j) & 1u) ? -1 : (!((valid >> j) & 1u) ? 0 : (off < (u64)span ? (int)off + 1 : -1));
     }
-    store_gids(gid, r0, a.n, g);
+    store_run(gid, r0, a.n, g);
   }
 }
 
-__global__ __launch_bounds__(kGroupThreads) void group_hash_insert_kernel(GroupKeyCol a, u64* table, u64 mask, u64* state) {
+__global__ __launch_bounds__(kGroupThreads) void group_hash_insert_kernel(KeyCol a, u64* table, u64 mask, u64* state) {
   const int lane = threadIdx.x & (kWave - 1);
   const int64_t trips = (a.n + kGroupTrip - 1) / kGroupTrip;
   bool saw_null = false, saw_top = false;
@@ -277,18 +244,13 @@ __global__ __launch_bounds__(kGroupThreads) void group_hash_insert_kernel(GroupK
   if (saw_top) atomicOr(state + 3, 1ull);
 }
 
-__device__ __forceinline__ int table_find(const u64* table, u64 mask, const int* slot_gid, u64 key) {
-  u64 slot = home_slot(key, mask);
-  for (u64 i = 0; i <= mask; ++i) {
-    const u64 cur = gptr<u64>(table)[slot];
-    if (cur == key) return gptr<int>(slot_gid)[slot];
-    if (cur == kEmpty) return -1;
-    slot = (slot + 1) & mask;
-  }
-  return -1;
+// the group id of a key of a finished table, -1 when the key is absent
+__device__ __forceinline__ int gid_of(const u64* table, u64 mask, const int* slot_gid, u64 key) {
+  const int64_t slot = table_slot(table, mask, key);
+  return slot < 0 ? -1 : gptr<int>(slot_gid)[slot];
 }
 
-__global__ __launch_bounds__(kGroupThreads) void group_hash_lookup_kernel(GroupKeyCol a, const u64* table, u64 mask,
+__global__ __launch_bounds__(kGroupThreads) void group_hash_lookup_kernel(KeyCol a, const u64* table, u64 mask,
                                                                          const int* slot_gid, int top_gid, int* gid) {
   const int lane = threadIdx.x & (kWave - 1);
   const int64_t trips = (a.n + kGroupTrip - 1) / kGroupTrip;
@@ -307,43 +269,26 @@ __global__ __launch_bounds__(kGroupThreads) void group_hash_lookup_kernel(GroupK
         const int leader = __ffsll((long long)rem) - 1;
         const u64 k0 = __shfl(k.key[j], leader, kWave);
         int g0 = -1;
-        if (lane == leader) g0 = table_find(table, mask, slot_gid, k0);
+        if (lane == leader) g0 = gid_of(table, mask, slot_gid, k0);
         g0 = __builtin_amdgcn_readlane(g0, leader);
         if (need && k.key[j] == k0) res = g0, need = false;
       }
-      if (need) res = table_find(table, mask, slot_gid, k.key[j]);
+      if (need) res = gid_of(table, mask, slot_gid, k.key[j]);
       g[j] = res;
     }
-    store_gids(gid, r0, a.n, g);
+    store_run(gid, r0, a.n, g);
   }
 }
 
-void check_key(const GroupKeyCol& a, int blocks) {
-  if (a.n < 0) throw std::invalid_argument("group_encode: negative row count");
-  if (blocks < 1) throw std::invalid_argument("group_encode: blocks must be >= 1");
-  if (a.dt != DT_F64 && a.dt != DT_F32 && a.dt != DT_I32 && a.dt != DT_I64 && a.dt != DT_U8)
-    throw std::invalid_argument("group_encode: keys must be f64, f32, i32, i64 or u8");
-  if (a.col == nullptr && a.n > 0) throw std::invalid_argument("group_encode: null column");
-}
-
-void check_table(int64_t capacity) {
-  if (capacity < 2 || (capacity & (capacity - 1)) != 0 || capacity > ((int64_t)1 << 40))
-    throw std::invalid_argument("group_encode: the table capacity must be a power of two >= 2");
+void check_group_table(int64_t capacity) {
+  check_table(capacity, (int64_t)1 << 40, "group_encode: the table capacity must be a power of two >= 2");
 }
 
 }  // namespace
 
-int group_blocks(int64_t n) {
-  int dev = 0, cus = 0;
-  DQ_HIP_CHECK(hipGetDevice(&dev));
-  DQ_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  // 4 blocks of 4 waves per CU: the 32 KiB of LDS accumulators allow that many, and 16 to 48 bytes
-  // in flight per thread and slot cover the HBM latency
-  const int64_t full = 4 * (int64_t)(cus < 1 ? 1 : cus);
-  int64_t want = (n + kGroupTrip - 1) / kGroupTrip;
-  if (want < 1) want = 1;
-  return (int)(want < full ? want : full);
-}
+// 4 blocks of 4 waves per CU: the 32 KiB of LDS accumulators allow that many, and 16 to 48 bytes
+// in flight per thread and slot cover the HBM latency
+int group_blocks(int64_t n) { return grid_for(4, (n + kGroupTrip - 1) / kGroupTrip); }
 
 void group_agg(const GroupAggArgs& a, unsigned long long* acc, int blocks, hipStream_t st) {
   if (a.n < 0) throw std::invalid_argument("group_agg: negative row count");
@@ -361,8 +306,7 @@ void group_agg(const GroupAggArgs& a, unsigned long long* acc, int blocks, hipSt
     const bool reads = op != GOP_ROWS && op != GOP_FIRST && op != GOP_COUNT;
     if (reads) {
       const int dt = a.dt[s];
-      if (dt != DT_F64 && dt != DT_F32 && dt != DT_I32 && dt != DT_I64 && dt != DT_U8)
-        throw std::invalid_argument("group_agg: columns must be f64, f32, i32, i64 or u8");
+      if (!is_key_dt(dt)) throw std::invalid_argument("group_agg: columns must be f64, f32, i32, i64 or u8");
       if (a.col[s] == nullptr && a.n > 0) throw std::invalid_argument("group_agg: null column");
       if (op == GOP_SUM_I && (dt == DT_F64 || dt == DT_F32)) throw std::invalid_argument("group_agg: SUM_I of a float column");
     }
@@ -379,8 +323,8 @@ void group_agg(const GroupAggArgs& a, unsigned long long* acc, int blocks, hipSt
   DQ_HIP_CHECK(hipGetLastError());
 }
 
-void group_encode_direct(const GroupKeyCol& a, int64_t base, int64_t span, int* gid, int blocks, hipStream_t st) {
-  check_key(a, blocks);
+void group_encode_direct(const KeyCol& a, int64_t base, int64_t span, int* gid, int blocks, hipStream_t st) {
+  check_key_col(a, blocks, "group_encode");
   if (a.dt == DT_F64 || a.dt == DT_F32) throw std::invalid_argument("group_encode: direct mode takes integer keys");
   if (span < 0 || span > kGroupDirectCap) throw std::invalid_argument("group_encode: direct range above the cap");
   if (a.n == 0) return;
@@ -388,20 +332,20 @@ void group_encode_direct(const GroupKeyCol& a, int64_t base, int64_t span, int* 
   DQ_HIP_CHECK(hipGetLastError());
 }
 
-void group_hash_insert(const GroupKeyCol& a, unsigned long long* table, int64_t capacity, unsigned long long* state,
+void group_hash_insert(const KeyCol& a, unsigned long long* table, int64_t capacity, unsigned long long* state,
                        int blocks, hipStream_t st) {
-  check_key(a, blocks);
-  check_table(capacity);
+  check_key_col(a, blocks, "group_encode");
+  check_group_table(capacity);
   if (a.n == 0) return;
   hipLaunchKernelGGL(group_hash_insert_kernel, dim3((unsigned)blocks), dim3(kGroupThreads), 0, st, a, table,
                      (u64)(capacity - 1), state);
   DQ_HIP_CHECK(hipGetLastError());
 }
 
-void group_hash_lookup(const GroupKeyCol& a, const unsigned long long* table, int64_t capacity, const int* slot_gid,
+void group_hash_lookup(const KeyCol& a, const unsigned long long* table, int64_t capacity, const int* slot_gid,
                        int top_gid, int* gid, int blocks, hipStream_t st) {
-  check_key(a, blocks);
-  check_table(capacity);
+  check_key_col(a, blocks, "group_encode");
+  check_group_table(capacity);
   if (a.n == 0) return;
   hipLaunchKernelGGL(group_hash_lookup_kernel, dim3((unsigned)blocks), dim3(kGroupThreads), 0, st, a, table,
                      (u64)(capacity - 1), slot_gid, top_gid, gid);

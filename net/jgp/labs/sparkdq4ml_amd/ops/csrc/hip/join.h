@@ -7,6 +7,8 @@
 
 #include <cstdint>
 
+#include "keys.h"
+
 namespace dq4ml {
 
 constexpr int kJoinRun = 4;  // consecutive rows per thread and trip
@@ -25,26 +27,17 @@ enum JoinMode : int {
   JOIN_SEMI = 3,   // only mask[l] = 1 when the row has a match (nothing is counted)
 };
 
-// one key column of one side
-struct JoinKeyCol {
-  const void* col;
-  const uint8_t* valid;  // 0/1 per row, or null
-  const uint8_t* sel;    // 0/1 per row, or null
-  int64_t n;
-  int dt;
-};
-
 // occupancy-sized grid for n rows / for `total` output positions
 int join_blocks(int64_t n);
 int join_expand_blocks(int64_t total);
 // table: capacity u64 slots, all ones on entry; cnt [capacity + 1] u32 zeroed; first [capacity + 1]
 // i32 set to INT32_MAX; bslot [n] i32; state: [distinct keys in the table, rows inserted, overflow,
 // the all-ones key was seen] zeroed.  The all-ones key owns the extra slot `capacity`.
-void join_build(const JoinKeyCol& right, unsigned long long* table, int64_t capacity, unsigned* cnt, int* first, int* bslot,
+void join_build(const KeyCol& right, unsigned long long* table, int64_t capacity, unsigned* cnt, int* first, int* bslot,
                 unsigned long long* state, int blocks, hipStream_t st);
 // pslot [n] i32 (-1: no match), pcnt [n] i32 (output pairs of the row), matched [capacity + 1] u8
 // (JOIN_FULL), mask [n] u8 (JOIN_SEMI; pslot and pcnt are not written then)
-void join_probe(const JoinKeyCol& left, const unsigned long long* table, int64_t capacity, const unsigned* cnt, int mode,
+void join_probe(const KeyCol& left, const unsigned long long* table, int64_t capacity, const unsigned* cnt, int mode,
                 int* pslot, int* pcnt, uint8_t* matched, uint8_t* mask, int blocks, hipStream_t st);
 // offsets [n_left + 1] i64: the exclusive prefix sum of pcnt and the total.  li / ri [total] i64.
 // start [capacity + 1] i32 and brow [nbrow] i32 (the right rows grouped by slot, in row order), or

@@ -36,39 +36,8 @@ namespace {
 static_assert(kJoinRun == kRawRun, "the run loaders of keys.h read kJoinRun rows");
 static_assert(kJoinThreads >= 2 * kWave, "the expansion's two boundary searches take a wave each");
 
-struct JoinRun {
-  u64 key[kJoinRun];
-  unsigned live, valid;
-};
-
-__device__ __forceinline__ JoinRun load_keys(const JoinKeyCol& a, int64_t r0) {
-  JoinRun k;
-  u64 raw[kJoinRun];
-  load_run(a.col, a.dt, r0, a.n, raw);
-  const bool isf = is_float_dt(a.dt);
-#pragma unroll
-  for (int j = 0; j < kJoinRun; ++j) k.key[j] = order_key(raw[j], isf, true);
-  k.live = mask_run(a.sel, r0, a.n);
-  k.valid = k.live;
-  if (a.valid != nullptr) k.valid &= mask_run(a.valid, r0, a.n);
-  return k;
-}
-
-__device__ __forceinline__ void store_run(int* out, int64_t r0, int64_t n, const int v[kJoinRun]) {
-  if (r0 + kJoinRun <= n && ((reinterpret_cast<uintptr_t>(out) & 15) == 0)) {
-    i32x4 x;
-#pragma unroll
-    for (int j = 0; j < kJoinRun; ++j) x[j] = v[j];
-    *reinterpret_cast<i32x4*>(out + r0) = x;
-    return;
-  }
-#pragma unroll
-  for (int j = 0; j < kJoinRun; ++j)
-    if (r0 + j < n) out[r0 + j] = v[j];
-}
-
 // state: [0] distinct keys in the table, [1] rows inserted, [2] overflow, [3] the all-ones key was seen
-__global__ __launch_bounds__(kJoinThreads) void join_build_kernel(JoinKeyCol a, u64* table, u64 mask, unsigned* cnt, int* first,
+__global__ __launch_bounds__(kJoinThreads) void join_build_kernel(KeyCol a, u64* table, u64 mask, unsigned* cnt, int* first,
                                                                   int* bslot, u64* state) {
   const int lane = threadIdx.x & (kWave - 1);
   const int top = (int)(mask + 1);  // the slot of the all-ones key
@@ -80,7 +49,7 @@ __global__ __launch_bounds__(kJoinThreads) void join_build_kernel(JoinKeyCol a, 
     // a full table: stop inserting, the launcher raises (wave-uniform read)
     if (__builtin_amdgcn_readfirstlane((int)load_slot(state + 2)) != 0) break;
     const int64_t r0 = t * kJoinTrip + (int64_t)threadIdx.x * kJoinRun;
-    const JoinRun k = load_keys(a, r0);
+    const KeyRun k = load_keys(a, r0);
     int s[kJoinRun];
 #pragma unroll
     for (int j = 0; j < kJoinRun; ++j) {
@@ -137,14 +106,14 @@ __global__ __launch_bounds__(kJoinThreads) void join_build_kernel(JoinKeyCol a, 
   if (saw_top) atomicOr(state + 3, 1ull);
 }
 
-__global__ __launch_bounds__(kJoinThreads) void join_probe_kernel(JoinKeyCol a, const u64* table, u64 mask, const unsigned* cnt,
+__global__ __launch_bounds__(kJoinThreads) void join_probe_kernel(KeyCol a, const u64* table, u64 mask, const unsigned* cnt,
                                                                   int mode, int* pslot, int* pcnt, uint8_t* matched,
                                                                   uint8_t* out_mask) {
   const int64_t top = (int64_t)(mask + 1);
   const int64_t trips = (a.n + kJoinTrip - 1) / kJoinTrip;
   for (int64_t t = blockIdx.x; t < trips; t += gridDim.x) {
     const int64_t r0 = t * kJoinTrip + (int64_t)threadIdx.x * kJoinRun;
-    const JoinRun k = load_keys(a, r0);
+    const KeyRun k = load_keys(a, r0);
     int ps[kJoinRun], pc[kJoinRun];
 #pragma unroll
     for (int j = 0; j < kJoinRun; ++j) {
@@ -252,40 +221,27 @@ __global__ __launch_bounds__(kJoinThreads) void join_expand_kernel(const int64_t
   }
 }
 
-int full_grid(int per_cu, int64_t want) {
-  int dev = 0, cus = 0;
-  DQ_HIP_CHECK(hipGetDevice(&dev));
-  DQ_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  const int64_t full = (int64_t)per_cu * (cus < 1 ? 1 : cus);
-  if (want < 1) want = 1;
-  return (int)(want < full ? want : full);
-}
-
-void check_key(const JoinKeyCol& a, int blocks) {
-  if (a.n < 0) throw std::invalid_argument("join: negative row count");
+void check_side(const KeyCol& a, int blocks) {
+  check_key_col(a, blocks, "join");
   if (a.n >= ((int64_t)1 << 31)) throw std::invalid_argument("join: fewer than 2^31 rows per side");
-  if (blocks < 1) throw std::invalid_argument("join: blocks must be >= 1");
-  if (!is_key_dt(a.dt)) throw std::invalid_argument("join: keys must be f64, f32, i32, i64 or u8");
-  if (a.col == nullptr && a.n > 0) throw std::invalid_argument("join: null column");
 }
 
-void check_table(int64_t capacity) {
-  if (capacity < 2 || (capacity & (capacity - 1)) != 0 || capacity > kJoinMaxCapacity)
-    throw std::invalid_argument("join: the table capacity must be a power of two in [2, 2^30]");
+void check_join_table(int64_t capacity) {
+  check_table(capacity, kJoinMaxCapacity, "join: the table capacity must be a power of two in [2, 2^30]");
 }
 
 }  // namespace
 
 // 8 blocks of 4 waves per CU: a probe is a chain of dependent random reads, which only more waves
 // in flight hide; the rest of the trips are grid-strided
-int join_blocks(int64_t n) { return full_grid(8, (n + kJoinTrip - 1) / kJoinTrip); }
+int join_blocks(int64_t n) { return grid_for(8, (n + kJoinTrip - 1) / kJoinTrip); }
 
-int join_expand_blocks(int64_t total) { return full_grid(8, (total + kJoinTile - 1) / kJoinTile); }
+int join_expand_blocks(int64_t total) { return grid_for(8, (total + kJoinTile - 1) / kJoinTile); }
 
-void join_build(const JoinKeyCol& right, unsigned long long* table, int64_t capacity, unsigned* cnt, int* first, int* bslot,
+void join_build(const KeyCol& right, unsigned long long* table, int64_t capacity, unsigned* cnt, int* first, int* bslot,
                 unsigned long long* state, int blocks, hipStream_t st) {
-  check_key(right, blocks);
-  check_table(capacity);
+  check_side(right, blocks);
+  check_join_table(capacity);
   if (right.n == 0) return;
   if (table == nullptr || cnt == nullptr || first == nullptr || bslot == nullptr || state == nullptr)
     throw std::invalid_argument("join: null buffer");
@@ -294,10 +250,10 @@ void join_build(const JoinKeyCol& right, unsigned long long* table, int64_t capa
   DQ_HIP_CHECK(hipGetLastError());
 }
 
-void join_probe(const JoinKeyCol& left, const unsigned long long* table, int64_t capacity, const unsigned* cnt, int mode,
+void join_probe(const KeyCol& left, const unsigned long long* table, int64_t capacity, const unsigned* cnt, int mode,
                 int* pslot, int* pcnt, uint8_t* matched, uint8_t* mask, int blocks, hipStream_t st) {
-  check_key(left, blocks);
-  check_table(capacity);
+  check_side(left, blocks);
+  check_join_table(capacity);
   if (mode < JOIN_INNER || mode > JOIN_SEMI) throw std::invalid_argument("join: unknown probe mode");
   if (left.n == 0) return;
   if (table == nullptr || cnt == nullptr) throw std::invalid_argument("join: null buffer");
@@ -315,7 +271,7 @@ void join_expand(const int64_t* offsets, int64_t n_left, int64_t total, const in
   if (n_left >= ((int64_t)1 << 31)) throw std::invalid_argument("join: fewer than 2^31 rows per side");
   if (total >= ((int64_t)1 << 31)) throw std::invalid_argument("join: fewer than 2^31 pairs per call");
   if (blocks < 1) throw std::invalid_argument("join: blocks must be >= 1");
-  check_table(capacity);
+  check_join_table(capacity);
   if ((start == nullptr) != (brow == nullptr))
     throw std::invalid_argument("join: the slot starts and the grouped right rows come together or not at all");
   if (total == 0) return;

@@ -1,6 +1,7 @@
-// Order-preserving 64-bit keys of typed column values, shared by the grouping kernels
-// (groupby.hip) and the sort kernels (sort.hip): the typed raw loaders, the 0/1 byte-mask loader
-// and order_key.  Device code only.
+// Order-preserving 64-bit keys of typed column values: the one home of the key rule for the
+// relational kernels (groupby.hip, join.hip, sort.hip, quantile.hip).  The key column and its
+// per-thread reader (KeyCol, KeyRun / load_keys, store_run), the typed raw loaders, the 0/1
+// byte-mask loader, order_key and its inverse.  ops/keys.py is the numpy statement of the rule.
 #pragma once
 #include "common.h"
 
@@ -14,6 +15,15 @@ constexpr u64 kSign = 0x8000000000000000ull;
 constexpr u64 kNaNBits = 0x7ff8000000000000ull;
 constexpr u64 kInfBits = 0x7ff0000000000000ull;
 constexpr int kRawRun = 4;  // consecutive rows of one run load
+
+// one key column: valid / sel are 0/1 bytes per row, or null
+struct KeyCol {
+  const void* col;
+  const uint8_t* valid;
+  const uint8_t* sel;
+  int64_t n;
+  int dt;
+};
 
 __device__ __forceinline__ bool is_float_dt(int dt) { return dt == DT_F64 || dt == DT_F32; }
 
@@ -108,13 +118,69 @@ __device__ __forceinline__ unsigned mask_run(const uint8_t* m, int64_t r0, int64
   return out;
 }
 
-// order key of a widened value; fold: the grouping rule (-0.0 == +0.0), else -0.0 < +0.0 (MIN / MAX)
-__device__ __forceinline__ u64 order_key(u64 raw, bool isf, bool fold) {
-  if (!isf) return raw ^ kSign;
-  u64 b = raw;
-  if ((b & ~kSign) > kInfBits) b = kNaNBits;  // every NaN: one canonical NaN above +inf
+// order key of the bits of a double that is not NaN; fold: the grouping rule (-0.0 == +0.0), else
+// -0.0 < +0.0 (MIN / MAX)
+__device__ __forceinline__ u64 float_key(u64 b, bool fold) {
   if (fold && b == kSign) b = 0;
   return (b & kSign) ? ~b : (b | kSign);
+}
+
+// order key of a widened value
+__device__ __forceinline__ u64 order_key(u64 raw, bool isf, bool fold) {
+  if (!isf) return raw ^ kSign;
+  // every NaN: one canonical NaN above +inf
+  return float_key((raw & ~kSign) > kInfBits ? kNaNBits : raw, fold);
+}
+
+// the bits of the double behind a float order key (order_key's inverse for isf)
+__host__ __device__ __forceinline__ u64 unkey(u64 k) { return (k & kSign) ? (k ^ kSign) : ~k; }
+
+// a widened value as a double (an i64 rounds to nearest, as a cast does)
+__device__ __forceinline__ double raw_as_f64(u64 raw, bool isf) {
+  return isf ? __longlong_as_double((long long)raw) : (double)(long long)raw;
+}
+
+// The folded keys of the rows [r0, r0 + 4) of a key column.  Bit j of `live`: the row is inside n
+// and selected; of `valid`: it is live and its key is not null.
+struct KeyRun {
+  u64 key[kRawRun];
+  unsigned live, valid;
+};
+
+__device__ __forceinline__ KeyRun load_keys(const KeyCol& a, int64_t r0) {
+  KeyRun k;
+  u64 raw[kRawRun];
+  load_run(a.col, a.dt, r0, a.n, raw);
+  const bool isf = is_float_dt(a.dt);
+#pragma unroll
+  for (int j = 0; j < kRawRun; ++j) k.key[j] = order_key(raw[j], isf, true);
+  k.live = mask_run(a.sel, r0, a.n);
+  k.valid = k.live;
+  if (a.valid != nullptr) k.valid &= mask_run(a.valid, r0, a.n);
+  return k;
+}
+
+// out[r0 + j] = v[j] for the rows inside n: one 16-byte store when the run is complete and aligned
+__device__ __forceinline__ void store_run(int* out, int64_t r0, int64_t n, const int v[kRawRun]) {
+  if (r0 + kRawRun <= n && ((reinterpret_cast<uintptr_t>(out) & 15) == 0)) {
+    i32x4 x;
+#pragma unroll
+    for (int j = 0; j < kRawRun; ++j) x[j] = v[j];
+    *reinterpret_cast<i32x4*>(out + r0) = x;
+    return;
+  }
+#pragma unroll
+  for (int j = 0; j < kRawRun; ++j)
+    if (r0 + j < n) out[r0 + j] = v[j];
+}
+
+// launcher-side check of a key column; `who` prefixes the message
+inline void check_key_col(const KeyCol& a, int blocks, const char* who) {
+  const std::string w(who);
+  if (a.n < 0) throw std::invalid_argument(w + ": negative row count");
+  if (blocks < 1) throw std::invalid_argument(w + ": blocks must be >= 1");
+  if (!is_key_dt(a.dt)) throw std::invalid_argument(w + ": keys must be f64, f32, i32, i64 or u8");
+  if (a.col == nullptr && a.n > 0) throw std::invalid_argument(w + ": null column");
 }
 
 }  // namespace dq4ml

@@ -254,28 +254,23 @@ PYBIND11_MODULE(_dq4ml_hip, m) {
   m.def("group_limits", []() {
     return py::make_tuple(kGroupTrip, kGroupLdsWords, kGroupMaxSlots, kGroupDefaultCapacity, kGroupDirectCap);
   });
-  auto group_key = [](uintptr_t col, int dt, uintptr_t valid, uintptr_t sel, int64_t n) {
-    GroupKeyCol a{};
-    a.col = P<const void>(col);
-    a.valid = P<const uint8_t>(valid);
-    a.sel = P<const uint8_t>(sel);
-    a.n = n;
-    a.dt = dt;
-    return a;
+  // the key column of the grouping and the join bindings
+  auto key_col = [](uintptr_t col, int dt, uintptr_t valid, uintptr_t sel, int64_t n) {
+    return KeyCol{P<const void>(col), P<const uint8_t>(valid), P<const uint8_t>(sel), n, dt};
   };
-  m.def("group_encode_direct", [group_key](uintptr_t col, int dt, uintptr_t valid, uintptr_t sel, int64_t n, int64_t base,
+  m.def("group_encode_direct", [key_col](uintptr_t col, int dt, uintptr_t valid, uintptr_t sel, int64_t n, int64_t base,
                                            int64_t span, uintptr_t gid, int blocks, uintptr_t stream) {
-    group_encode_direct(group_key(col, dt, valid, sel, n), base, span, P<int>(gid), blocks, as_stream(stream));
+    group_encode_direct(key_col(col, dt, valid, sel, n), base, span, P<int>(gid), blocks, as_stream(stream));
   });
-  m.def("group_hash_insert", [group_key](uintptr_t col, int dt, uintptr_t valid, uintptr_t sel, int64_t n, uintptr_t table,
+  m.def("group_hash_insert", [key_col](uintptr_t col, int dt, uintptr_t valid, uintptr_t sel, int64_t n, uintptr_t table,
                                          int64_t capacity, uintptr_t state, int blocks, uintptr_t stream) {
-    group_hash_insert(group_key(col, dt, valid, sel, n), P<unsigned long long>(table), capacity,
+    group_hash_insert(key_col(col, dt, valid, sel, n), P<unsigned long long>(table), capacity,
                       P<unsigned long long>(state), blocks, as_stream(stream));
   });
-  m.def("group_hash_lookup", [group_key](uintptr_t col, int dt, uintptr_t valid, uintptr_t sel, int64_t n, uintptr_t table,
+  m.def("group_hash_lookup", [key_col](uintptr_t col, int dt, uintptr_t valid, uintptr_t sel, int64_t n, uintptr_t table,
                                          int64_t capacity, uintptr_t slot_gid, int top_gid, uintptr_t gid, int blocks,
                                          uintptr_t stream) {
-    group_hash_lookup(group_key(col, dt, valid, sel, n), P<const unsigned long long>(table), capacity,
+    group_hash_lookup(key_col(col, dt, valid, sel, n), P<const unsigned long long>(table), capacity,
                       P<const int>(slot_gid), top_gid, P<int>(gid), blocks, as_stream(stream));
   });
   // slots: (op, column, dtype, valid, e) each; the words of slot s follow those of slot s - 1
@@ -333,27 +328,18 @@ PYBIND11_MODULE(_dq4ml_hip, m) {
   m.def("join_expand_blocks", &join_expand_blocks);
   // rows per trip, output positions per expansion tile, left rows of a tile staged in LDS, largest table
   m.def("join_limits", []() { return py::make_tuple(kJoinTrip, kJoinTile, kJoinLdsRows, kJoinMaxCapacity); });
-  auto join_key = [](uintptr_t col, int dt, uintptr_t valid, uintptr_t sel, int64_t n) {
-    JoinKeyCol a{};
-    a.col = P<const void>(col);
-    a.valid = P<const uint8_t>(valid);
-    a.sel = P<const uint8_t>(sel);
-    a.n = n;
-    a.dt = dt;
-    return a;
-  };
   // table [capacity] u64 all ones; cnt / first [capacity + 1] u32 zeroed / i32 INT32_MAX; state [4] u64 zeroed
-  m.def("join_build", [join_key](uintptr_t col, int dt, uintptr_t valid, uintptr_t sel, int64_t n, uintptr_t table,
+  m.def("join_build", [key_col](uintptr_t col, int dt, uintptr_t valid, uintptr_t sel, int64_t n, uintptr_t table,
                                  int64_t capacity, uintptr_t cnt, uintptr_t first, uintptr_t bslot, uintptr_t state, int blocks,
                                  uintptr_t stream) {
-    join_build(join_key(col, dt, valid, sel, n), P<unsigned long long>(table), capacity, P<unsigned>(cnt), P<int>(first),
+    join_build(key_col(col, dt, valid, sel, n), P<unsigned long long>(table), capacity, P<unsigned>(cnt), P<int>(first),
                P<int>(bslot), P<unsigned long long>(state), blocks, as_stream(stream));
   });
   // mode: 0 inner, 1 outer, 2 full (marks matched [capacity + 1] u8), 3 semi (writes only mask [n] u8)
-  m.def("join_probe", [join_key](uintptr_t col, int dt, uintptr_t valid, uintptr_t sel, int64_t n, uintptr_t table,
+  m.def("join_probe", [key_col](uintptr_t col, int dt, uintptr_t valid, uintptr_t sel, int64_t n, uintptr_t table,
                                  int64_t capacity, uintptr_t cnt, int mode, uintptr_t pslot, uintptr_t pcnt, uintptr_t matched,
                                  uintptr_t mask, int blocks, uintptr_t stream) {
-    join_probe(join_key(col, dt, valid, sel, n), P<const unsigned long long>(table), capacity, P<const unsigned>(cnt), mode,
+    join_probe(key_col(col, dt, valid, sel, n), P<const unsigned long long>(table), capacity, P<const unsigned>(cnt), mode,
                P<int>(pslot), P<int>(pcnt), P<uint8_t>(matched), P<uint8_t>(mask), blocks, as_stream(stream));
   });
   // offsets [n_left + 1] i64; start [capacity + 1] / brow [nbrow] i32, or both 0 for unique right keys

@@ -1,8 +1,8 @@
 // Exact quantiles by most-significant-digit-first radix select.
 //
 // A value becomes a 64-bit key whose unsigned order is the numeric order of the value cast to
-// double (-0.0 folded into +0.0; IEEE bits, negative values flip every bit, the others the sign
-// bit).  Pass k of kQuantPasses histograms digit k (kQuantBits wide, most significant first) of the
+// double: the folded float key of keys.h (-0.0 folded into +0.0) of that double, read with the
+// run loaders of keys.h.  Pass k of kQuantPasses histograms digit k (kQuantBits wide, most significant first) of the
 // keys whose higher digits equal a target's prefix; the one-block pick kernel then finds the bin
 // that holds the target's rank, appends it to the prefix and reduces the rank by the count below
 // it.  After the last pass the prefix is the key of the order statistic.
@@ -22,78 +22,12 @@
 #include <stdexcept>
 
 #include "common.h"
+#include "keys.h"
 
 namespace dq4ml {
 namespace {
 
-typedef __attribute__((ext_vector_type(2))) long long i64x2;
-typedef __attribute__((ext_vector_type(4))) int i32x4;
-
-constexpr uint64_t kSign = 0x8000000000000000ull;
-
-// kQuantRun consecutive rows [r0, r0 + 4) of a typed column as doubles (0 past n): 16-byte loads
-// when the run is complete and the column 16-byte aligned (r0 is a multiple of 4), else a guarded
-// scalar tail.  Nothing is narrowed: f64 stays f64, i64 rounds to nearest as a cast does.
-template <int DT>
-__device__ __forceinline__ void load_run_f64(const void* p, bool aligned, int64_t r0, int64_t n, double x[kQuantRun]) {
-  if (aligned && r0 + kQuantRun <= n) {
-    if constexpr (DT == DT_F64) {
-      const f64x2 a = *gptr<f64x2>(reinterpret_cast<const double*>(p) + r0);
-      const f64x2 b = *gptr<f64x2>(reinterpret_cast<const double*>(p) + r0 + 2);
-      x[0] = a[0], x[1] = a[1], x[2] = b[0], x[3] = b[1];
-    } else if constexpr (DT == DT_I64) {
-      const i64x2 a = *gptr<i64x2>(reinterpret_cast<const long long*>(p) + r0);
-      const i64x2 b = *gptr<i64x2>(reinterpret_cast<const long long*>(p) + r0 + 2);
-      x[0] = (double)a[0], x[1] = (double)a[1], x[2] = (double)b[0], x[3] = (double)b[1];
-    } else if constexpr (DT == DT_F32) {
-      const f32x4 a = *gptr<f32x4>(reinterpret_cast<const float*>(p) + r0);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) x[j] = (double)a[j];
-    } else {
-      const i32x4 a = *gptr<i32x4>(reinterpret_cast<const int*>(p) + r0);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) x[j] = (double)a[j];
-    }
-    return;
-  }
-#pragma unroll
-  for (int j = 0; j < kQuantRun; ++j) {
-    const int64_t r = r0 + j;
-    double v = 0.0;
-    if (r < n) {
-      if constexpr (DT == DT_F64) v = gptr<double>(p)[r];
-      else if constexpr (DT == DT_I64) v = (double)gptr<long long>(p)[r];
-      else if constexpr (DT == DT_F32) v = (double)gptr<float>(p)[r];
-      else v = (double)gptr<int>(p)[r];
-    }
-    x[j] = v;
-  }
-}
-
-// bit j: row r0 + j is inside n and its 0/1 byte is set (null mask: every row inside n)
-__device__ __forceinline__ unsigned mask_run(const uint8_t* m, int64_t r0, int64_t n) {
-  unsigned out = 0;
-  if (m != nullptr && r0 + kQuantRun <= n && ((reinterpret_cast<uintptr_t>(m + r0) & 3) == 0)) {
-    const uint32_t w = *gptr<uint32_t>(m + r0);
-#pragma unroll
-    for (int j = 0; j < kQuantRun; ++j) out |= ((w >> (8 * j)) & 0xffu) ? (1u << j) : 0u;
-    return out;
-  }
-#pragma unroll
-  for (int j = 0; j < kQuantRun; ++j) {
-    const int64_t r = r0 + j;
-    if (r < n && (m == nullptr || gptr<uint8_t>(m)[r] != 0)) out |= 1u << j;
-  }
-  return out;
-}
-
-__device__ __forceinline__ uint64_t key_of(double v) {
-  uint64_t b = (uint64_t)__double_as_longlong(v);
-  if (b == kSign) b = 0;  // -0.0 == +0.0
-  return (b & kSign) ? ~b : (b | kSign);
-}
-
-__host__ __device__ __forceinline__ uint64_t unkey(uint64_t k) { return (k & kSign) ? (k ^ kSign) : ~k; }
+static_assert(kQuantRun == kRawRun, "the run loaders of keys.h read kQuantRun rows");
 
 // One count of bin d for every lane with m set.  Two rounds of "the lanes that agree with the
 // first live lane are one add of their number", then plain atomics for the rest.  Every lane of
@@ -117,21 +51,22 @@ __device__ __forceinline__ void count_digit(uint32_t* h, bool m, unsigned d, int
 template <int DT>
 __device__ __forceinline__ void hist_column(const void* col, const uint8_t* valid, const uint8_t* sel, int64_t n,
                                             int pass, int U, const uint64_t* upref, uint32_t* h) {
-  const bool aligned = (reinterpret_cast<uintptr_t>(col) & 15) == 0;
   const int lane = threadIdx.x & (kWave - 1);
   const int dshift = 64 - kQuantBits * (pass + 1);
   const int64_t trips = (n + kQuantTrip - 1) / kQuantTrip;
   // the trip loop is block-uniform: rows past n are dead lanes, never absent ones
   for (int64_t t = blockIdx.x; t < trips; t += gridDim.x) {
     const int64_t r0 = t * kQuantTrip + (int64_t)threadIdx.x * kQuantRun;
-    double x[kQuantRun];
-    load_run_f64<DT>(col, aligned, r0, n, x);
+    u64 raw[kQuantRun];
+    load_run_raw<DT>(col, r0, n, raw);
     unsigned live = mask_run(sel, r0, n);
     if (valid != nullptr) live &= mask_run(valid, r0, n);
 #pragma unroll
     for (int j = 0; j < kQuantRun; ++j) {
-      const bool ok = ((live >> j) & 1u) && x[j] == x[j];  // NaN is never counted
-      const uint64_t key = key_of(x[j]);
+      // nothing is narrowed: f64 stays f64, i64 rounds to nearest as a cast does
+      const double x = raw_as_f64(raw[j], DT == DT_F64 || DT == DT_F32);
+      const bool ok = ((live >> j) & 1u) && x == x;  // NaN is never counted ...
+      const uint64_t key = float_key((u64)__double_as_longlong(x), true);  // ... so its key is never read
       const unsigned d = (unsigned)(key >> dshift) & (kQuantBins - 1);
       const uint64_t hi = pass == 0 ? 0ull : key >> (dshift + kQuantBits);
       for (int u = 0; u < U; ++u) count_digit(h + u * kQuantBins, ok && hi == upref[u], d, lane);
@@ -250,19 +185,11 @@ void check_shape(int C, int Q) {
 
 }  // namespace
 
-int quantile_blocks(int64_t n) {
-  int dev = 0, cus = 0;
-  DQ_HIP_CHECK(hipGetDevice(&dev));
-  DQ_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  // x dimension: 4 blocks of 4 waves per CU and column (the grid is blocks x C, so C >= 2 columns
-  // already ask for more than the 8 wave slots per SIMD hold and the dispatcher queues the rest);
-  // 32 bytes in flight per thread cover the HBM latency, and the 16.1 KiB of static LDS per block
-  // would allow 9 blocks per CU, so the wave slots, not LDS, bound the residency
-  const int64_t full = 4 * (int64_t)(cus < 1 ? 1 : cus);
-  int64_t want = (n + kQuantTrip - 1) / kQuantTrip;
-  if (want < 1) want = 1;
-  return (int)(want < full ? want : full);
-}
+// x dimension: 4 blocks of 4 waves per CU and column (the grid is blocks x C, so C >= 2 columns
+// already ask for more than the 8 wave slots per SIMD hold and the dispatcher queues the rest);
+// 32 bytes in flight per thread cover the HBM latency, and the 16.1 KiB of static LDS per block
+// would allow 9 blocks per CU, so the wave slots, not LDS, bound the residency
+int quantile_blocks(int64_t n) { return grid_for(4, (n + kQuantTrip - 1) / kQuantTrip); }
 
 void quantile_hist(const QuantCols& a, int pass, const int64_t* state, unsigned long long* hist, int blocks,
                    hipStream_t st) {
@@ -271,7 +198,7 @@ void quantile_hist(const QuantCols& a, int pass, const int64_t* state, unsigned 
   if (blocks < 1) throw std::invalid_argument("quantiles: blocks must be >= 1");
   if (a.n < 0) throw std::invalid_argument("quantiles: negative row count");
   for (int c = 0; c < a.C; ++c) {
-    if (a.dt[c] != DT_F64 && a.dt[c] != DT_F32 && a.dt[c] != DT_I32 && a.dt[c] != DT_I64)
+    if (!is_key_dt(a.dt[c]) || a.dt[c] == DT_U8)  // (order statistics of a boolean: not offered)
       throw std::invalid_argument("quantiles: columns must be f64, f32, i32 or i64");
     if (a.col[c] == nullptr && a.n > 0) throw std::invalid_argument("quantiles: null column");
   }

@@ -257,16 +257,8 @@ __global__ __launch_bounds__(kSortThreads) void sort_scatter_kernel(const u64* k
 
 }  // namespace
 
-int sort_blocks(int64_t m) {
-  int dev = 0, cus = 0;
-  DQ_HIP_CHECK(hipGetDevice(&dev));
-  DQ_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  // up to 8 blocks of 4 waves per CU (the scatter's 29 KiB of LDS allow 5); the rest of the tiles are grid-strided
-  const int64_t full = 8 * (int64_t)(cus < 1 ? 1 : cus);
-  int64_t want = sort_tiles(m);
-  if (want < 1) want = 1;
-  return (int)(want < full ? want : full);
-}
+// up to 8 blocks of 4 waves per CU (the scatter's 29 KiB of LDS allow 5); the rest of the tiles are grid-strided
+int sort_blocks(int64_t m) { return grid_for(8, sort_tiles(m)); }
 
 void sort_keys(const SortKeyCol& a, unsigned long long* keys, unsigned* idx, unsigned long long* hist, int blocks,
                hipStream_t st) {

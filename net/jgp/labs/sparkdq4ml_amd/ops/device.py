@@ -17,6 +17,7 @@ import torch
 from ..parallel import comm
 from ..runtime import faststream
 from . import native
+from .keys import I64_MAX, I64_MIN, KEY_DTYPES
 
 __all__ = ["dtype_code", "gram_stats", "compact_indices", "pack_columns", "predict", "regression_metrics",
            "GRAM_MODES", "quantiles", "group_agg_raw", "group_encode_direct", "group_encode_hash"]
@@ -437,6 +438,8 @@ def gram_stats_folds(X, y, sel, k_or_weights, seed: int, granule: int, compute: 
 # ------------------------------------------------------------------------------------------
 # exact quantiles: radix select (csrc/hip/quantile.hip)
 # ------------------------------------------------------------------------------------------
+# (the relational kernels below -- quantiles, groupby, sort, join -- share the key reader of keys.h;
+# ops/keys.py is its Python statement)
 _QUANT_DTYPES = (torch.float64, torch.float32, torch.int32, torch.int64)
 
 
@@ -448,6 +451,38 @@ def _mask_u8(m: Optional[torch.Tensor], n: int, what: str, who: str = "quantiles
     if m.dtype not in (torch.bool, torch.uint8):
         m = m != 0
     return m.contiguous()
+
+
+def _group_col(c: torch.Tensor, n: int, what: str, dtypes=KEY_DTYPES) -> torch.Tensor:
+    if c.dim() != 1 or int(c.numel()) != n:
+        raise ValueError(f"{what}: columns must be 1-D and of one length")
+    if c.dtype not in dtypes:
+        raise TypeError(f"{what}: unsupported column dtype {c.dtype}")
+    return c.contiguous()
+
+
+class _KeyCol:
+    """One column of ``n`` rows with its validity mask and selection, checked and normalised for
+    the kernels; ``args`` are the five binding arguments of a ``KeyCol`` (the tensors behind the
+    pointers live as long as this object).  ``who`` prefixes the messages, ``art`` words the masks
+    ("the left validity mask")."""
+
+    def __init__(self, col, valid, sel, n: int, who: str, art: str = "the", dtypes=KEY_DTYPES):
+        self.n = int(n)
+        self.col = _group_col(col, self.n, who, dtypes)
+        self.valid = _mask_u8(valid, self.n, f"{art} validity mask", who)
+        self.sel = _mask_u8(sel, self.n, f"{art} selection", who)
+
+    @property
+    def args(self):
+        return self.col.data_ptr(), dtype_code(self.col), _ptr(self.valid), _ptr(self.sel), self.n
+
+
+def _blocks(blocks: Optional[int], default: int) -> int:
+    """The grid override of a relational launch, or the kernel's own occupancy-sized grid."""
+    if blocks is not None and int(blocks) < 1:
+        raise ValueError("blocks must be >= 1")
+    return int(blocks) if blocks else int(default)
 
 
 def quantiles(cols, valids, sel, probs, blocks: Optional[int] = None, reduce=None):
@@ -477,27 +512,21 @@ def quantiles(cols, valids, sel, probs, blocks: Optional[int] = None, reduce=Non
         raise ValueError("quantiles: probabilities must lie in [0, 1]")
     _check_dev(*cols, *valids, sel)
     n = int(cols[0].numel())
-    for c in cols:
-        if c.dim() != 1 or int(c.numel()) != n:
-            raise ValueError("quantiles: columns must be 1-D and of one length")
-        if c.dtype not in _QUANT_DTYPES:
-            raise TypeError(f"quantiles: unsupported column dtype {c.dtype}")
+    ks = [_KeyCol(c, v, None, n, "quantiles", "a", _QUANT_DTYPES) for c, v in zip(cols, valids)]
     if len(cols) > max_c:  # the kernel takes its column table by value: chunk
         vs, ns = zip(*(quantiles(cols[i:i + max_c], valids[i:i + max_c], sel, p, blocks, reduce)
                        for i in range(0, len(cols), max_c)))
         return torch.cat(vs), torch.cat(ns)
     dev = cols[0].device
-    cols = [c.contiguous() for c in cols]
-    valids = [_mask_u8(v, n, "a validity mask") for v in valids]
     sel = _mask_u8(sel, n, "the selection")
     C = len(cols)
-    nb = int(blocks) if blocks else int(h.quantile_blocks(n))
+    nb = _blocks(blocks, h.quantile_blocks(n))
     probs_d = _h2d(p, dev)
     hist = torch.zeros(C, Q, bins, dtype=torch.int64, device=dev)
     state = torch.zeros(C, 2 + 3 * Q, dtype=torch.int64, device=dev)
     values = torch.empty(C, Q, dtype=torch.float64, device=dev)
     counts = torch.empty(C, dtype=torch.int64, device=dev)
-    cp, dt, vp = [c.data_ptr() for c in cols], [dtype_code(c) for c in cols], [_ptr(v) for v in valids]
+    cp, dt, vp, _, _ = (list(a) for a in zip(*(k.args for k in ks)))
     st = _stream()
     for k in range(passes):
         h.quantile_hist(cp, dt, vp, _ptr(sel), n, Q, k, state.data_ptr(), hist.data_ptr(), nb, st)
@@ -513,24 +542,6 @@ def quantiles(cols, valids, sel, probs, blocks: Optional[int] = None, reduce=Non
 # ------------------------------------------------------------------------------------------
 # grouped aggregation on integer words (csrc/hip/groupby.hip); orchestration in ops/groupby.py
 # ------------------------------------------------------------------------------------------
-_GROUP_DTYPES = (torch.float64, torch.float32, torch.int32, torch.int64, torch.uint8, torch.bool)
-_I64_MIN = -(1 << 63)
-
-
-def _group_col(c: torch.Tensor, n: int, what: str) -> torch.Tensor:
-    if c.dim() != 1 or int(c.numel()) != n:
-        raise ValueError(f"{what}: columns must be 1-D and of one length")
-    if c.dtype not in _GROUP_DTYPES:
-        raise TypeError(f"{what}: unsupported column dtype {c.dtype}")
-    return c.contiguous()
-
-
-def _group_blocks(h, n: int, blocks: Optional[int]) -> int:
-    if blocks is not None and int(blocks) < 1:
-        raise ValueError("blocks must be >= 1")
-    return int(blocks) if blocks else int(h.group_blocks(n))
-
-
 def group_agg_raw(gid, G: int, ops, cols, valids, es, sel, n: int, row_offset: int, init: np.ndarray,
                   blocks: Optional[int] = None) -> torch.Tensor:
     """One ``group_agg`` launch: at most ``group_limits()[2]`` slots, ``init`` the identity of each
@@ -556,7 +567,7 @@ def group_agg_raw(gid, G: int, ops, cols, valids, es, sel, n: int, row_offset: i
     acc = _h2d(np.ascontiguousarray(init, dtype=np.int64).reshape(1, -1), dev).repeat(G, 1).contiguous()
     h.group_agg(_ptr(gid), G, [int(o) for o in ops], [_ptr(c) for c in cols],
                 [0 if c is None else dtype_code(c) for c in cols], [_ptr(v) for v in valids], [int(e) for e in es],
-                _ptr(sel), n, int(row_offset), acc.data_ptr(), _group_blocks(h, n, blocks), _stream())
+                _ptr(sel), n, int(row_offset), acc.data_ptr(), _blocks(blocks, h.group_blocks(n)), _stream())
     return acc
 
 
@@ -565,12 +576,9 @@ def group_encode_direct(col, valid, sel, base: int, span: int, blocks: Optional[
     ``[base, base + span)``: -1 dead, 0 null, else ``key - base + 1``."""
     h = native.hip()
     _check_dev(col, valid, sel)
-    n = int(col.numel())
-    col = _group_col(col, n, "group_encode")
-    valid, sel = _mask_u8(valid, n, "the validity mask", "group_encode"), _mask_u8(sel, n, "the selection", "group_encode")
-    gid = torch.empty(n, dtype=torch.int32, device=col.device)
-    h.group_encode_direct(col.data_ptr(), dtype_code(col), _ptr(valid), _ptr(sel), n, int(base), int(span),
-                          gid.data_ptr(), _group_blocks(h, n, blocks), _stream())
+    k = _KeyCol(col, valid, sel, col.numel(), "group_encode")
+    gid = torch.empty(k.n, dtype=torch.int32, device=col.device)
+    h.group_encode_direct(*k.args, int(base), int(span), gid.data_ptr(), _blocks(blocks, h.group_blocks(k.n)), _stream())
     return gid
 
 
@@ -582,16 +590,14 @@ def group_encode_hash(col, valid, sel, capacity: int, max_capacity: int, union=N
     all ranks) widens the key list before the lookup launch."""
     h = native.hip()
     _check_dev(col, valid, sel)
-    n = int(col.numel())
-    col = _group_col(col, n, "group_encode")
-    valid, sel = _mask_u8(valid, n, "the validity mask", "group_encode"), _mask_u8(sel, n, "the selection", "group_encode")
-    dev = col.device
-    nb, st, dt = _group_blocks(h, n, blocks), _stream(), dtype_code(col)
+    k = _KeyCol(col, valid, sel, col.numel(), "group_encode")
+    n, dev = k.n, col.device
+    nb, st = _blocks(blocks, h.group_blocks(n)), _stream()
     cap = int(capacity)
     while True:
         table = torch.full((cap,), -1, dtype=torch.int64, device=dev)
         state = torch.zeros(4, dtype=torch.int64, device=dev)
-        h.group_hash_insert(col.data_ptr(), dt, _ptr(valid), _ptr(sel), n, table.data_ptr(), cap, state.data_ptr(), nb, st)
+        h.group_hash_insert(*k.args, table.data_ptr(), cap, state.data_ptr(), nb, st)
         count, overflow, _has_null, has_top = (int(v) for v in state.tolist())  # the group count sizes the output
         if not overflow:
             break
@@ -600,18 +606,17 @@ def group_encode_hash(col, valid, sel, capacity: int, max_capacity: int, union=N
         cap = min(cap * 8, int(max_capacity))
     # table-sized work: compact the occupied slots, sort the unique keys, build slot -> gid
     occ = torch.nonzero(table != -1, as_tuple=False).flatten()
-    skeys = table[occ] ^ _I64_MIN  # signed order == unsigned key order
+    skeys = table[occ] ^ I64_MIN  # signed order == unsigned key order
     keys = torch.sort(skeys).values
     if has_top:
-        keys = torch.cat([keys, torch.full((1,), (1 << 63) - 1, dtype=torch.int64, device=dev)])
+        keys = torch.cat([keys, torch.full((1,), I64_MAX, dtype=torch.int64, device=dev)])
     if union is not None:
         keys = union(keys)
     assert count == int(occ.numel())
     slot_gid = torch.full((cap,), -1, dtype=torch.int32, device=dev)
     slot_gid[occ] = (torch.searchsorted(keys, skeys) + 1).to(torch.int32)
     gid = torch.empty(n, dtype=torch.int32, device=dev)
-    h.group_hash_lookup(col.data_ptr(), dt, _ptr(valid), _ptr(sel), n, table.data_ptr(), cap, slot_gid.data_ptr(),
-                        int(keys.numel()), gid.data_ptr(), nb, st)
+    h.group_hash_lookup(*k.args, table.data_ptr(), cap, slot_gid.data_ptr(), int(keys.numel()), gid.data_ptr(), nb, st)
     return gid, keys, cap
 
 
@@ -630,11 +635,8 @@ def sort_permutation(cols, valids, sel, ascending, nulls_first, blocks: Optional
     assert tuple(h.sort_limits()) == so.sort_limits(), "sort.py / sort.h constants differ"
     _check_dev(*cols, *valids, sel)
     n = int(cols[0].numel())
-    cols = [_group_col(c, n, "sort") for c in cols]
-    valids = [_mask_u8(v, n, "a validity mask", "sort") for v in valids]
+    ks = [_KeyCol(c, v, None, n, "sort", "a") for c, v in zip(cols, valids)]
     sel = _mask_u8(sel, n, "the selection", "sort")
-    if blocks is not None and int(blocks) < 1:
-        raise ValueError("blocks must be >= 1")
     dev = cols[0].device
     perm = None
     m = n
@@ -651,13 +653,13 @@ def sort_permutation(cols, valids, sel, ascending, nulls_first, blocks: Optional
     keys = [torch.empty(m, dtype=torch.int64, device=dev) for _ in range(2)]
     idx = [torch.empty(m, dtype=torch.int32, device=dev) for _ in range(2)]
     counts = torch.empty(bins * stride, dtype=torch.int32, device=dev)
-    nb = int(blocks) if blocks else int(h.sort_blocks(m))
+    nb = _blocks(blocks, h.sort_blocks(m))
     st = _stream()
     cur = 0
-    for c, v, asc, nf in reversed(list(zip(cols, valids, ascending, nulls_first))):
+    for k, asc, nf in reversed(list(zip(ks, ascending, nulls_first))):
         hist = torch.zeros(so.SORT_DIGITS + 1, bins, dtype=torch.int64, device=dev)
         # (reads perm[i] and writes idx[cur][i] in the same thread: in place after the first column)
-        h.sort_keys(c.data_ptr(), dtype_code(c), _ptr(v), _ptr(perm), n, m, not asc, keys[cur].data_ptr(),
+        h.sort_keys(k.col.data_ptr(), dtype_code(k.col), _ptr(k.valid), _ptr(perm), n, m, not asc, keys[cur].data_ptr(),
                     idx[cur].data_ptr(), hist.data_ptr(), nb, st)
         H = hist.cpu().numpy()  # the one host read of this column
         seen = H[:so.SORT_DIGITS].copy()
@@ -696,8 +698,8 @@ class _JoinBuild:
         from . import join as jo
 
         assert tuple(h.join_limits()) == jo.join_limits(), "join.py / join.h constants differ"
-        nr = int(rkey.numel())
-        dev = rkey.device
+        self.right = right = _KeyCol(rkey, rvalid, rsel, rkey.numel(), "join", "the right")
+        nr, dev = right.n, rkey.device
         self.n = nr
         self.capacity = cap = int(capacity) if capacity else jo.join_capacity(nr)
         self.table = torch.full((cap,), -1, dtype=torch.int64, device=dev)
@@ -705,9 +707,8 @@ class _JoinBuild:
         self.first = torch.full((cap + 1,), (1 << 31) - 1, dtype=torch.int32, device=dev)
         self.bslot = torch.empty(nr, dtype=torch.int32, device=dev)
         state = torch.zeros(4, dtype=torch.int64, device=dev)
-        nb = int(blocks) if blocks else int(h.join_blocks(nr))
-        h.join_build(rkey.data_ptr(), dtype_code(rkey), _ptr(rvalid), _ptr(rsel), nr, self.table.data_ptr(), cap,
-                     self.cnt.data_ptr(), self.first.data_ptr(), self.bslot.data_ptr(), state.data_ptr(), nb, _stream())
+        h.join_build(*right.args, self.table.data_ptr(), cap, self.cnt.data_ptr(), self.first.data_ptr(),
+                     self.bslot.data_ptr(), state.data_ptr(), _blocks(blocks, h.join_blocks(nr)), _stream())
         in_table, inserted, overflow, has_top = (int(v) for v in state.tolist())  # also tells whether a sort is needed
         if overflow or in_table >= cap:
             raise RuntimeError(f"join: a hash table of {cap} slots cannot hold the right side's distinct keys plus one "
@@ -727,13 +728,11 @@ class _JoinBuild:
         self.brow = sort_permutation([self.bslot], [None], self.bslot >= 0, [True], [True], blocks).to(torch.int32)
 
 
-def _join_sides(lkey, rkey, lvalid, rvalid, lsel, rsel):
+def _join_sides(h, lkey, rkey, lvalid, rvalid, lsel, rsel, capacity, blocks):
+    """The probe side, checked and normalised, and the finished build of the right side."""
     _check_dev(lkey, rkey, lvalid, rvalid, lsel, rsel)
-    nl, nr = int(lkey.numel()), int(rkey.numel())
-    lkey, rkey = _group_col(lkey, nl, "join"), _group_col(rkey, nr, "join")
-    lvalid, lsel = _mask_u8(lvalid, nl, "the left validity mask", "join"), _mask_u8(lsel, nl, "the left selection", "join")
-    rvalid, rsel = _mask_u8(rvalid, nr, "the right validity mask", "join"), _mask_u8(rsel, nr, "the right selection", "join")
-    return lkey, rkey, lvalid, rvalid, lsel, rsel
+    left = _KeyCol(lkey, lvalid, lsel, lkey.numel(), "join", "the left")
+    return left, _JoinBuild(h, rkey, rvalid, rsel, capacity, blocks)
 
 
 def join_pairs(lkey, rkey, lvalid, rvalid, lsel, rsel, how: str, capacity: Optional[int] = None, blocks: Optional[int] = None,
@@ -741,40 +740,37 @@ def join_pairs(lkey, rkey, lvalid, rvalid, lsel, rsel, how: str, capacity: Optio
     """Device form of ``ops.join.join_pairs`` (arguments already checked).  Two host reads: the
     build's state vector, and the total of the output offsets, which sizes the result."""
     h = native.hip()
-    lkey, rkey, lvalid, rvalid, lsel, rsel = _join_sides(lkey, rkey, lvalid, rvalid, lsel, rsel)
-    nl, dev = int(lkey.numel()), lkey.device
-    b = _JoinBuild(h, rkey, rvalid, rsel, capacity, blocks)
+    left, b = _join_sides(h, lkey, rkey, lvalid, rvalid, lsel, rsel, capacity, blocks)
+    nl, dev = left.n, left.col.device
     b.layout(blocks)
     st = _stream()
     mode = _JOIN_MODES[how]
     pslot = torch.empty(nl, dtype=torch.int32, device=dev)
     pcnt = torch.empty(nl, dtype=torch.int32, device=dev)
     matched = torch.zeros(b.capacity + 1, dtype=torch.uint8, device=dev) if how == "full_outer" else None
-    nb = int(blocks) if blocks else int(h.join_blocks(nl))
-    h.join_probe(lkey.data_ptr(), dtype_code(lkey), _ptr(lvalid), _ptr(lsel), nl, b.table.data_ptr(), b.capacity,
-                 b.cnt.data_ptr(), mode, pslot.data_ptr(), pcnt.data_ptr(), _ptr(matched), 0, nb, st)
+    h.join_probe(*left.args, b.table.data_ptr(), b.capacity, b.cnt.data_ptr(), mode, pslot.data_ptr(), pcnt.data_ptr(),
+                 _ptr(matched), 0, _blocks(blocks, h.join_blocks(nl)), st)
     offsets = torch.zeros(nl + 1, dtype=torch.int64, device=dev)
     if nl > 0:
         torch.cumsum(pcnt, 0, dtype=torch.int64, out=offsets[1:])
     extra = None
     if how == "full_outer":  # the live right rows that no left row matched (a null key: bslot < 0), in row order
         un = (b.bslot < 0) | (matched[b.bslot.clamp(min=0).to(torch.int64)] == 0)
-        if rsel is not None:
-            un &= rsel.to(torch.bool)
+        if b.right.sel is not None:
+            un &= b.right.sel.to(torch.bool)
         extra = compact_indices(un) if b.n > 0 else torch.empty(0, dtype=torch.int64, device=dev)
     total = int(offsets[nl].item())  # the one host read that sizes the output
     pairs = total + (0 if extra is None else int(extra.numel()))
     if pairs >= 1 << 31:
-        from .join import _too_many
+        from .join import too_many_pairs
 
-        raise _too_many(pairs)
+        raise too_many_pairs(pairs)
     li = torch.empty(total, dtype=torch.int64, device=dev)
     ri = torch.empty(total, dtype=torch.int64, device=dev)
     if total > 0:
-        nbe = int(blocks) if blocks else int(h.join_expand_blocks(total))
         h.join_expand(offsets.data_ptr(), nl, total, pslot.data_ptr(), _ptr(b.start), _ptr(b.brow),
                       0 if b.brow is None else int(b.brow.numel()), b.first.data_ptr(), b.capacity, li.data_ptr(),
-                      ri.data_ptr(), nbe, st)
+                      ri.data_ptr(), _blocks(blocks, h.join_expand_blocks(total)), st)
     if extra is not None and extra.numel():
         li = torch.cat([li, torch.full_like(extra, -1)])
         ri = torch.cat([ri, extra])
@@ -788,13 +784,11 @@ def join_mask(lkey, rkey, lvalid, rvalid, lsel, rsel, capacity: Optional[int] = 
     """Device form of ``ops.join.join_mask``: the build pass and a probe pass that writes only the
     mask (no layout, no expansion)."""
     h = native.hip()
-    lkey, rkey, lvalid, rvalid, lsel, rsel = _join_sides(lkey, rkey, lvalid, rvalid, lsel, rsel)
-    nl, dev = int(lkey.numel()), lkey.device
-    b = _JoinBuild(h, rkey, rvalid, rsel, capacity, blocks)
-    mask = torch.empty(nl, dtype=torch.uint8, device=dev)
-    nb = int(blocks) if blocks else int(h.join_blocks(nl))
-    h.join_probe(lkey.data_ptr(), dtype_code(lkey), _ptr(lvalid), _ptr(lsel), nl, b.table.data_ptr(), b.capacity,
-                 b.cnt.data_ptr(), _JOIN_MODES["semi"], 0, 0, 0, mask.data_ptr(), nb, _stream())
+    left, b = _join_sides(h, lkey, rkey, lvalid, rvalid, lsel, rsel, capacity, blocks)
+    nl = left.n
+    mask = torch.empty(nl, dtype=torch.uint8, device=left.col.device)
+    h.join_probe(*left.args, b.table.data_ptr(), b.capacity, b.cnt.data_ptr(), _JOIN_MODES["semi"], 0, 0, 0,
+                 mask.data_ptr(), _blocks(blocks, h.join_blocks(nl)), _stream())
     mask = mask.view(torch.bool)
     if stats is not None:
         stats.append({"distinct": b.distinct, "unique_build": b.unique, "capacity": b.capacity, "pairs": int(mask.sum().item())})

@@ -5,12 +5,9 @@ numpy forms below, which do exactly the kernels' arithmetic: the raw accumulator
 engines are bit-identical, and so is every result built from them (the finalisation is one piece
 of torch integer code for both).
 
-Keys.  A key value becomes an order-preserving 64-bit key.  Doubles and floats use the IEEE bits
-of the value as a double with ``-0.0`` folded into ``+0.0`` and every NaN mapped to one canonical
-NaN that orders above ``+inf`` (Spark 3's grouping rule; 2.4 kept them apart, SPARK-26021);
-integers and booleans are biased by the sign bit.  Python holds a key as the *signed* order key
-(the u64 key with its top bit flipped, as int64), which for an integer column is the value itself.
-Null keys form one group, slot 0; slots ascend with the key.
+Keys.  A key value becomes the order-preserving 64-bit key of ``ops/keys.py`` (the statement of
+``keys.h``), held as the *signed* order key.  Null keys form one group, slot 0; slots ascend with
+the key.
 
 Accumulators.  Every word is an int64 updated by an integer add / or / max / min, so the result
 does not depend on the grid, the schedule or a shard split.  A double sum is kept in fixed point:
@@ -27,6 +24,9 @@ from typing import List, Optional, Sequence
 import numpy as np
 import torch
 
+from .keys import (I64_MAX, I64_MIN, INTS, KEY_DTYPES, as_np, column_np, hash_home, is_cuda, keys_to_values,
+                   mixed_radix, next_pow2, side_np, skeys_np)
+
 __all__ = ["ROWS", "COUNT", "SUM_I", "SUM_F", "MIN", "MAX", "FIRST", "ABSMAX", "GroupEncoding", "group_limits",
            "group_encode", "group_encode_columns", "group_agg", "group_scale", "op_words", "word_kinds",
            "finalize_sum", "keys_to_values", "hash_home"]
@@ -41,12 +41,7 @@ GROUP_MAX_SLOTS = 8
 GROUP_DEFAULT_CAPACITY = 1 << 16
 GROUP_DIRECT_CAP = 1 << 20
 
-_I64_MIN = -(1 << 63)
-_I64_MAX = (1 << 63) - 1
-_NAN_BITS = 0x7FF8000000000000
 _INF_BITS = 0x7FF0000000000000
-_FLOATS = (torch.float64, torch.float32)
-_INTS = (torch.int32, torch.int64, torch.uint8, torch.bool)
 
 
 def group_limits():
@@ -78,60 +73,35 @@ def _identity(kinds) -> np.ndarray:
     return np.array([-1 if k == K_MIN else 0 for k in kinds], dtype=np.int64)
 
 
-def hash_home(skey: int, capacity: int) -> int:
-    """Home slot of a signed order key in a table of ``capacity`` slots (the kernels' hash)."""
-    key = (int(skey) ^ _I64_MIN) & ((1 << 64) - 1)
-    return ((key * 0x9E3779B97F4A7C15 & ((1 << 64) - 1)) >> 20) & (capacity - 1)
-
-
 # ------------------------------------------------------------------------------------------
-# numpy twins
+# numpy twins (columns are read as the kernels' loaders read them: keys.column_np)
 # ------------------------------------------------------------------------------------------
-def _np(t) -> Optional[np.ndarray]:
-    return None if t is None else t.detach().numpy()
-
-
-def _skeys_np(x: np.ndarray, fold: bool) -> np.ndarray:
-    """Signed order keys of a column (int64)."""
-    if x.dtype.kind in "iub":
-        return x.astype(np.int64)
-    b = x.astype(np.float64).view(np.int64).copy()
-    b[(b & _I64_MAX) > _INF_BITS] = _NAN_BITS
-    if fold:
-        b[b == _I64_MIN] = 0
-    return np.where(b >= 0, b, ~b ^ np.int64(_I64_MIN))
-
-
-def _live_np(sel, n: int) -> np.ndarray:
-    return np.ones(n, dtype=bool) if sel is None else (_np(sel) != 0)
-
-
 def _agg_host(gid, G, ops, cols, valids, es, sel, n, row_offset, init):
     acc = np.tile(np.asarray(init, dtype=np.int64).reshape(1, -1), (G, 1))
-    live = _live_np(sel, n)
+    live = np.ones(n, dtype=bool) if sel is None else (as_np(sel) != 0)
     g = np.zeros(n, dtype=np.int64)
     if gid is not None:
-        g = _np(gid).astype(np.int64)
+        g = as_np(gid).astype(np.int64)
         live = live & (g >= 0) & (g < G)
     w = 0
     with np.errstate(over="ignore", invalid="ignore"):
         for op, c, v, e in zip(ops, cols, valids, es):
-            ok = live if (v is None or op in (ROWS, FIRST)) else live & (_np(v) != 0)
-            x = None if c is None else _np(c)
+            ok = live if (v is None or op in (ROWS, FIRST)) else live & (as_np(v) != 0)
+            x = None if c is None else column_np(c)
             if op in (ROWS, COUNT):
                 np.add.at(acc[:, w], g[ok], 1)
             elif op == SUM_I:
                 np.add.at(acc[:, w], g[ok], x[ok].astype(np.int64))
             elif op in (MIN, MAX):
-                k = _skeys_np(x[ok], False)
-                m = np.full(G, _I64_MAX if op == MIN else _I64_MIN, dtype=np.int64)
+                k = skeys_np(x[ok], False)
+                m = np.full(G, I64_MAX if op == MIN else I64_MIN, dtype=np.int64)
                 (np.minimum if op == MIN else np.maximum).at(m, g[ok], k)
-                acc[:, w] = m ^ np.int64(_I64_MIN)
+                acc[:, w] = m ^ np.int64(I64_MIN)
             elif op == FIRST:
                 m = acc[:, w].view(np.uint64)
                 np.minimum.at(m, g[ok], (np.nonzero(ok)[0] + int(row_offset)).astype(np.uint64))
             elif op == ABSMAX:
-                b = x[ok].astype(np.float64).view(np.int64) & np.int64(_I64_MAX)
+                b = x[ok].astype(np.float64).view(np.int64) & np.int64(I64_MAX)
                 fin = b < _INF_BITS
                 np.maximum.at(acc[:, w], g[ok][fin], b[fin])
             else:  # SUM_F
@@ -149,9 +119,7 @@ def _agg_host(gid, G, ops, cols, valids, es, sel, n, row_offset, init):
 
 
 def _direct_host(col, valid, sel, base, span):
-    x = _np(col).astype(np.int64)
-    live = _live_np(sel, x.size)
-    ok = live if valid is None else live & (_np(valid) != 0)
+    x, live, ok = side_np(col, valid, sel)  # (an integer's key is its value)
     off = x - np.int64(base)  # (wraps like the kernel's unsigned subtraction)
     inside = (off >= 0) & (off < span)
     g = np.where(~live, -1, np.where(~ok, 0, np.where(inside, off + 1, -1)))
@@ -159,10 +127,7 @@ def _direct_host(col, valid, sel, base, span):
 
 
 def _hash_host(col, valid, sel, union):
-    x = _np(col)
-    live = _live_np(sel, x.size)
-    ok = live if valid is None else live & (_np(valid) != 0)
-    k = _skeys_np(x, True)
+    k, live, ok = side_np(col, valid, sel)
     keys = torch.from_numpy(np.unique(k[ok]))
     if union is not None:
         keys = union(keys)
@@ -184,13 +149,9 @@ def _n_rows(gid, sel, slots) -> int:
     raise ValueError("group_agg: nothing tells the row count (no gid, selection, column or mask)")
 
 
-def _is_cuda(*ts) -> bool:
-    return any(t is not None and t.is_cuda for t in ts)
-
-
 def _agg_call(gid, G, ops, cols, valids, es, sel, n, row_offset, blocks):
     init = _identity(word_kinds(ops))
-    if _is_cuda(gid, sel, *cols, *valids):
+    if is_cuda(gid, sel, *cols, *valids):
         from . import device
 
         return device.group_agg_raw(gid, G, ops, cols, valids, es, sel, n, row_offset, init, blocks)
@@ -260,10 +221,6 @@ class GroupEncoding:
     capacity: Optional[int] = None
 
 
-def _next_pow2(v: int) -> int:
-    return 1 << max(1, int(v - 1).bit_length())
-
-
 def group_encode(col: torch.Tensor, valid=None, sel=None, capacity: Optional[int] = None, blocks: Optional[int] = None,
                  reduce=None, union=None, mode: Optional[str] = None) -> GroupEncoding:
     """Group ids of one key column (f64 / f32 / i32 / i64 / bool / u8).  Integer and boolean keys
@@ -273,17 +230,17 @@ def group_encode(col: torch.Tensor, valid=None, sel=None, capacity: Optional[int
     are exchanged."""
     if col.dim() != 1:
         raise ValueError("group_encode: the key column must be 1-D")
-    if col.dtype not in _FLOATS + _INTS:
+    if col.dtype not in KEY_DTYPES:
         raise TypeError(f"group_encode: unsupported key dtype {col.dtype}")
     n = int(col.numel())
     if n >= 1 << 31:
         raise ValueError("group_encode: fewer than 2^31 rows per call")
     dev = col.device
-    if col.dtype in _INTS and mode != "hash":
+    if col.dtype in INTS and mode != "hash":
         acc, off = group_agg(None, 1, [(MIN, col, valid), (MAX, col, valid), (COUNT, None, valid)], sel, blocks=blocks,
                              reduce=reduce, n=n)
         lo, hi, cnt = (int(v) for v in acc[0, off].tolist())
-        lo, hi = lo ^ _I64_MIN, hi ^ _I64_MIN
+        lo, hi = lo ^ I64_MIN, hi ^ I64_MIN
         lo, hi = (lo + (1 << 63)) % (1 << 64) - (1 << 63), (hi + (1 << 63)) % (1 << 64) - (1 << 63)
         span = hi - lo + 1 if cnt > 0 else 0
         if span <= GROUP_DIRECT_CAP:
@@ -298,26 +255,18 @@ def group_encode(col: torch.Tensor, valid=None, sel=None, capacity: Optional[int
             return GroupEncoding(gid, span + 1, keys, "direct", col.dtype)
     if mode == "direct":
         raise ValueError("group_encode: direct mode takes integer keys of a live range within the cap")
-    cap = _next_pow2(int(capacity)) if capacity else GROUP_DEFAULT_CAPACITY
+    cap = next_pow2(int(capacity)) if capacity else GROUP_DEFAULT_CAPACITY
     if cap < 2:
         raise ValueError("group_encode: capacity must be at least 2")
     used = None
     if col.is_cuda:
         from . import device
 
-        gid, keys, used = device.group_encode_hash(col, valid, sel, cap, max(cap, _next_pow2(2 * max(n, 1))), union, blocks)
+        gid, keys, used = device.group_encode_hash(col, valid, sel, cap, max(cap, next_pow2(2 * max(n, 1))), union, blocks)
     else:
         gid, keys = _hash_host(col, valid, sel, union)
     keys = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), keys.to(dev)])
     return GroupEncoding(gid, int(keys.numel()), keys, "hash", col.dtype, used)
-
-
-def keys_to_values(keys: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
-    """The column values (of ``dtype``) behind signed order keys."""
-    if dtype in _FLOATS:
-        bits = torch.where(keys >= 0, keys, ~(keys ^ _I64_MIN))
-        return bits.view(torch.float64).to(dtype)
-    return keys.to(dtype) if dtype != torch.bool else keys != 0
 
 
 def group_encode_columns(cols, valids=None, sel=None, capacity: Optional[int] = None, blocks: Optional[int] = None,
@@ -335,18 +284,7 @@ def group_encode_columns(cols, valids=None, sel=None, capacity: Optional[int] = 
         e = encs[0]
         slot = torch.arange(e.G, device=e.keys.device)
         return e.gid, e.G, [(keys_to_values(e.keys, e.dtype), slot > 0)]
-    total = 1
-    for e in encs:
-        total *= e.G
-    if total >= 1 << 63:
-        raise ValueError("group_encode: the product of the key columns' cardinalities does not fit in 63 bits")
-    code, stride, strides = None, 1, []
-    for e in reversed(encs):  # the first column is the most significant digit
-        term = e.gid.to(torch.int64) * stride
-        code = term if code is None else code + term
-        strides.append(stride)
-        stride *= e.G
-    strides.reverse()
+    code, strides = mixed_radix([e.gid for e in encs], [e.G for e in encs], "group_encode")
     c = group_encode(code, None, sel, capacity, blocks, reduce, union)  # (a dead row's code is never read)
     out = []
     for e, s in zip(encs, strides):

@@ -10,7 +10,7 @@ form below.  The pair order is defined, so the two engines return the same pairs
 * ``full_outer`` does the same, then appends ``(-1, r)`` for every live right row that no left row
   matched, in right row order (a null right key counts as unmatched).
 
-Keys.  The key of a row is the folded order key of ``ops/groupby.py`` (``_skeys_np`` with
+Keys.  The key of a row is the folded order key of ``ops/keys.py`` (``skeys_np`` with
 ``fold=True``): ``-0.0`` joins ``0.0``, every NaN joins every NaN (Spark's ``NaN = NaN`` is true in
 join keys), integers compare as int64, booleans / ``uint8`` as 0 / non-zero.  A null key matches
 nothing; a row outside its side's selection vector does not exist.
@@ -26,7 +26,8 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from .groupby import _FLOATS, _INTS, _next_pow2, _np, _skeys_np, group_encode
+from .groupby import group_encode
+from .keys import KEY_DTYPES, is_cuda, mixed_radix, next_pow2, side_np
 
 __all__ = ["join_pairs", "join_mask", "join_key_columns", "join_limits", "join_capacity", "HOWS"]
 
@@ -49,17 +50,17 @@ def join_limits():
 def join_capacity(n_right: int) -> int:
     """Default table capacity for ``n_right`` build rows: the next power of two at or above twice
     the row count (known before the launch, so nothing grows or retries), at most 2^30."""
-    return min(_next_pow2(2 * max(int(n_right), 1)), JOIN_MAX_CAPACITY)
+    return min(next_pow2(2 * max(int(n_right), 1)), JOIN_MAX_CAPACITY)
 
 
-def _too_many(total: int):
+def too_many_pairs(total: int):
     return ValueError(f"join: the result has {total} pairs; a join returns fewer than 2^31 pairs per call")
 
 
 def _check_side(key, valid, sel, who: str) -> int:
     if key.dim() != 1:
         raise ValueError(f"join: the {who} key must be 1-D")
-    if key.dtype not in _FLOATS + _INTS:
+    if key.dtype not in KEY_DTYPES:
         raise TypeError(f"join: unsupported key dtype {key.dtype}")
     n = int(key.numel())
     if n >= 1 << 31:
@@ -70,7 +71,12 @@ def _check_side(key, valid, sel, who: str) -> int:
     return n
 
 
-def _check_capacity(capacity) -> Optional[int]:
+def _check_join(lkey, rkey, lvalid, rvalid, lsel, rsel, capacity, blocks) -> Optional[int]:
+    """Checks both sides and the launch overrides (for both engines); returns the capacity."""
+    _check_side(lkey, lvalid, lsel, "left")
+    _check_side(rkey, rvalid, rsel, "right")
+    if blocks is not None and int(blocks) < 1:
+        raise ValueError("blocks must be >= 1")
     if capacity is None:
         return None
     cap = int(capacity)
@@ -79,30 +85,14 @@ def _check_capacity(capacity) -> Optional[int]:
     return cap
 
 
-def _is_cuda(*ts) -> bool:
-    return any(t is not None and t.is_cuda for t in ts)
-
-
 # ------------------------------------------------------------------------------------------
 # numpy twin
 # ------------------------------------------------------------------------------------------
-def _side_np(key, valid, sel):
-    x = _np(key)
-    if x.dtype == np.uint8:
-        x = x != 0
-    with np.errstate(invalid="ignore"):  # (widening a signalling f32 NaN)
-        k = _skeys_np(x, True)
-    n = int(k.size)
-    live = np.ones(n, dtype=bool) if sel is None else (_np(sel) != 0)
-    ok = live if valid is None else (live & (_np(valid) != 0))
-    return k, live, ok
-
-
 def _match_host(lkey, rkey, lvalid, rvalid, lsel, rsel):
     """Per left row the run ``[lo, lo + c)`` of its matches in ``srow``, the live non-null right
     rows in the stable order of their keys."""
-    lk, llive, lok = _side_np(lkey, lvalid, lsel)
-    rk, rlive, rok = _side_np(rkey, rvalid, rsel)
+    lk, llive, lok = side_np(lkey, lvalid, lsel)
+    rk, rlive, rok = side_np(rkey, rvalid, rsel)
     rrows = np.nonzero(rok)[0]
     keys = rk[rrows]
     order = np.argsort(keys, kind="stable")
@@ -129,7 +119,7 @@ def _pairs_host(lkey, rkey, lvalid, rvalid, lsel, rsel, how, stats):
         hit = np.isin(rk, lk[lok]) & rok
         extra = np.nonzero(rlive & ~hit)[0].astype(np.int64)
     if total + int(extra.size) >= MAX_PAIRS:  # from the counts alone: nothing of that size exists yet
-        raise _too_many(total + int(extra.size))
+        raise too_many_pairs(total + int(extra.size))
     li = np.repeat(np.arange(lk.size, dtype=np.int64), pcnt)
     off = np.cumsum(pcnt) - pcnt
     k = np.arange(total, dtype=np.int64) - off[li]
@@ -161,12 +151,8 @@ def join_pairs(lkey: torch.Tensor, rkey: torch.Tensor, lvalid=None, rvalid=None,
     fewer than 2^31 pairs (``ValueError`` naming the count, before anything of that size exists)."""
     if how not in HOWS:
         raise ValueError(f"join: how must be one of {', '.join(HOWS)}, got {how!r}")
-    _check_side(lkey, lvalid, lsel, "left")
-    _check_side(rkey, rvalid, rsel, "right")
-    cap = _check_capacity(capacity)
-    if blocks is not None and int(blocks) < 1:
-        raise ValueError("blocks must be >= 1")
-    if _is_cuda(lkey, rkey, lvalid, rvalid, lsel, rsel):
+    cap = _check_join(lkey, rkey, lvalid, rvalid, lsel, rsel, capacity, blocks)
+    if is_cuda(lkey, rkey, lvalid, rvalid, lsel, rsel):
         from . import device
 
         return device.join_pairs(lkey, rkey, lvalid, rvalid, lsel, rsel, how, cap, blocks, stats)
@@ -178,12 +164,8 @@ def join_mask(lkey: torch.Tensor, rkey: torch.Tensor, lvalid=None, rvalid=None, 
     """bool ``[n_left]``: the live left rows whose key has a match on the right (``left_semi``; the
     caller complements it within the selection for ``left_anti``).  One build pass and one probe
     pass: nothing is expanded and no row is moved."""
-    _check_side(lkey, lvalid, lsel, "left")
-    _check_side(rkey, rvalid, rsel, "right")
-    cap = _check_capacity(capacity)
-    if blocks is not None and int(blocks) < 1:
-        raise ValueError("blocks must be >= 1")
-    if _is_cuda(lkey, rkey, lvalid, rvalid, lsel, rsel):
+    cap = _check_join(lkey, rkey, lvalid, rvalid, lsel, rsel, capacity, blocks)
+    if is_cuda(lkey, rkey, lvalid, rvalid, lsel, rsel):
         from . import device
 
         return device.join_mask(lkey, rkey, lvalid, rvalid, lsel, rsel, cap, blocks, stats)
@@ -225,17 +207,9 @@ def join_key_columns(lcols: Sequence[torch.Tensor], rcols: Sequence[torch.Tensor
         e = group_encode(torch.cat([lc, rc]), valid, sel)
         gids.append(e.gid)
         cards.append(int(e.G))
-    total = 1
-    for g in cards:
-        total *= g
-    if total >= 1 << 63:
-        raise ValueError("join: the product of the key columns' cardinalities does not fit in 63 bits")
-    code, stride = None, 1
+    code, _ = mixed_radix([g.clamp(min=0) for g in gids], cards, "join")
     ok = None
-    for gid, g in zip(reversed(gids), reversed(cards)):  # the first column is the most significant digit
-        term = gid.to(torch.int64).clamp(min=0) * stride
-        code = term if code is None else code + term
+    for gid in gids:
         present = gid > 0  # 0: a null component, -1: a dead row
         ok = present if ok is None else (ok & present)
-        stride *= g
     return code[:nl].contiguous(), ok[:nl].contiguous(), code[nl:].contiguous(), ok[nl:].contiguous()

@@ -5,7 +5,7 @@ form below, which is the same algorithm: an LSD radix sort of (order key, row in
 8-bit digits, over the sort columns from last to first, so that stability makes the earlier columns
 dominate.  A stable sort has one right answer, so the two engines return the same permutation.
 
-Keys.  The order key of a value is the folded key of ``ops/groupby.py`` (``_skeys_np`` with
+Keys.  The order key of a value is the folded key of ``ops/keys.py`` (``skeys_np`` with
 ``fold=True``): ``-0.0`` equals ``0.0`` and every NaN is one value above ``+inf``, which is Spark's
 ordering of doubles; integers are biased by the sign bit; booleans (and ``uint8`` columns, read as
 0 / non-zero) are 0 / 1.  A descending order complements the key.  A null row has key 0 and a null
@@ -20,7 +20,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 import torch
 
-from .groupby import _FLOATS, _INTS, _I64_MIN, _np, _skeys_np
+from .keys import I64_MIN, KEY_DTYPES, as_np, is_cuda, side_np
 
 __all__ = ["sort_permutation", "sort_limits", "NULL_DIGIT"]
 
@@ -51,17 +51,14 @@ def _flags(v, k: int, what: str) -> List[bool]:
 
 def _sort_host(cols, valids, sel, ascending, nulls_first, stats) -> torch.Tensor:
     n = int(cols[0].numel())
-    perm = np.arange(n, dtype=np.int64) if sel is None else np.nonzero(_np(sel) != 0)[0].astype(np.int64)
+    perm = np.arange(n, dtype=np.int64) if sel is None else np.nonzero(as_np(sel) != 0)[0].astype(np.int64)
     m = int(perm.size)
     for c, v, asc, nf in reversed(list(zip(cols, valids, ascending, nulls_first))):
-        x = _np(c)
-        if x.dtype == np.uint8:
-            x = x != 0
-        with np.errstate(invalid="ignore"):  # (widening a signalling f32 NaN)
-            key = (_skeys_np(x[perm], True) ^ np.int64(_I64_MIN)).view(np.uint64)
+        k, _, ok = side_np(c, v, None)
+        key = (k[perm] ^ np.int64(I64_MIN)).view(np.uint64)
         if not asc:
             key = ~key
-        null = np.zeros(m, dtype=bool) if v is None else (_np(v)[perm] == 0)
+        null = ~ok[perm]
         key[null] = 0
         live = []
         for d in range(SORT_DIGITS):
@@ -101,11 +98,11 @@ def sort_permutation(cols: Sequence[torch.Tensor], valids=None, sel: Optional[to
     for c in cols:
         if c.dim() != 1 or int(c.numel()) != n:
             raise ValueError("sort: columns must be 1-D and of one length")
-        if c.dtype not in _FLOATS + _INTS:
+        if c.dtype not in KEY_DTYPES:
             raise TypeError(f"sort: unsupported column dtype {c.dtype}")
     if n >= 1 << 31:
         raise ValueError("sort: fewer than 2^31 rows per call")
-    if any(t is not None and t.is_cuda for t in (*cols, *valids, sel)):
+    if is_cuda(*cols, *valids, sel):
         from . import device
 
         return device.sort_permutation(cols, valids, sel, ascending, nulls_first, blocks, stats)

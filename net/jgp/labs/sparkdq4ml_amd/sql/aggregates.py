@@ -17,6 +17,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from ..ops.keys import I64_MIN
 from .expressions import Alias, AnalysisException, ColRef, Expr, Lit, to_expr
 from .table import ColumnData, Table
 from .types import (BooleanType, DoubleType, LongType, StringType, StructField, StructType, VectorUDT, is_numeric)
@@ -25,7 +26,6 @@ __all__ = ["AggExpr", "GroupedData", "build_aggregate", "contains_aggregate", "a
            "sort_table"]
 
 _FNS = ("count", "sum", "avg", "min", "max")
-_I64_MIN = -(1 << 63)
 
 
 class AggExpr(Expr):
@@ -155,9 +155,9 @@ class _Ranks:
         if add.numel():
             out[:, add] = comm.all_reduce_sum(acc[:, add].contiguous())
         if mx.numel():  # unsigned max: flip the top bit, signed max
-            out[:, mx] = comm.all_reduce_max((acc[:, mx] ^ _I64_MIN).contiguous()) ^ _I64_MIN
+            out[:, mx] = comm.all_reduce_max((acc[:, mx] ^ I64_MIN).contiguous()) ^ I64_MIN
         if mn.numel():  # unsigned min: the max of the complements
-            out[:, mn] = ~(comm.all_reduce_max((~acc[:, mn] ^ _I64_MIN).contiguous()) ^ _I64_MIN)
+            out[:, mn] = ~(comm.all_reduce_max((~acc[:, mn] ^ I64_MIN).contiguous()) ^ I64_MIN)
         if orr.numel():  # flag words hold three bits: or = per-bit max
             f = acc[:, orr]
             bits = torch.stack([(f >> b) & 1 for b in range(3)], dim=0).contiguous()
@@ -295,7 +295,7 @@ def aggregate_table(t: Table, keys: Sequence[str], aggs, schema: StructType, sha
             if fn == "avg":
                 v = v / n_c.to(torch.float64)
         else:
-            v = gb.keys_to_values(acc[:, w] ^ _I64_MIN, col.dtype)
+            v = gb.keys_to_values(acc[:, w] ^ I64_MIN, col.dtype)
             if v.dtype != f.dataType.torch_dtype:
                 v = v.to(f.dataType.torch_dtype)
         valid = n_c > 0
