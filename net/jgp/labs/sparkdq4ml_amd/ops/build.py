@@ -99,7 +99,7 @@ def build_hip(force: bool = False) -> str:
     """One object per translation unit under ``ops/.obj/`` (compiled in parallel, only the stale
     ones: a kernel edit recompiles one file, not the module), then one link."""
     srcs = _sources("hip", [".hip", ".cpp"])
-    headers = glob.glob(os.path.join(CSRC, "hip", "*.h"))
+    headers = glob.glob(os.path.join(CSRC, "hip", "*.h")) + glob.glob(os.path.join(CSRC, "host", "*.h"))
     objdir = os.path.join(HERE, ".obj")
     with _Lock("hip"):
         if force or _stale(HIP_SO, srcs):
@@ -110,6 +110,7 @@ def build_hip(force: bool = False) -> str:
             tl = _torch_lib()
             flags = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden",
                      "-munsafe-fp-atomics", *_py_includes(), f"-I{os.path.join(CSRC, 'hip')}",
+                     f"-I{os.path.join(CSRC, 'host')}",  # qn_ctl.h: shared with the host module
                      *os.environ.get("DQ4ML_HIPCC_EXTRA", "").split()]  # A/B builds (-D knobs)
             objs = [os.path.join(objdir, os.path.basename(s) + ".o") for s in srcs]
             todo = [(s, o) for s, o in zip(srcs, objs) if force or _obj_stale(o, s, headers)]

@@ -186,6 +186,19 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
   return v;
 }
 
+// every thread of an NW-wave block gets the block-wide sum (fixed order: waves 0..NW-1); red: [NW] in LDS
+template <int NW>
+__device__ __forceinline__ double block_sum(double v, double* red) {
+  v = wave_sum_f64(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double s = 0.0;
+#pragma unroll
+  for (int i = 0; i < NW; ++i) s += red[i];
+  return s;
+}
+
 // Grid-wide barrier of a plain launch whose blocks are co-resident (at most one block per CU, as
 // the launchers size it).  bar = [arrivals, abandoned], zeroed by a stream-ordered memset before
 // the launch; gen counts the barriers this block has passed (thread 0's copy).  Writes before the

@@ -9,13 +9,13 @@
 //    compact model B = theta I - W M W^T minimized segment by segment), then -- after the first
 //    iteration -- the direct primal subspace minimization over the free variables (Breeze's
 //    findAlpha always returns 1), projected onto the box;
-//  * step: Breeze's StrongWolfeLineSearch (64 bracket / 64 zoom steps, cubic interpolation) from
-//    t = 1 on the UNPROJECTED ray; the accepted point is projected and, when the projection moved
-//    it, evaluated once more (CachedDiffFunction otherwise returns the last trial's values);
+//  * step: Breeze's StrongWolfeLineSearch (qn_ctl.h, with LBFGSB's step caps) from t = 1 on the
+//    UNPROJECTED ray; the accepted point is projected and, when the projection moved it,
+//    evaluated once more (CachedDiffFunction otherwise returns the last trial's values);
 //  * memory: a pair is kept when |s.y| > 2.2e-16 y.y; theta = y.y / s.y; M = inv([[-D, L^T],
 //    [L, theta S^T S]]) by Gauss-Jordan with partial pivoting (2m x 2m <= 20 x 20);
-//  * convergence: ||P(x - g) - x||_inf <= 1e-5, max iterations, |f - max(last 20 f)| <= tol |f0|,
-//    ||g|| <= max(tol |f|, 1e-8), a search failed twice (the first failure resets the memory).
+//  * convergence: ||P(x - g) - x||_inf <= 1e-5, then the tests and the failure rule every
+//    quasi-Newton solver here shares (qn_ctl.h); a failed search also resets theta.
 //
 // One evaluation = the Huber row pass over THIS rank's rows (rowops.hip huber_pass_dev: the trial
 // point is read from HBM), its fold into red = [loss, W, g_b, g_sigma, g_x(d)], the caller's
@@ -28,6 +28,8 @@
 
 #pragma clang fp contract(off)  // the scalar algebra mirrors models/lbfgsb.py's numpy expressions
 
+#include "qn_ctl.h"  // (after the pragma: its functions take this file's contraction setting)
+
 namespace dq4ml {
 
 namespace {
@@ -35,15 +37,15 @@ namespace {
 constexpr int kT = 256;
 constexpr int kW = kT / 64;
 constexpr int kM = 10;  // Spark's LBFGSB memory
-constexpr int kFv = 20;
+constexpr int kWolfeCap = 64;  // LBFGSB: bracket and zoom steps of a strong-Wolfe search
 constexpr double kProjEps = 1e-5, kCurvEps = 2.2e-16, kDmax = 1.7976931348623157e308;
-enum { kLsBracket = 0, kLsZoom = 1 };
 enum { kPhInit = 0, kPhSearch = 1, kPhAccept = 2 };
 
 struct HCtl {
-  int act, phase, ls, bi, zi, iter, H, hh, nfv, failed_once, search_failed, why, overflow, nev;
-  double alpha, value, init_value, theta, f0, d0, lo_t, lo_d, lo_f, hi_t, hi_d, hi_f;
-  double fv[kFv];
+  int act, phase, iter, H, hh, failed_once, search_failed, why, overflow, nev;
+  double value, init_value, theta;
+  qn::Wolfe wolfe;
+  qn::FvWindow fvals;
 };
 
 struct HArgs {
@@ -89,23 +91,6 @@ __device__ __forceinline__ HV views(const HArgs& a) {
   return v;
 }
 
-__device__ __forceinline__ double wsum(double v) {
-#pragma unroll
-  for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s);
-  return v;
-}
-
-// every thread gets the block-wide sum (fixed order)
-__device__ __forceinline__ double bsum(double v, double* red) {
-  v = wsum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = 0.0;
-  for (int i = 0; i < kW; ++i) s += red[i];
-  return s;
-}
-
 __device__ __forceinline__ double lower_of(const HArgs& a, int i) { return i == a.dim - 1 ? 4.9406564584124654e-324 : -kDmax; }
 __device__ __forceinline__ double upper_of(const HArgs&, int) { return kDmax; }
 __device__ __forceinline__ double clampb(const HArgs& a, int i, double v) {
@@ -128,7 +113,7 @@ __device__ __forceinline__ void write_trial(const HArgs& a, const double* th, do
     if (a.shift) sd += a.shift[j] * ce;
     a.trial[j] = a.scale ? ce * a.scale[j] : ce;
   }
-  sd = a.shift ? bsum(sd, red) : 0.0;
+  sd = a.shift ? block_sum<kW>(sd, red) : 0.0;
   if (threadIdx.x == 0) {
     a.trial[d] = (a.fit_icpt ? th[d] : 0.0) + sd;
     a.trial[d + 1] = th[a.dim - 1];
@@ -146,7 +131,7 @@ __device__ __forceinline__ double eval_of(const HArgs& a, const HV& v, double* r
     v.ge[j] = gx / W + a.lam[j] * c;
     reg += a.lam[j] * c * c;
   }
-  reg = bsum(reg, red);
+  reg = block_sum<kW>(reg, red);
   if (threadIdx.x == 0) {
     if (a.fit_icpt) v.ge[d] = a.red[2] / W;
     v.ge[a.dim - 1] = a.red[3] / W;
@@ -166,19 +151,13 @@ __device__ __forceinline__ int converged(const HArgs& a, const HV& v, const HCtl
   for (int s = 32; s > 0; s >>= 1) pm = fmax(pm, __shfl_xor(pm, s));
   __syncthreads();
   if ((threadIdx.x & 63) == 0) red[kW + (threadIdx.x >> 6)] = pm;
-  gg = bsum(gg, red);
+  gg = block_sum<kW>(gg, red);
   double pmax = 0.0;
   for (int i = 0; i < kW; ++i) pmax = fmax(pmax, red[kW + i]);
-  if (pmax <= kProjEps) return 0;                                  // projected step converged
-  if (a.max_iter >= 0 && C.iter >= a.max_iter) return 1;          // max iterations
-  if (C.nfv >= 2) {
-    double mx = -__builtin_inf();
-    for (int i = kFv - C.nfv; i < kFv; ++i) mx = fmax(mx, C.fv[i]);
-    if (fabs(C.value - mx) <= a.tol * fabs(C.init_value)) return 2;  // function values converged
-  }
-  if (sqrt(gg) <= fmax(a.tol * fabs(C.value), 1e-8)) return 3;   // gradient converged
-  if (C.search_failed) return 4;
-  return -1;
+  if (pmax <= kProjEps) return 0;  // projected step converged; then the shared reasons, from 1
+  const int why = qn::converged(a.max_iter, C.iter, C.fvals.n, C.fvals.max_indexed(), C.value, C.init_value, C.value,
+                                sqrt(gg), a.tol, C.search_failed);
+  return why < 0 ? -1 : why + 1;
 }
 
 // Partial pivot of column `col` of an m-row matrix (row stride ld) in LDS, computed by EVERY wave
@@ -251,7 +230,7 @@ __device__ __forceinline__ void wave_dots(int npairs, int n, F term, P put) {
   for (int q = wave; q < npairs; q += kW) {
     double s = 0.0;
     for (int e = lane; e < n; e += 64) s += term(q, e);
-    s = wsum(s);
+    s = wave_sum_f64(s);
     if (lane == 0) put(q, s);
   }
 }
@@ -350,7 +329,7 @@ __device__ __forceinline__ double direction(const HArgs& a, const HV& v, HCtl& C
             [&](int k, double s) { p[k] = s, c[k] = 0.0; });
   double f1 = 0.0;
   for (int i = threadIdx.x; i < n; i += kT) f1 += v.g[i] * v.dd[i];
-  f1 = bsum(f1, red);  // (its barriers also publish p)
+  f1 = block_sum<kW>(f1, red);  // (its barriers also publish p)
   if (threadIdx.x < m2) {
     double mp = 0.0;
     for (int q = 0; q < m2; ++q) mp += mget(v, threadIdx.x, q) * p[q];
@@ -455,7 +434,7 @@ __device__ __forceinline__ double direction(const HArgs& a, const HV& v, HCtl& C
       v.dir[i] = di;
       gd += v.g[i] * di;
     }
-    return bsum(gd, red);
+    return block_sum<kW>(gd, red);
   }
   // subspace minimization over the free variables of the Cauchy point
   const double it = 1.0 / C.theta;
@@ -526,16 +505,12 @@ __device__ __forceinline__ double direction(const HArgs& a, const HV& v, HCtl& C
     v.dir[i] = di;
     gd += v.g[i] * di;
   }
-  return bsum(gd, red);
+  return block_sum<kW>(gd, red);
 }
 
 __device__ __forceinline__ void record(const HArgs& a, HCtl& C) {
-  if (C.H >= a.hist_cap) {
-    C.overflow = 1;
-    return;
-  }
-  a.out[a.d + 8 + C.H] = C.value;
-  ++C.H;
+  const int slot = qn::record(C.H, a.hist_cap, C.overflow);
+  if (slot >= 0) a.out[a.d + 8 + slot] = C.value;
 }
 
 // the output [coef(d) | intercept | scale | status | why | H | iter | nev | hist(H)]
@@ -559,31 +534,12 @@ __device__ __forceinline__ void set_trial(const HArgs& a, const HV& v, HCtl& C, 
   for (int i = threadIdx.x; i < a.dim; i += kT) v.xe[i] = v.x[i] + v.dir[i] * t;
   __syncthreads();
   write_trial(a, v.xe, red);
-  if (threadIdx.x == 0) {
-    C.alpha = t;
-    C.act = kHuberEval;
-  }
+  if (threadIdx.x == 0) C.act = kHuberEval;
 }
 
 // a FirstOrderException (line search failed / zoom failed / non-descent direction)
-__device__ __forceinline__ bool fail(const HArgs& a, HCtl& C) {
-  if (!C.failed_once) {
-    C.failed_once = 1;
-    C.hh = 0;
-    C.theta = 1.0;
-  } else {
-    C.search_failed = 1;
-  }
-  return true;
-}
-
-__device__ __forceinline__ double interp(double at, double ad, double af, double bt, double bd, double bf) {
-  const double d1 = ad + bd - 3.0 * (af - bf) / (at - bt);
-  const double d2 = sqrt(d1 * d1 - ad * bd);
-  const double mul = bt - at;
-  const double x = bt - mul * (bd + d2 - d1) / (bd - ad + 2.0 * d2);
-  const double lb = at + 0.1 * mul, ub = at + 0.9 * mul;
-  return x < lb ? lb : (x > ub ? ub : x);
+__device__ __forceinline__ void fail(HCtl& C) {
+  if (qn::note_failure(C.failed_once, C.search_failed)) C.hh = 0, C.theta = 1.0;
 }
 
 }  // namespace
@@ -607,16 +563,13 @@ __device__ __forceinline__ void next_search(const HArgs& a, const HV& v, HCtl& C
       return;
     }
     const double d0 = direction(a, v, C, red, sh);
-    if (d0 > 0.0) {  // "Line search invoked with non-descent direction"
-      if (threadIdx.x == 0) fail(a, C);
+    if (qn::non_descent(d0)) {
+      if (threadIdx.x == 0) fail(C);
       continue;      // the failed state is a state of the iterator: recorded, checked
     }
     if (threadIdx.x == 0) {
       C.phase = kPhSearch;
-      C.ls = kLsBracket;
-      C.bi = 0;
-      C.f0 = C.value, C.d0 = d0;
-      C.lo_t = 0.0, C.lo_d = d0, C.lo_f = C.value;
+      C.wolfe.start(C.value, d0, 1.0);
     }
     __syncthreads();
     set_trial(a, v, C, 1.0, red);
@@ -649,16 +602,14 @@ __device__ __forceinline__ void ctl_body(const HArgs& a, const HV& v, HCtl& C, d
   const double f = eval_of(a, v, red);
   double dd = 0.0;
   for (int i = threadIdx.x; i < a.dim; i += kT) dd += v.ge[i] * v.dir[i];
-  dd = bsum(dd, red);
+  dd = block_sum<kW>(dd, red);
   if (threadIdx.x == 0) ++C.nev;
   __syncthreads();
-  const double c1 = 1e-4, c2 = 0.9;
   if (C.phase == kPhInit) {
     for (int i = threadIdx.x; i < a.dim; i += kT) v.g[i] = v.ge[i];
     if (threadIdx.x == 0) {
       C.value = f, C.init_value = f;
-      C.fv[kFv - 1] = __builtin_inf();  // FunctionValuesConverged's initial info
-      C.nfv = 1;
+      C.fvals.init();
     }
     next_search(a, v, C, red, sh);
     __syncthreads();
@@ -670,44 +621,8 @@ __device__ __forceinline__ void ctl_body(const HArgs& a, const HV& v, HCtl& C, d
   if (C.phase == kPhAccept) {
     accept = true;  // (f, ge) at the projected accepted point
   } else if (threadIdx.x == 0) {
-    const double t = C.alpha;
-    if (C.ls == kLsBracket) {
-      const int i = C.bi;
-      if (!(f - f == 0.0)) {  // not finite: halve, same bracket step count
-        tnext = t / 2.0;
-      } else if (f > C.f0 + c1 * t * C.d0 || (f >= C.lo_f && i > 0)) {
-        C.hi_t = t, C.hi_d = dd, C.hi_f = f;
-        C.ls = kLsZoom, C.zi = 0;
-      } else if (fabs(dd) <= c2 * fabs(C.d0)) {
-        accept = true;
-      } else if (dd >= 0.0) {
-        C.hi_t = C.lo_t, C.hi_d = C.lo_d, C.hi_f = C.lo_f;
-        C.lo_t = t, C.lo_d = dd, C.lo_f = f;
-        C.ls = kLsZoom, C.zi = 0;
-      } else {
-        C.lo_t = t, C.lo_d = dd, C.lo_f = f;
-        tnext = t * 1.5;
-      }
-      if (!accept && C.ls == kLsBracket && ++C.bi >= 64) failed = true;  // "Line search failed"
-      if (!accept && !failed && C.ls == kLsZoom) {
-        tnext = C.lo_t > C.hi_t ? interp(C.hi_t, C.hi_d, C.hi_f, C.lo_t, C.lo_d, C.lo_f)
-                                : interp(C.lo_t, C.lo_d, C.lo_f, C.hi_t, C.hi_d, C.hi_f);
-      }
-    } else {  // zoom: the trial just evaluated
-      if (f > C.f0 + c1 * t * C.d0 || f >= C.lo_f) {
-        C.hi_t = t, C.hi_d = dd, C.hi_f = f;
-      } else if (fabs(dd) <= c2 * fabs(C.d0)) {
-        accept = true;
-      } else {
-        if (dd * (C.hi_t - C.lo_t) >= 0.0) C.hi_t = C.lo_t, C.hi_d = C.lo_d, C.hi_f = C.lo_f;
-        C.lo_t = t, C.lo_d = dd, C.lo_f = f;
-      }
-      if (!accept && ++C.zi >= 64) failed = true;  // "Line search zoom failed"
-      if (!accept && !failed)
-        tnext = C.lo_t > C.hi_t ? interp(C.hi_t, C.hi_d, C.hi_f, C.lo_t, C.lo_d, C.lo_f)
-                                : interp(C.lo_t, C.lo_d, C.lo_f, C.hi_t, C.hi_d, C.hi_f);
-    }
-    red[0] = accept ? 1.0 : 0.0, red[1] = failed ? 1.0 : 0.0, red[2] = tnext;
+    const qn::Step step = C.wolfe.next(f, dd, kWolfeCap, kWolfeCap);
+    red[0] = step == qn::kAccept ? 1.0 : 0.0, red[1] = step == qn::kFail ? 1.0 : 0.0, red[2] = C.wolfe.alpha;
   }
   __syncthreads();
   if (C.phase != kPhAccept) {
@@ -715,7 +630,7 @@ __device__ __forceinline__ void ctl_body(const HArgs& a, const HV& v, HCtl& C, d
   }
   __syncthreads();
   if (failed) {
-    if (threadIdx.x == 0) fail(a, C);
+    if (threadIdx.x == 0) fail(C);
     next_search(a, v, C, red, sh);
     __syncthreads();
     if (threadIdx.x == 0) *v.C = C;
@@ -736,7 +651,7 @@ __device__ __forceinline__ void ctl_body(const HArgs& a, const HV& v, HCtl& C, d
       if (p != v.xe[i]) moved += 1.0;
       v.xe[i] = p;
     }
-    moved = bsum(moved, red);
+    moved = block_sum<kW>(moved, red);
     same = moved == 0.0;
     if (!same) {
       write_trial(a, v.xe, red);
@@ -756,8 +671,8 @@ __device__ __forceinline__ void ctl_body(const HArgs& a, const HV& v, HCtl& C, d
     sy += s * y;
     yy += y * y;
   }
-  sy = bsum(sy, red);
-  yy = bsum(yy, red);
+  sy = block_sum<kW>(sy, red);
+  yy = block_sum<kW>(yy, red);
   const int n = a.dim;
   if (kCurvEps * yy < fabs(sy)) {
     const int h = C.hh;
@@ -784,9 +699,7 @@ __device__ __forceinline__ void ctl_body(const HArgs& a, const HV& v, HCtl& C, d
   }
   for (int i = threadIdx.x; i < n; i += kT) v.x[i] = v.xe[i], v.g[i] = v.ge[i];
   if (threadIdx.x == 0) {
-    for (int i = 0; i < kFv - 1; ++i) C.fv[i] = C.fv[i + 1];
-    C.fv[kFv - 1] = f;
-    C.nfv = C.nfv < kFv ? C.nfv + 1 : kFv;
+    C.fvals.push(f);
     C.value = f;
     ++C.iter;
     C.failed_once = 0;

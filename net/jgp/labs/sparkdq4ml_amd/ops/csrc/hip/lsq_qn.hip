@@ -24,14 +24,17 @@
 //
 // Per evaluation: 2 grid barriers, a redundant O(d) trial-point build per block (the f32
 // effective coefficients go to LDS), a distributed fixed-order fold of the per-block column slabs.
-// Loop passes are bounded by hist_cap and every line search by 21 (backtracking) or 20 (strong
-// Wolfe) evaluations, so the kernel terminates on any input.
+// The line searches, the convergence tests and the failure rule are qn_ctl.h's; loop passes are
+// bounded by hist_cap and every line search by its step caps, so the kernel terminates on any
+// input.
 #include <hip/hip_runtime.h>
 
 #include "common.h"
 #include "lsq.h"
 
 #pragma clang fp contract(off)  // the scalar algebra mirrors the host's numpy / torch expressions
+
+#include "qn_ctl.h"  // (after the pragma: its functions take this file's contraction setting)
 
 namespace dq4ml {
 
@@ -40,22 +43,9 @@ namespace {
 constexpr int kT = 512;
 constexpr int kW = kT / kWave;
 constexpr int kMem = 10;
-constexpr int kFv = 20;
+constexpr int kWolfeCap = 10;  // L-BFGS: bracket and zoom steps of a strong-Wolfe search
 constexpr int kDParts = 4;  // per-block partials of an evaluation: x.(regw x), Σ|l1 x|, dir . g, g . g
 
-
-__device__ __forceinline__ double block_sum(double v, double* red) {
-  v = wave_sum_f64(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = 0.0;
-#pragma unroll
-  for (int i = 0; i < kW; ++i) s += red[i];
-  return s;
-}
-
-__device__ __forceinline__ double sgn(double v) { return v > 0.0 ? 1.0 : (v < 0.0 ? -1.0 : 0.0); }
 
 template <int L>
 __device__ __forceinline__ void unpack(const u32x4 q, float* x) {
@@ -90,7 +80,7 @@ struct Eval {
 
 // ---- optimizer control (thread 0 of each block; scalar code, state in LDS) ------------------
 enum { kActEval = 0, kActAccept = 1, kActApply = 2, kActDone = 3 };
-enum { kLsInit = 0, kLsBack = 1, kLsBracket = 2, kLsZoom = 3 };
+enum { kLsInit = 0, kLsBack = 1, kLsWolfe = 2 };
 
 struct Ctl {
   // next action and the trial it evaluates
@@ -98,16 +88,16 @@ struct Ctl {
   double alpha;
   // optimizer state (models/qn_device.py: st.*, fvals, history, flags)
   double value, adj, gnorm, init_adj;
-  double fv[kFv];
-  int nfv, iter, H, head, hh, pass, search_failed, failed_once, overflow, why, nev;
+  qn::FvWindow fvals;
+  int iter, H, head, hh, pass, search_failed, failed_once, overflow, why, nev;
   int first;  // L-BFGS: the next evaluation is the first of its line search (it forms dvec)
   double pend;  // data-parallel form: the accepted step not yet folded into mvec (the next
                 // search's first pass adds pend * dvec: one grid pass fewer per iteration)
   double last_v, last_adj, last_gg;  // the last evaluation (the accepted step's values)
-  // line search: backtracking (initfval, initd, shrink, it, force) / strong Wolfe (f0, d0, bracket
-  // counter, lo / hi points, zoom counter), |g| of the state for the step checks
-  double initfval, initd, shrink, gnrm, f0, d0, lo_t, lo_d, lo_f, hi_t, hi_d, hi_f;
-  int it, force, bi, zi;
+  // the line search under way (ls), |g| of the state for the accepted step's check
+  qn::Backtrack back;
+  qn::Wolfe wolfe;
+  double gnrm;
   // two-loop scratch (block 0)
   double as_[kMem], rho[kMem];
 };
@@ -140,67 +130,18 @@ struct QnArgs {
   unsigned* gbar;  // the one-launch form's grid barrier [arrivals, abandoned] (grid_barrier)
 };
 
-__device__ void ctl_record(Ctl& C, const QnArgs& a, double* hist) {
-  if (C.H >= a.hist_cap) {
-    C.overflow = 1;
-    return;
-  }
-  if (hist) hist[C.H] = C.adj;
-  ++C.H;
-}
-
-__device__ int ctl_converged(const Ctl& C, const QnArgs& a) {
-  if (a.max_iter >= 0 && C.iter >= a.max_iter) return 0;
-  if (C.nfv >= 2) {
-    double mxv = -__builtin_inf();
-    for (int i = kFv - C.nfv; i < kFv; ++i) mxv = fmax(mxv, C.fv[i]);
-    if (fabs(C.adj - mxv) <= a.tol * fabs(C.init_adj)) return 1;
-  }
-  if (C.gnorm <= fmax(a.tol * fabs(C.value), 1e-8)) return 2;
-  if (C.search_failed) return 3;
-  return -1;
-}
-
 // the end of a loop pass (host: last.clear(); history.append(adj); why = converged())
 __device__ void ctl_end_pass(Ctl& C, const QnArgs& a, double* hist) {
-  ctl_record(C, a, hist);
-  C.why = ctl_converged(C, a);
+  const int slot = qn::record(C.H, a.hist_cap, C.overflow);
+  if (hist && slot >= 0) hist[slot] = C.adj;
+  C.why = qn::converged(a.max_iter, C.iter, C.fvals.n, C.fvals.max_indexed(), C.adj, C.init_adj, C.value, C.gnorm,
+                        a.tol, C.search_failed);
   C.act = (C.why >= 0 || C.overflow) ? kActDone : kActApply;
 }
 
 __device__ void ctl_fail(Ctl& C, const QnArgs& a, double* hist) {  // a FirstOrderException
-  if (!C.failed_once) {
-    C.failed_once = 1;
-    C.hh = 0;
-  } else {
-    C.search_failed = 1;
-  }
+  if (qn::note_failure(C.failed_once, C.search_failed)) C.hh = 0;
   ctl_end_pass(C, a, hist);
-}
-
-__device__ double ctl_interp(double at, double ad, double af, double bt, double bd, double bf) {
-  const double d1 = ad + bd - 3.0 * (af - bf) / (at - bt);
-  const double d2 = sqrt(d1 * d1 - ad * bd);
-  const double mul = bt - at;
-  const double x = bt - mul * (bd + d2 - d1) / (bd - ad + 2.0 * d2);
-  const double lb = at + 0.1 * mul, ub = at + 0.9 * mul;
-  return x < lb ? lb : (x > ub ? ub : x);
-}
-
-__device__ void ctl_zoom_next(Ctl& C) {  // the next zoom trial (interp(hi, lo) if lo.t > hi.t)
-  C.alpha = C.lo_t > C.hi_t ? ctl_interp(C.hi_t, C.hi_d, C.hi_f, C.lo_t, C.lo_d, C.lo_f)
-                            : ctl_interp(C.lo_t, C.lo_d, C.lo_f, C.hi_t, C.hi_d, C.hi_f);
-  C.act = kActEval;
-  C.mode = 1;
-}
-
-__device__ void ctl_found(Ctl& C, const QnArgs& a, double* hist) {
-  // L-BFGS: StepSizeUnderflow when the accepted step is tiny relative to |g|
-  if (C.ls != kLsBack && C.alpha * C.gnrm < 1e-10) {
-    ctl_fail(C, a, hist);
-    return;
-  }
-  C.act = kActAccept;
 }
 
 __device__ void ctl_after_eval(Ctl& C, const Eval& ev, const QnArgs& a, double* hist) {
@@ -209,94 +150,34 @@ __device__ void ctl_after_eval(Ctl& C, const Eval& ev, const QnArgs& a, double* 
     C.act = kActAccept;
     return;
   }
-  const double c1 = 1e-4, c2 = 0.9;
-  if (C.ls == kLsBack) {  // Breeze BacktrackingLineSearch as OWLQN configures it
-    if (C.force) {
-      C.act = kActAccept;
-      return;
-    }
-    double mult;
-    if (ev.adj > C.initfval + C.alpha * C.initd * c1) mult = C.shrink;
-    else if (ev.dd < c2 * C.initd) mult = 2.1;
-    else if (ev.dd > -c2 * C.initd) mult = C.shrink;
-    else mult = 1.0;
-    if (mult == 1.0) {
-      C.act = kActAccept;
-      return;
-    }
-    const double na = C.alpha * mult;
-    if (C.it >= 20 || na < 1e-10 || na > 1e10) {
-      ctl_fail(C, a, hist);
-      return;
-    }
-    C.alpha = na;
-    if (C.it + 1 >= 20) C.force = 1;  // takeWhile(iter < maxIterations) keeps the last state
-    else ++C.it;
-    C.act = kActEval;
-    return;
-  }
-  const double f = ev.v, dd = ev.dd, tt = C.alpha;
-  if (C.ls == kLsBracket) {  // Breeze StrongWolfeLineSearch, bracketing phase
-    const int i = C.bi;
-    if (!(f - f == 0.0)) {  // not finite: halve and retry
-      C.alpha = tt / 2.0;
-    } else if (f > C.f0 + c1 * tt * C.d0 || (f >= C.lo_f && i > 0)) {
-      C.hi_t = tt, C.hi_d = dd, C.hi_f = f;
-      C.ls = kLsZoom, C.zi = 0;
-      ctl_zoom_next(C);
-      return;
-    } else if (fabs(dd) <= c2 * fabs(C.d0)) {
-      ctl_found(C, a, hist);
-      return;
-    } else if (dd >= 0.0) {
-      C.hi_t = C.lo_t, C.hi_d = C.lo_d, C.hi_f = C.lo_f;
-      C.lo_t = tt, C.lo_d = dd, C.lo_f = f;
-      C.ls = kLsZoom, C.zi = 0;
-      ctl_zoom_next(C);
-      return;
-    } else {
-      C.lo_t = tt, C.lo_d = dd, C.lo_f = f;
-      C.alpha = tt * 1.5;
-    }
-    if (++C.bi >= 10) {
-      ctl_fail(C, a, hist);  // "Line search failed"
-      return;
-    }
-    C.act = kActEval;
-    return;
-  }
-  // zoom
-  if (f > C.f0 + c1 * tt * C.d0 || f >= C.lo_f) {
-    C.hi_t = tt, C.hi_d = dd, C.hi_f = f;
+  qn::Step step;
+  if (C.ls == kLsBack) {
+    step = C.back.next(ev.adj, ev.dd);
+    C.alpha = C.back.alpha;
   } else {
-    if (fabs(dd) <= c2 * fabs(C.d0)) {
-      ctl_found(C, a, hist);
-      return;
-    }
-    if (dd * (C.hi_t - C.lo_t) >= 0.0) C.hi_t = C.lo_t, C.hi_d = C.lo_d, C.hi_f = C.lo_f;
-    C.lo_t = tt, C.lo_d = dd, C.lo_f = f;
+    step = C.wolfe.next(ev.v, ev.dd, kWolfeCap, kWolfeCap);
+    C.alpha = C.wolfe.alpha;
+    // L-BFGS: StepSizeUnderflow when the accepted step is tiny relative to |g|
+    if (step == qn::kAccept && C.alpha * C.gnrm < 1e-10) step = qn::kFail;
   }
-  if (++C.zi >= 10) {
-    ctl_fail(C, a, hist);  // "Line search zoom failed"
+  if (step == qn::kFail) {
+    ctl_fail(C, a, hist);
     return;
   }
-  ctl_zoom_next(C);
+  C.act = step == qn::kAccept ? kActAccept : kActEval;
+  C.mode = 1;
 }
 
 __device__ void ctl_after_accept(Ctl& C, const QnArgs& a, double* hist) {
   if (C.ls == kLsInit) {  // the start point
     C.value = C.last_v, C.adj = C.last_adj, C.gnorm = sqrt(C.last_gg);
     C.init_adj = C.adj;
-    ctl_record(C, a, hist);
-    C.why = ctl_converged(C, a);
-    C.act = (C.why >= 0 || C.overflow) ? kActDone : kActApply;
+    ctl_end_pass(C, a, hist);
     return;
   }
   C.head = (C.head + kMem - 1) % kMem;
   C.hh = C.hh < kMem ? C.hh + 1 : kMem;
-  for (int i = 0; i < kFv - 1; ++i) C.fv[i] = C.fv[i + 1];
-  C.fv[kFv - 1] = C.last_v;
-  C.nfv = C.nfv < kFv ? C.nfv + 1 : kFv;
+  C.fvals.push(C.last_v);
   C.value = C.last_v, C.adj = C.last_adj, C.gnorm = sqrt(C.last_gg);
   ++C.iter;
   C.failed_once = 0;
@@ -315,23 +196,17 @@ __device__ void ctl_start_search(Ctl& C, const double* scal, const QnArgs& a, do
   C.act = kActEval;
   if (a.owlqn) {
     C.ls = kLsBack;
-    C.initfval = C.adj;
-    C.initd = initd;
-    C.shrink = C.iter < 1 ? 0.1 : 0.5;
-    C.alpha = C.iter < 1 ? 0.5 / gnrm : 1.0;
-    C.it = 0, C.force = 0;
+    C.back.start(C.iter, C.adj, initd, gnrm);
+    C.alpha = C.back.alpha;
     return;
   }
-  C.ls = kLsBracket;
+  C.ls = kLsWolfe;
   C.first = 1;
-  C.f0 = C.value, C.d0 = initd;
-  if (initd > 0.0) {  // "Line search invoked with non-descent direction"
+  if (!C.wolfe.start(C.value, initd, qn::lbfgs_first_step(C.iter, dnrm))) {
     ctl_fail(C, a, hist);
     return;
   }
-  C.alpha = C.iter == 0 ? 1.0 / dnrm : 1.0;
-  C.lo_t = 0.0, C.lo_d = initd, C.lo_f = C.value;
-  C.bi = 0;
+  C.alpha = C.wolfe.alpha;
 }
 
 // block 0: two-loop recursion on the (pseudo-)gradient -> dir (HBM); scal = [g . dir, |g|^2,
@@ -342,7 +217,7 @@ __device__ void apply_dir(const QnArgs& a, Ctl& C, double* scal, double* red, bo
   auto dot = [&](const double* p, const double* q) {
     double v = 0.0;
     for (int j = t; j < d; j += kT) v += p[j] * q[j];
-    return block_sum(v, red);
+    return block_sum<kW>(v, red);
   };
   const int hh = C.hh, head = C.head;
   bool fail = false;
@@ -380,13 +255,13 @@ __device__ void apply_dir(const QnArgs& a, Ctl& C, double* scal, double* red, bo
   double pd = 0.0, pgg = 0.0, pdd = 0.0;
   for (int j = t; j < d; j += kT) {
     double dj = -a.dir[j];
-    if (owlqn && !(dj * gv[j] < 0.0)) dj = 0.0;
+    if (owlqn) dj = qn::orthant_direction(dj, gv[j]);
     a.dir[j] = dj;
     pd += gv[j] * dj;
     pgg += a.g[j] * a.g[j];
     pdd += dj * dj;
   }
-  const double initd = block_sum(pd, red), gg = block_sum(pgg, red), dn = block_sum(pdd, red);
+  const double initd = block_sum<kW>(pd, red), gg = block_sum<kW>(pgg, red), dn = block_sum<kW>(pdd, red);
   if (t == 0) {
     scal[0] = initd;
     scal[1] = gg;
@@ -450,11 +325,10 @@ __device__ __forceinline__ void ctl_init(Ctl& C) {
   C.mode = 0;
   C.alpha = 0.0;
   C.ls = kLsInit;
-  C.head = 0, C.hh = 0, C.H = 0, C.iter = 0, C.nfv = 1, C.pass = 0;
+  C.head = 0, C.hh = 0, C.H = 0, C.iter = 0, C.pass = 0;
   C.search_failed = 0, C.failed_once = 0, C.overflow = 0, C.why = -1, C.nev = 0, C.first = 0;
   C.pend = 0.0;
-  for (int i = 0; i < kFv; ++i) C.fv[i] = 0.0;
-  C.fv[kFv - 1] = __builtin_inf();
+  C.fvals.init();
 }
 
 // E1 (one block): the trial point x + alpha dir (mode 1, projected for OWLQN) or x0 = 0 (mode 0),
@@ -472,10 +346,7 @@ __device__ void build_trial(const QnArgs& a, const Std& S, int mode, double alph
       if (mode == 1) {
         const double xj = a.x[j];
         nx = xj + a.dir[j] * alpha;
-        if (owlqn) {
-          const double orth = xj != 0.0 ? sgn(xj) : sgn(-a.ag[j]);
-          if (sgn(nx) != orth) nx = 0.0;
-        }
+        if (owlqn) nx = qn::orthant_project(xj, nx, a.ag[j]);
       }
       a.cx[j] = nx;
       const double cf = nx * a.inv_sx[j];
@@ -488,9 +359,9 @@ __device__ void build_trial(const QnArgs& a, const Std& S, int mode, double alph
     }
     a.cs[j] = c32;
   }
-  const double cfmx = block_sum(pm, red);
+  const double cfmx = block_sum<kW>(pm, red);
   double off = a.fit_icpt ? S.icpt0 - cfmx : S.icpt0;
-  if (a.shift) off = off + block_sum(ps, red);
+  if (a.shift) off = off + block_sum<kW>(ps, red);
   if (t == 0) a.scal[16] = off;
   __threadfence();
 }
@@ -612,7 +483,7 @@ __device__ __forceinline__ void qn_pass(const QnArgs& a, const Std& S, int mode,
   // the block's column slab
   double* slab = a.part + (int64_t)b * NC;
   for (int j = t; j < NC; j += kT) slab[j] = colacc[j];
-  const double bl = block_sum(loss, red), bv = block_sum(vsum, red);
+  const double bl = block_sum<kW>(loss, red), bv = block_sum<kW>(vsum, red);
   if (t == 0) a.lpart[2 * b] = bl, a.lpart[2 * b + 1] = bv;
 }
 
@@ -638,14 +509,7 @@ __device__ __forceinline__ void grad_j(const QnArgs& a, const Std& S, int j, dou
   const double l = a.l1[j];
   if (a.owlqn) {
     pl += fabs(l * nx);
-    if (l != 0.0) {
-      if (nx == 0.0) {
-        const double dp = gj + l, dm = gj - l;
-        agj = dm > 0.0 ? dm : (dp < 0.0 ? dp : 0.0);
-      } else {
-        agj = gj + sgn(nx) * l;
-      }
-    }
+    agj = qn::pseudo_gradient(nx, gj, l);
   }
   a.cg[j] = gj;
   a.cag[j] = agj;
@@ -696,7 +560,7 @@ __device__ void finalize_block(const QnArgs& a, const Ctl& C, const Std& S, doub
     a.out[j] = c;
     pc += c * a.mx[j];
   }
-  const double cm = block_sum(pc, red);
+  const double cm = block_sum<kW>(pc, red);
   if (t == 0) {
     a.out[d] = a.fit_icpt ? S.my - cm : 0.0;
     a.out[d + 1] = 0.0;
@@ -785,8 +649,8 @@ __global__ __launch_bounds__(kT, 1) void lsq_qn_kernel(QnArgs a) {
       __syncthreads();
     }
     {
-      const double s0 = block_sum(pr, red), s1 = block_sum(pl, red), s2 = block_sum(pd, red),
-                   s3 = block_sum(pg, red);
+      const double s0 = block_sum<kW>(pr, red), s1 = block_sum<kW>(pl, red), s2 = block_sum<kW>(pd, red),
+                   s3 = block_sum<kW>(pg, red);
       if (t == 0) {
         double* dp = a.dpart + (int64_t)b * kDParts;
         dp[0] = s0, dp[1] = s1, dp[2] = s2, dp[3] = s3;
@@ -956,7 +820,8 @@ __global__ __launch_bounds__(kT) void lsq_qn_dp_ctl_kernel(QnArgs a, int nc) {
   const double lsum = a.red[d];
   double pr = 0.0, pl = 0.0, pd = 0.0, pg = 0.0;
   for (int j = t; j < d; j += kT) grad_j(a, S, j, a.red[j], pr, pl, pd, pg);
-  const double sr = block_sum(pr, red), sl = block_sum(pl, red), sd = block_sum(pd, red), sg = block_sum(pg, red);
+  const double sr = block_sum<kW>(pr, red), sl = block_sum<kW>(pl, red), sd = block_sum<kW>(pd, red),
+               sg = block_sum<kW>(pg, red);
   const Eval ev = eval_of(a, S, lsum, sr, sl, sd, sg);
   __threadfence();
   __syncthreads();

@@ -4,8 +4,8 @@
 // Breeze OWLQN -> un-standardize with no host round trip, so an L1 fit at any k the tall path
 // reaches can be asynchronous.  Same algorithm and decisions as the one-wave wls_qn_kernel
 // (wls_small.hip) and the host driver (csrc/host/solvers.cpp): m = 10 two-loop recursion on the
-// pseudo-gradient, orthant projection, backtracking line search seeded with 0.5 / |g| on the first
-// iteration, FunctionValuesConverged over 20 values, one history reset on a failed search.
+// pseudo-gradient; the standardization, the orthant rules, the line search, the convergence tests
+// and the failure rule are qn_ctl.h's, computed redundantly and uniformly by every thread.
 //
 // Work split (one block per CU, co-resident; grid-wide barriers by common.h grid_barrier):
 //  * the dense standardized k x k system lives in HBM (134 MB at k = 4097 -- MALL resident);
@@ -20,12 +20,13 @@
 //    two barriers, from the history vectors in HBM (L2 resident), with its direction in
 //    registers; the other blocks wait at the barrier.
 // Loop passes are bounded by hist_cap (every pass records one objective value) and each line
-// search by 21 evaluations, so the kernel terminates on any input (NaNs included).
+// search by its step cap, so the kernel terminates on any input (NaNs included).
 // out = [coef(nf), intercept, status, count, wSum, wwSum, bSum, bbSum, H, reason, history(H)] --
 // the wls_qn_small layout (ops/device.py, models/optim.py owlqn_result read both).
 #include <hip/hip_runtime.h>
 
 #include "common.h"
+#include "qn_ctl.h"
 #include "wls_small.h"
 
 namespace dq4ml {
@@ -35,24 +36,9 @@ namespace {
 constexpr int kQT = 512;  // threads per block
 constexpr int kQW = kQT / kWave;
 constexpr int kMem = 10;
-constexpr int kFvals = 20;
 constexpr int kParts = 5;  // per-block partial sums of one evaluation
 
 __device__ __forceinline__ int64_t pk(int i, int j) { return i + (int64_t)j * (j + 1) / 2; }
-
-// every thread gets the block-wide sum (fixed order: waves 0..kQW-1)
-__device__ __forceinline__ double block_sum(double v, double* red) {
-  v = wave_sum_f64(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = 0.0;
-#pragma unroll
-  for (int i = 0; i < kQW; ++i) s += red[i];
-  return s;
-}
-
-__device__ __forceinline__ double sgn(double v) { return v > 0.0 ? 1.0 : (v < 0.0 ? -1.0 : 0.0); }
 
 template <int SL>  // block 0's register slots: element t + kQT s, k <= kQT * SL
 __global__ __launch_bounds__(kQT) void wls_qn_grid_kernel(const double* __restrict__ flat, int nf, int fit_intercept,
@@ -72,34 +58,22 @@ __global__ __launch_bounds__(kQT) void wls_qn_grid_kernel(const double* __restri
   const double* aSum = flat + 5;
   const double* abSum = flat + 5 + nf;
   const double* aa = flat + 5 + 2 * nf;
-  const double count = flat[0], wSum = flat[1], bSum = flat[3], bbSum = flat[4];
+  const double wSum = flat[1];
   if (b == 0 && t < 5) out[nf + 2 + t] = flat[t];
-  const double rawBBar = wSum > 0.0 ? bSum / wSum : 0.0;
-  const double rawBStd = wSum > 0.0 ? sqrt(fmax(bbSum / wSum - rawBBar * rawBBar, 0.0)) : 0.0;
-  if (wSum <= 0.0 || rawBStd == 0.0) {  // uniform across the grid: no barrier has been reached
-    if (b == 0 && t == 0) out[nf + 1] = wSum <= 0.0 ? (count > 0 ? 1.0 : 2.0) : 3.0;
+  const qn::WlsHead hd = qn::wls_head(flat[0], wSum, flat[3], flat[4], reg, enet);
+  if (hd.status != 0) {  // uniform across the grid: no barrier has been reached
+    if (b == 0 && t == 0) out[nf + 1] = (double)hd.status;
     return;
   }
-  const double bStd = rawBStd, bBar = rawBBar / bStd, bbBar = bbSum / wSum / (bStd * bStd);
-  const double eff_reg = reg / bStd, eff_l1 = enet * eff_reg, eff_l2 = (1.0 - enet) * eff_reg;
-  if (eff_l1 == 0.0) {
-    if (b == 0 && t == 0) out[nf + 1] = 9.0;
-    return;
-  }
+  const double bStd = hd.bStd, bBar = hd.bBar, bbBar = hd.bbBar;
   // ---- standardization: owners write the per-feature vectors, then their rows of A ----------
   for (int i = r0 + t; i < r1; i += kQT) {
     double sd = 0.0, bar = 0.0;
-    if (i < nf) {
-      const double m = aSum[i] / wSum;
-      sd = sqrt(fmax(aa[pk(i, i)] / wSum - m * m, 0.0));
-      bar = sd == 0.0 ? 0.0 : m / sd;
-    }
+    if (i < nf) qn::wls_feature(aSum[i], aa[pk(i, i)], wSum, sd, bar);
     w.sstd[i] = sd;
     w.bar[i] = bar;
-    w.ab[i] = i < nf ? (sd == 0.0 ? 0.0 : abSum[i] / wSum / (sd * bStd)) : bBar;  // i == nf: the intercept
-    double l = std_f ? eff_l1 : (sd != 0.0 ? eff_l1 / sd : 0.0);
-    if (i >= nf) l = 0.0;
-    w.l1[i] = l;
+    w.ab[i] = i < nf ? qn::wls_ab(abSum[i], wSum, sd, bStd) : bBar;  // i == nf: the intercept
+    w.l1[i] = i < nf ? qn::wls_l1(hd, sd, std_f) : 0.0;
   }
   __threadfence();
   grid_sync();
@@ -107,14 +81,7 @@ __global__ __launch_bounds__(kQT) void wls_qn_grid_kernel(const double* __restri
     for (int j = t; j < k; j += kQT) {
       double v;
       if (r < nf && j < nf) {
-        const double den = w.sstd[r] * w.sstd[j];
-        v = den == 0.0 ? 0.0 : aa[r <= j ? pk(r, j) : pk(j, r)] / wSum / den;
-        if (r == j) {
-          double lam = eff_l2;
-          if (!std_f) lam = w.sstd[j] != 0.0 ? lam / (w.sstd[j] * w.sstd[j]) : 0.0;
-          if (!std_l) lam *= bStd;
-          v += lam;
-        }
+        v = qn::wls_a(hd, aa[r <= j ? pk(r, j) : pk(j, r)], wSum, w.sstd[r], w.sstd[j], r == j, std_f, std_l);
       } else if (r == nf && j == nf) {
         v = 1.0;
       } else {
@@ -135,9 +102,7 @@ __global__ __launch_bounds__(kQT) void wls_qn_grid_kernel(const double* __restri
         v = (fit_intercept && j == k - 1) ? bBar : 0.0;
       } else {
         const double xj = w.x[j];
-        v = xj + w.d[j] * alpha;
-        const double orth = xj != 0.0 ? sgn(xj) : sgn(-w.ag[j]);
-        if (sgn(v) != orth) v = 0.0;
+        v = qn::orthant_project(xj, xj + w.d[j] * alpha, w.ag[j]);
       }
       nxs[j] = v;
     }
@@ -145,7 +110,7 @@ __global__ __launch_bounds__(kQT) void wls_qn_grid_kernel(const double* __restri
     if (fit_intercept) {  // intercept re-set to bBar - coef . aBar (in place, as the host cost does)
       double p = 0.0;
       for (int j = t; j < nf; j += kQT) p += nxs[j] * w.bar[j];
-      const double dp = block_sum(p, red);
+      const double dp = block_sum<kQW>(p, red);
       if (t == 0) nxs[nf] = bBar - dp;
       __syncthreads();
     }
@@ -181,15 +146,7 @@ __global__ __launch_bounds__(kQT) void wls_qn_grid_kernel(const double* __restri
 #pragma unroll
       for (int i = 0; i < kQW; ++i) acc += rowp[t * kQW + i];
       const double xr = nxs[r], g = acc - w.ab[r], l = w.l1[r];
-      double ag = g;
-      if (l != 0.0) {
-        if (xr == 0.0) {
-          const double dp = g + l, dm = g - l;
-          ag = dm > 0.0 ? dm : (dp < 0.0 ? dp : 0.0);
-        } else {
-          ag = g + sgn(xr) * l;
-        }
-      }
+      const double ag = qn::pseudo_gradient(xr, g, l);
       part[0] = xr * w.ab[r];
       part[1] = xr * acc;
       part[2] = fabs(l * xr);
@@ -203,7 +160,7 @@ __global__ __launch_bounds__(kQT) void wls_qn_grid_kernel(const double* __restri
     double* slab = w.part + (int64_t)parity * B * kParts + (int64_t)b * kParts;
 #pragma unroll
     for (int q = 0; q < kParts; ++q) {
-      const double s = block_sum(part[q], red);
+      const double s = block_sum<kQW>(part[q], red);
       if (t == 0) slab[q] = s;
     }
     __threadfence();
@@ -243,36 +200,17 @@ __global__ __launch_bounds__(kQT) void wls_qn_grid_kernel(const double* __restri
   evaluate(0, 0.0, value, adj, dd0, agag);
   accept(false);
   const double init_adj = adj;
-  double fv[kFvals];
-#pragma unroll
-  for (int i = 0; i < kFvals; ++i) fv[i] = 0.0;
-  int nfv = 1;
-  fv[kFvals - 1] = __builtin_inf();
+  qn::FvWindow fvals;
+  fvals.init();
   int iter = 0, H = 0;
   bool search_failed = false, failed_once = false, overflow = false;
-  auto record = [&](double v) {
-    if (H >= hist_cap) {
-      overflow = true;
-      return;
-    }
-    if (b == 0 && t == 0) out[nf + 9 + H] = v;
-    ++H;
+  // the end of a loop pass: one history value, then the convergence tests
+  auto end_pass = [&]() -> int {
+    const int slot = qn::record(H, hist_cap, overflow);
+    if (slot >= 0 && b == 0 && t == 0) out[nf + 9 + slot] = adj;
+    return qn::converged(max_iter, iter, fvals.n, fvals.max(), adj, init_adj, value, sqrt(agag), tol, search_failed);
   };
-  auto converged = [&]() -> int {
-    if (max_iter >= 0 && iter >= max_iter) return 0;
-    if (nfv >= 2) {
-      double mx = -__builtin_inf();
-#pragma unroll
-      for (int i = 0; i < kFvals; ++i)
-        if (i >= kFvals - nfv) mx = fmax(mx, fv[i]);
-      if (fabs(adj - mx) <= tol * fabs(init_adj)) return 1;
-    }
-    if (sqrt(agag) <= fmax(tol * fabs(value), 1e-8)) return 2;
-    if (search_failed) return 3;
-    return -1;
-  };
-  record(adj);
-  int why = converged();
+  int why = end_pass();
   int pass = 0;  // loop passes (uniform over the grid): w.scal is double-buffered by its parity
   while (why < 0 && !overflow) {
     // scal[4 * (pass & 1) ..]: block 0 writes this pass's direction scalars while a slow block may
@@ -289,7 +227,7 @@ __global__ __launch_bounds__(kQT) void wls_qn_grid_kernel(const double* __restri
           const int j = t + kQT * s;
           if (j < k) v += p[j] * q[j];
         }
-        return block_sum(v, red);
+        return block_sum<kQW>(v, red);
       };
       auto dotr = [&](const double* p, const double (&q)[SL]) {
         double v = 0.0;
@@ -298,7 +236,7 @@ __global__ __launch_bounds__(kQT) void wls_qn_grid_kernel(const double* __restri
           const int j = t + kQT * s;
           if (j < k) v += p[j] * q[s];
         }
-        return block_sum(v, red);
+        return block_sum<kQW>(v, red);
       };
       bool fail = false;
       double diag = 1.0;
@@ -353,7 +291,7 @@ __global__ __launch_bounds__(kQT) void wls_qn_grid_kernel(const double* __restri
       for (int s = 0; s < SL; ++s) {
         const int j = t + kQT * s;
         d[s] = -d[s];
-        if (!(d[s] * agr[s] < 0.0)) d[s] = 0.0;
+        d[s] = qn::orthant_direction(d[s], agr[s]);
         if (j < k) {
           w.d[j] = d[s];
           pd += agr[s] * d[s];
@@ -361,7 +299,7 @@ __global__ __launch_bounds__(kQT) void wls_qn_grid_kernel(const double* __restri
           pg += g * g;
         }
       }
-      const double initd = block_sum(pd, red), gg = block_sum(pg, red);
+      const double initd = block_sum<kQW>(pd, red), gg = block_sum<kQW>(pg, red);
       if (t == 0) {
         scal[0] = initd;
         scal[1] = gg;
@@ -372,51 +310,29 @@ __global__ __launch_bounds__(kQT) void wls_qn_grid_kernel(const double* __restri
     grid_sync();
     const double initd = scal[0], gg = scal[1];
     bool fail = scal[2] != 0.0;
-    double alpha = 0.0, nv = 0.0, nadj = 0.0, nagag = 0.0;
-    if (!fail) {  // backtracking line search (Breeze BacktrackingLineSearch as OWLQN configures it)
-      const double initfval = adj;
-      const double shrink = iter < 1 ? 0.1 : 0.5, grow = 2.1, c1 = 1e-4, c2 = 0.9;
-      alpha = iter < 1 ? 0.5 / sqrt(gg) : 1.0;
-      double f, fd;
-      evaluate(1, alpha, nv, f, fd, nagag);
-      for (int it = 0;; ++it) {
-        double mult;
-        if (f > initfval + alpha * initd * c1) mult = shrink;
-        else if (fd < c2 * initd) mult = grow;
-        else if (fd > -c2 * initd) mult = shrink;
-        else mult = 1.0;
-        if (mult == 1.0) break;
-        const double na = alpha * mult;
-        if (it >= 20 || na < 1e-10 || na > 1e10) {
-          fail = true;
-          break;
-        }
-        alpha = na;
-        evaluate(1, alpha, nv, f, fd, nagag);
-        if (it + 1 >= 20) break;
-      }
-      nadj = f;
+    double nv = 0.0, nadj = 0.0, nagag = 0.0;
+    if (!fail) {  // the backtracking line search
+      qn::Backtrack ls;
+      ls.start(iter, adj, initd, sqrt(gg));
+      double fd;
+      evaluate(1, ls.alpha, nv, nadj, fd, nagag);
+      qn::Step step;
+      while ((step = ls.next(nadj, fd)) == qn::kEval) evaluate(1, ls.alpha, nv, nadj, fd, nagag);
+      fail = step == qn::kFail;
     }
-    if (!fail) {  // the last evaluation was at alpha: its candidates are the new state
+    if (!fail) {  // the last evaluation was at the accepted step: its candidates are the new state
       accept(true);
       hh = hh < kMem ? hh + 1 : kMem;
-#pragma unroll
-      for (int i = 0; i < kFvals - 1; ++i) fv[i] = fv[i + 1];
-      fv[kFvals - 1] = nv;
-      nfv = nfv < kFvals ? nfv + 1 : kFvals;
+      fvals.push(nv);
       value = nv;
       adj = nadj;
       agag = nagag;
       ++iter;
       failed_once = false;
-    } else if (!failed_once) {
-      failed_once = true;
+    } else if (qn::note_failure(failed_once, search_failed)) {
       hh = 0;
-    } else {
-      search_failed = true;
     }
-    record(adj);
-    why = converged();
+    why = end_pass();
   }
   if (b != 0) return;
   if (overflow) {

@@ -27,6 +27,7 @@
 #include <hip/hip_runtime.h>
 
 #include "common.h"
+#include "qn_ctl.h"
 #include "wls_small.h"
 
 namespace dq4ml {
@@ -199,18 +200,16 @@ __global__ __launch_bounds__(kThreads) void wls_gj_kernel(const double* __restri
 // ---- K6-small, L1 branch: OWLQN in one wave ---------------------------------------------------
 // The OWLQN branch of WeightedLeastSquares (regParam > 0, elasticNetParam > 0: the lab's own
 // LinearRegression at DataQuality4MachineLearningApp.java:120-126) for k <= 64 * SLOTS, entirely
-// on the device: standardize -> Breeze OWLQN (m = 10 two-loop on the pseudo-gradient, orthant
-// projection, backtracking line search, FunctionValuesConverged over 20 values, one history reset
-// on a failed search; csrc/host/solvers.cpp is the reference implementation) -> un-standardize.
+// on the device: standardize -> Breeze OWLQN (m = 10 two-loop on the pseudo-gradient; the
+// standardization, the orthant rules, the line search, the convergence tests and the failure rule
+// are qn_ctl.h's; csrc/host/solvers.cpp is the reference implementation) -> un-standardize.
 // One wave: lane l owns vector elements l + 64 s; dot products are wave reductions, every scalar
 // decision is computed redundantly by all lanes (uniform control flow, no barriers except around
 // the dspmv broadcast of x); the packed standardized system and the m = 10 history live in LDS.
 // out = [coef(nf), intercept, status, count, wSum, wwSum, bSum, bbSum, H, reason, history(H)]
 // status: 0 ok | 1, 2, 3 label / weight short-circuits (host owns them) | 8 history capacity
-// exceeded | 9 no L1 term (host: L-BFGS).  reason: 0 max iterations, 1 function values converged,
-// 2 gradient converged, 3 search failed.
+// exceeded | 9 no L1 term (host: L-BFGS).  reason: qn_ctl.h's.
 constexpr int kQnMem = 10;
-constexpr int kQnFvals = 20;
 
 template <int SLOTS>
 __global__ __launch_bounds__(64) void wls_qn_kernel(const double* __restrict__ flat, int nf, int fit_intercept,
@@ -226,27 +225,17 @@ __global__ __launch_bounds__(64) void wls_qn_kernel(const double* __restrict__ f
   const double* aSum = flat + 5;
   const double* abSum = flat + 5 + nf;
   const double* aa = flat + 5 + 2 * nf;
-  const double count = flat[0], wSum = flat[1], bSum = flat[3], bbSum = flat[4];
+  const double wSum = flat[1];
   if (lane < 5) out[nf + 2 + lane] = flat[lane];
-  const double rawBBar = wSum > 0.0 ? bSum / wSum : 0.0;
-  const double rawBStd = wSum > 0.0 ? sqrt(fmax(bbSum / wSum - rawBBar * rawBBar, 0.0)) : 0.0;
-  if (wSum <= 0.0 || rawBStd == 0.0) {
-    if (lane == 0) out[nf + 1] = wSum <= 0.0 ? (count > 0 ? 1.0 : 2.0) : 3.0;
+  const qn::WlsHead hd = qn::wls_head(flat[0], wSum, flat[3], flat[4], reg, enet);
+  if (hd.status != 0) {
+    if (lane == 0) out[nf + 1] = (double)hd.status;
     return;
   }
-  const double bStd = rawBStd, bBar = rawBBar / bStd, bbBar = bbSum / wSum / (bStd * bStd);
-  const double eff_reg = reg / bStd, eff_l1 = enet * eff_reg, eff_l2 = (1.0 - enet) * eff_reg;
-  if (eff_l1 == 0.0) {
-    if (lane == 0) out[nf + 1] = 9.0;
-    return;
-  }
+  const double bStd = hd.bStd, bBar = hd.bBar, bbBar = hd.bbBar;
   for (int i = lane; i < KMAX; i += 64) {
     double sd = 0.0, bar = 0.0;
-    if (i < nf) {
-      const double m = aSum[i] / wSum;
-      sd = sqrt(fmax(aa[pku(i, i)] / wSum - m * m, 0.0));
-      bar = sd == 0.0 ? 0.0 : m / sd;
-    }
+    if (i < nf) qn::wls_feature(aSum[i], aa[pku(i, i)], wSum, sd, bar);
     sStd[i] = sd;
     sBar[i] = bar;
   }
@@ -254,18 +243,8 @@ __global__ __launch_bounds__(64) void wls_qn_kernel(const double* __restrict__ f
   for (int j = 0; j < k; ++j)
     for (int i = lane; i <= j; i += 64) {
       double v;
-      if (j < nf) {
-        const double den = sStd[i] * sStd[j];
-        v = den == 0.0 ? 0.0 : aa[pku(i, j)] / wSum / den;
-        if (i == j) {
-          double lam = eff_l2;
-          if (!std_f) lam = sStd[j] != 0.0 ? lam / (sStd[j] * sStd[j]) : 0.0;
-          if (!std_l) lam *= bStd;
-          v += lam;
-        }
-      } else {
-        v = i < nf ? sBar[i] : 1.0;
-      }
+      if (j < nf) v = qn::wls_a(hd, aa[pku(i, j)], wSum, sStd[i], sStd[j], i == j, std_f, std_l);
+      else v = i < nf ? sBar[i] : 1.0;
       Ap[pku(i, j)] = v;
     }
   double ab[SLOTS], l1[SLOTS], bar[SLOTS];
@@ -273,9 +252,8 @@ __global__ __launch_bounds__(64) void wls_qn_kernel(const double* __restrict__ f
   for (int s = 0; s < SLOTS; ++s) {
     const int i = lane + 64 * s;
     const double sd = i < nf ? sStd[i] : 0.0;
-    ab[s] = i < nf ? (sd == 0.0 ? 0.0 : abSum[i] / wSum / (sd * bStd)) : (i == nf && fit_intercept ? bBar : 0.0);
-    l1[s] = i < k ? (std_f ? eff_l1 : (sd != 0.0 ? eff_l1 / sd : 0.0)) : 0.0;
-    if (fit_intercept && i == nf) l1[s] = 0.0;
+    ab[s] = i < nf ? qn::wls_ab(abSum[i], wSum, sd, bStd) : (i == nf && fit_intercept ? bBar : 0.0);
+    l1[s] = i < nf ? qn::wls_l1(hd, sd, std_f) : 0.0;
     bar[s] = i < nf ? sBar[i] : 0.0;
   }
   __syncthreads();
@@ -286,7 +264,6 @@ __global__ __launch_bounds__(64) void wls_qn_kernel(const double* __restrict__ f
     for (int s = 0; s < SLOTS; ++s) v += a[s] * b[s];
     return wave_sum_f64(v);
   };
-  auto sgn = [](double v) { return v > 0.0 ? 1.0 : (v < 0.0 ? -1.0 : 0.0); };
   // f(x) = 1/2 bbBar - x.ab + 1/2 x^T A x, g = A x - ab; the intercept is re-set to
   // bBar - coef.aBar first (in place, as the host cost function writes into the optimizer's x)
   auto cost = [&](double* x, double* g) {
@@ -324,16 +301,8 @@ __global__ __launch_bounds__(64) void wls_qn_kernel(const double* __restrict__ f
 #pragma unroll
     for (int s = 0; s < SLOTS; ++s) {
       const double l = l1[s];
-      ag[s] = g[s];
-      if (l != 0.0) {
-        p += fabs(l * x[s]);
-        if (x[s] == 0.0) {
-          const double dp = g[s] + l, dm = g[s] - l;
-          ag[s] = dm > 0.0 ? dm : (dp < 0.0 ? dp : 0.0);
-        } else {
-          ag[s] = g[s] + sgn(x[s]) * l;
-        }
-      }
+      if (l != 0.0) p += fabs(l * x[s]);
+      ag[s] = qn::pseudo_gradient(x[s], g[s], l);
     }
     return v + wave_sum_f64(p);
   };
@@ -343,42 +312,21 @@ __global__ __launch_bounds__(64) void wls_qn_kernel(const double* __restrict__ f
   double value = cost(x, grad);
   double adj = adjust(x, grad, value, agrad);
   const double init_adj = adj;
-  double fv[kQnFvals];
-#pragma unroll
-  for (int i = 0; i < kQnFvals; ++i) fv[i] = 0.0;
-  int nfv = 1;
-  fv[kQnFvals - 1] = __builtin_inf();
+  qn::FvWindow fvals;
+  fvals.init();
   int iter = 0, hh = 0, head = 0, H = 0;
   bool search_failed = false, failed_once = false, overflow = false;
-  auto record = [&](double v) {
-    if (H >= hist_cap) {
-      overflow = true;
-      return;
-    }
-    if (lane == 0) out[nf + 9 + H] = v;
-    ++H;
-  };
-  auto converged = [&]() -> int {
-    if (max_iter >= 0 && iter >= max_iter) return 0;
-    if (nfv >= 2) {
-      double mx = -__builtin_inf();
-#pragma unroll
-      for (int i = 0; i < kQnFvals; ++i)
-        if (i >= kQnFvals - nfv) mx = fmax(mx, fv[i]);
-      if (fabs(adj - mx) <= tol * fabs(init_adj)) return 1;
-    }
-    if (sqrt(dot(agrad, agrad)) <= fmax(tol * fabs(value), 1e-8)) return 2;
-    if (search_failed) return 3;
-    return -1;
+  // the end of a loop pass: one history value, then the convergence tests
+  auto end_pass = [&]() -> int {
+    const int slot = qn::record(H, hist_cap, overflow);
+    if (slot >= 0 && lane == 0) out[nf + 9 + slot] = adj;
+    return qn::converged(max_iter, iter, fvals.n, fvals.max(), adj, init_adj, value, sqrt(dot(agrad, agrad)), tol,
+                         search_failed);
   };
   // projected step x + a d, then (adjusted value, adjusted directional derivative)
   auto take_step = [&](const double* d, double a, double* nx) {
 #pragma unroll
-    for (int s = 0; s < SLOTS; ++s) {
-      nx[s] = x[s] + d[s] * a;
-      const double orth = x[s] != 0.0 ? sgn(x[s]) : sgn(-agrad[s]);
-      if (sgn(nx[s]) != orth) nx[s] = 0.0;
-    }
+    for (int s = 0; s < SLOTS; ++s) nx[s] = qn::orthant_project(x[s], x[s] + d[s] * a, agrad[s]);
   };
   auto phi = [&](const double* d, double a, double& dd) {
     double nx[SLOTS], g[SLOTS], ag[SLOTS];
@@ -388,8 +336,7 @@ __global__ __launch_bounds__(64) void wls_qn_kernel(const double* __restrict__ f
     dd = dot(ag, d);
     return av;
   };
-  record(adj);
-  int why = converged();
+  int why = end_pass();
   while (why < 0 && !overflow) {
     bool fail = false;
     double d[SLOTS];
@@ -437,39 +384,21 @@ __global__ __launch_bounds__(64) void wls_qn_kernel(const double* __restrict__ f
         }
       }
 #pragma unroll
-      for (int s = 0; s < SLOTS; ++s) {
-        d[s] = -d[s];
-        if (!(d[s] * agrad[s] < 0.0)) d[s] = 0.0;
-      }
+      for (int s = 0; s < SLOTS; ++s) d[s] = qn::orthant_direction(-d[s], agrad[s]);
     }
-    double alpha = 0.0;
-    if (!fail) {  // backtracking line search (Breeze BacktrackingLineSearch as OWLQN configures it)
-      const double initfval = adj;
-      const double shrink = iter < 1 ? 0.1 : 0.5, grow = 2.1, c1 = 1e-4, c2 = 0.9;
+    qn::Backtrack ls;
+    if (!fail) {  // the backtracking line search
       double initd, fd;
       phi(d, 0.0, initd);
-      alpha = iter < 1 ? 0.5 / sqrt(dot(grad, grad)) : 1.0;
-      double f = phi(d, alpha, fd);
-      for (int it = 0;; ++it) {
-        double mult;
-        if (f > initfval + alpha * initd * c1) mult = shrink;
-        else if (fd < c2 * initd) mult = grow;
-        else if (fd > -c2 * initd) mult = shrink;
-        else mult = 1.0;
-        if (mult == 1.0) break;
-        const double na = alpha * mult;
-        if (it >= 20 || na < 1e-10 || na > 1e10) {
-          fail = true;
-          break;
-        }
-        alpha = na;
-        f = phi(d, alpha, fd);
-        if (it + 1 >= 20) break;
-      }
+      ls.start(iter, adj, initd, iter < 1 ? sqrt(dot(grad, grad)) : 0.0);  // (|g| seeds the first step only)
+      double f = phi(d, ls.alpha, fd);
+      qn::Step step;
+      while ((step = ls.next(f, fd)) == qn::kEval) f = phi(d, ls.alpha, fd);
+      fail = step == qn::kFail;
     }
     if (!fail) {
       double nx[SLOTS], g[SLOTS], ag[SLOTS];
-      take_step(d, alpha, nx);
+      take_step(d, ls.alpha, nx);
       const double v = cost(nx, g);
       const double av = adjust(nx, g, v, ag);
       head = (head + kQnMem - 1) % kQnMem;
@@ -480,22 +409,15 @@ __global__ __launch_bounds__(64) void wls_qn_kernel(const double* __restrict__ f
         x[s] = nx[s], grad[s] = g[s], agrad[s] = ag[s];
       }
       hh = hh < kQnMem ? hh + 1 : kQnMem;
-#pragma unroll
-      for (int i = 0; i < kQnFvals - 1; ++i) fv[i] = fv[i + 1];
-      fv[kQnFvals - 1] = v;
-      nfv = nfv < kQnFvals ? nfv + 1 : kQnFvals;
+      fvals.push(v);
       value = v;
       adj = av;
       ++iter;
       failed_once = false;
-    } else if (!failed_once) {
-      failed_once = true;
+    } else if (qn::note_failure(failed_once, search_failed)) {
       hh = 0;
-    } else {
-      search_failed = true;
     }
-    record(adj);
-    why = converged();
+    why = end_pass();
   }
   if (overflow) {
     if (lane == 0) out[nf + 1] = 8.0;

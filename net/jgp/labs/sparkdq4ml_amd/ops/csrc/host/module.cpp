@@ -82,26 +82,28 @@ PYBIND11_MODULE(_dq4ml_host, m) {
     return to_np(cholesky_inverse(k, to_vec(ap)));
   });
 
-  m.def(
-      "quasi_newton",
-      [](double bBar, double bbBar, py::array_t<double, py::array::c_style | py::array::forcecast> ab,
-         py::array_t<double, py::array::c_style | py::array::forcecast> aa,
-         py::array_t<double, py::array::c_style | py::array::forcecast> aBar, bool fit_intercept, int max_iter,
-         double tol, py::object l1, int memory) {
-        std::vector<double> l1v;
-        if (!l1.is_none()) l1v = to_vec(l1.cast<py::array_t<double, py::array::c_style | py::array::forcecast>>());
-        const int k = static_cast<int>(ab.size());
-        if (aa.size() != (py::ssize_t)k * (k + 1) / 2) throw std::invalid_argument("quasi_newton: aa size");
-        QNResult r;
-        {
-          auto abv = to_vec(ab), aav = to_vec(aa), abar = to_vec(aBar);
-          py::gil_scoped_release nogil;
-          r = quasi_newton(bBar, bbBar, abv, aav, abar, fit_intercept, max_iter, tol, l1v, memory);
-        }
-        return py::make_tuple(to_np(r.x), to_np(r.objective_history), r.converged_reason);
-      },
-      py::arg("bBar"), py::arg("bbBar"), py::arg("ab"), py::arg("aa"), py::arg("aBar"), py::arg("fit_intercept"),
-      py::arg("max_iter"), py::arg("tol"), py::arg("l1") = py::none(), py::arg("memory") = 10);
+  for (const bool ctl : {false, true})  // quasi_newton_ctl: the same fit steered by qn_ctl.h
+    m.def(
+        ctl ? "quasi_newton_ctl" : "quasi_newton",
+        [ctl](double bBar, double bbBar, py::array_t<double, py::array::c_style | py::array::forcecast> ab,
+              py::array_t<double, py::array::c_style | py::array::forcecast> aa,
+              py::array_t<double, py::array::c_style | py::array::forcecast> aBar, bool fit_intercept, int max_iter,
+              double tol, py::object l1, int memory) {
+          std::vector<double> l1v;
+          if (!l1.is_none()) l1v = to_vec(l1.cast<py::array_t<double, py::array::c_style | py::array::forcecast>>());
+          const int k = static_cast<int>(ab.size());
+          if (aa.size() != (py::ssize_t)k * (k + 1) / 2) throw std::invalid_argument("quasi_newton: aa size");
+          QNResult r;
+          {
+            auto abv = to_vec(ab), aav = to_vec(aa), abar = to_vec(aBar);
+            py::gil_scoped_release nogil;
+            r = (ctl ? quasi_newton_ctl : quasi_newton)(bBar, bbBar, abv, aav, abar, fit_intercept, max_iter, tol, l1v,
+                                                        memory);
+          }
+          return py::make_tuple(to_np(r.x), to_np(r.objective_history), r.converged_reason);
+        },
+        py::arg("bBar"), py::arg("bbBar"), py::arg("ab"), py::arg("aa"), py::arg("aBar"), py::arg("fit_intercept"),
+        py::arg("max_iter"), py::arg("tol"), py::arg("l1") = py::none(), py::arg("memory") = 10);
 
   m.def("csv_infer_field", [](const std::string& s) { return csv_infer_field(s.data(), s.size()); });
   m.def("csv_merge_types", &csv_merge_types);

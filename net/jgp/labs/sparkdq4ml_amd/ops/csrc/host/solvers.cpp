@@ -7,6 +7,8 @@
 // || |adjusted gradient| <= max(tol*|f|, 1e-8) || search failed twice.
 #include "solvers.h"
 
+#include "qn_ctl.h"
+
 #include <algorithm>
 #include <cmath>
 #include <deque>
@@ -394,6 +396,103 @@ QNResult quasi_newton(double bBar, double bbBar, const std::vector<double>& ab,
   }
   res.x = st.x;
   res.converged_reason = why;
+  return res;
+}
+
+// The same fit with every decision taken by qn_ctl.h (the controller of the device solvers) over
+// the same cost function and history: bit for bit quasi_newton's result, which is what the CPU
+// test of the shared controller asserts.
+QNResult quasi_newton_ctl(double bBar, double bbBar, const std::vector<double>& ab,
+                          const std::vector<double>& aa_packed, const std::vector<double>& aBar,
+                          bool fit_intercept, int max_iter, double tol, const std::vector<double>& l1,
+                          int memory) {
+  const int nf = static_cast<int>(aBar.size());
+  const int k = fit_intercept ? nf + 1 : nf;
+  if (static_cast<int>(ab.size()) != k) throw std::invalid_argument("ab has wrong length");
+  const bool owlqn = !l1.empty();
+  if (owlqn && static_cast<int>(l1.size()) != k) throw std::invalid_argument("l1 has wrong length");
+  static const char* const kReasons[] = {"max iterations", "function values converged", "gradient converged",
+                                         "search failed"};
+  CostFun cf{bBar, bbBar, ab, aa_packed, aBar, fit_intercept, nf, k};
+  // (value, gradient, pseudo-gradient) at x -> the adjusted value
+  auto eval = [&](std::vector<double>& x, std::vector<double>& g, std::vector<double>& ag, double& v) {
+    v = cf.calculate(x, g);
+    ag = g;
+    double av = v;
+    for (int i = 0; owlqn && i < k; ++i) {
+      if (l1[i] != 0.0) av += std::fabs(l1[i] * x[i]);
+      ag[i] = qn::pseudo_gradient(x[i], g[i], l1[i]);
+    }
+    return av;
+  };
+  std::vector<double> x(k, 0.0), g, ag, dir, nx(k), ng, nag;
+  if (fit_intercept) x[k - 1] = bBar;
+  double value, nv = 0.0, nadj = 0.0;
+  double adj = eval(x, g, ag, value);
+  const double init_adj = adj;
+  History hist{memory};
+  qn::FvWindow fvals;
+  fvals.init();
+  int iter = 0, H = 0, failed_once = 0, search_failed = 0, overflow = 0;
+  QNResult res;
+  auto end_pass = [&]() {
+    if (qn::record(H, std::numeric_limits<int>::max(), overflow) >= 0) res.objective_history.push_back(adj);
+    return qn::converged(max_iter, iter, fvals.n, fvals.max(), adj, init_adj, value, norm2(ag), tol, search_failed != 0);
+  };
+  // the trial proj(x + a dir) -> (nx, ng, nag, nv, nadj) and its directional derivative
+  auto trial = [&](double a) {
+    for (int i = 0; i < k; ++i) {
+      nx[i] = x[i] + dir[i] * a;
+      if (owlqn) nx[i] = qn::orthant_project(x[i], nx[i], ag[i]);
+    }
+    nadj = eval(nx, ng, nag, nv);
+    return dot(owlqn ? nag : ng, dir);
+  };
+  int why = end_pass();
+  while (why < 0) {
+    bool fail = false;
+    try {
+      dir = hist.apply(owlqn ? ag : g);
+    } catch (const FirstOrderException&) {
+      fail = true;
+    }
+    if (!fail) {
+      qn::Step step;
+      if (owlqn)
+        for (int i = 0; i < k; ++i) dir[i] = qn::orthant_direction(dir[i], ag[i]);
+      const double d0 = trial(0.0);
+      if (owlqn) {
+        qn::Backtrack ls;
+        ls.start(iter, adj, d0, norm2(g));
+        double fd = trial(ls.alpha);
+        while ((step = ls.next(nadj, fd)) == qn::kEval) fd = trial(ls.alpha);
+      } else {
+        qn::Wolfe ls;
+        step = ls.start(nv, d0, qn::lbfgs_first_step(iter, norm2(dir))) ? qn::kEval : qn::kFail;
+        while (step == qn::kEval) {
+          const double dd = trial(ls.alpha);
+          step = ls.next(nv, dd, 10, 10);
+        }
+        if (step == qn::kAccept && ls.alpha * norm2(g) < 1e-10) step = qn::kFail;  // StepSizeUnderflow
+      }
+      fail = step == qn::kFail;
+    }
+    if (!fail) {  // the last trial is the accepted point
+      std::vector<double> sdiff(k), gdiff(k);
+      for (int i = 0; i < k; ++i) sdiff[i] = nx[i] - x[i], gdiff[i] = ng[i] - g[i];
+      hist.update(sdiff, gdiff);
+      fvals.push(nv);
+      x = nx, g = ng, ag = nag, value = nv, adj = nadj;
+      ++iter;
+      failed_once = 0;
+    } else if (qn::note_failure(failed_once, search_failed)) {
+      hist.s.clear();
+      hist.y.clear();
+    }
+    why = end_pass();
+  }
+  res.x = x;
+  res.converged_reason = kReasons[why];
   return res;
 }
 

@@ -46,4 +46,11 @@ QNResult quasi_newton(double bBar, double bbBar, const std::vector<double>& ab,
                       bool fit_intercept, int max_iter, double tol, const std::vector<double>& l1,
                       int memory = 10);
 
+// quasi_newton with every decision taken by qn_ctl.h (the device solvers' controller): the same
+// result bit for bit.  For the CPU test of that controller; the fits call quasi_newton.
+QNResult quasi_newton_ctl(double bBar, double bbBar, const std::vector<double>& ab,
+                          const std::vector<double>& aa_packed, const std::vector<double>& aBar,
+                          bool fit_intercept, int max_iter, double tol, const std::vector<double>& l1,
+                          int memory = 10);
+
 }  // namespace dq4ml

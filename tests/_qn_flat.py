@@ -14,3 +14,14 @@ def _flat(nf, n, seed, w=False):
     packed = G[iu[0], iu[1]][order]
     head = [n, wv.sum(), (wv * wv).sum(), (wv * y).sum(), (wv * y * y).sum()]
     return np.concatenate([head, X.T @ wv, X.T @ (wv * y), packed])
+
+
+def _corr_flat(nf, n, seed, mix):
+    """Unweighted statistics of features that share a common factor (``mix`` of it in each)."""
+    rng = np.random.default_rng(seed)
+    X = mix * rng.standard_normal((n, 1)) + (1.0 - mix) * rng.standard_normal((n, nf))
+    y = X @ rng.standard_normal(nf) + 1.0 + 0.1 * rng.standard_normal(n)
+    iu = np.triu_indices(nf)
+    order = np.argsort(iu[0] + iu[1] * (iu[1] + 1) // 2)
+    G = X.T @ X
+    return np.concatenate([[n, n, n, y.sum(), (y * y).sum()], X.sum(0), X.T @ y, G[iu[0], iu[1]][order]])

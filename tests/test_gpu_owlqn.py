@@ -214,3 +214,121 @@ def test_qn_grid_kernel_history_reset_terminates():
         assert torch.equal(o[:used], outs[0][:used])  # same decisions on every run
     H = int(outs[0][d + 7])
     assert 1 <= H <= 2 * 60 + 8
+
+
+def _indefinite(flat, d, scale):
+    """The statistics with every covariance between different features scaled (past 1: indefinite)."""
+    flat = flat.copy()
+    W = flat[1]
+    mean = flat[5:5 + d] / W
+    i, j = np.triu_indices(d)
+    order = np.argsort(i + j * (j + 1) // 2)
+    ii, jj = i[order], j[order]
+    cov = flat[5 + 2 * d:] / W - mean[ii] * mean[jj]
+    cov = np.where(ii == jj, cov, scale * cov)
+    flat[5 + 2 * d:] = (cov + mean[ii] * mean[jj]) * W
+    return flat
+
+
+_REASONS = ("max iterations", "function values converged", "gradient converged", "search failed")
+
+
+@pytest.mark.parametrize("nf", [12, 100])  # one register slot per lane, and two
+def test_qn_kernel_history_reset_matches_native(nf):
+    """The recipe of ``test_qn_grid_kernel_history_reset_terminates`` on the one-wave kernel: the
+    failed searches and the history reset, deterministic run to run and as the host driver takes
+    them."""
+    from net.jgp.labs.sparkdq4ml_amd.models.optim import owlqn_result
+    from net.jgp.labs.sparkdq4ml_amd.ops import device
+
+    max_iter = 60
+    flat = _indefinite(_wide_flat(nf, 20_000, 11).cpu().numpy(), nf, 3.0)
+    t = torch.tensor(flat, device="cuda")
+    outs = [device.wls_qn_small(t, nf, True, 0.01, 1.0, True, True, max_iter, 1e-6) for _ in range(3)]
+    torch.cuda.synchronize()
+    H = int(outs[0][nf + 7])
+    assert 1 <= H <= 2 * max_iter + 8
+    for o in outs[1:]:
+        assert torch.equal(o[:nf + 9 + H], outs[0][:nf + 9 + H])
+    host = outs[0].cpu().numpy()
+    wls, _ = owlqn_result(host, nf)
+    r = _host(flat, nf, True, 0.01, 1.0, True, max_iter)
+    hist, ref = wls.objectiveHistory, np.asarray(r["objective_history"])
+    print(nf, "device", H, _REASONS[int(host[nf + 8])], "host", len(ref), r["converged_reason"])
+    assert _REASONS[int(host[nf + 8])] == r["converged_reason"]
+    assert hist[0] == ref[0]
+    m = min(len(hist), len(ref))
+    assert abs(len(hist) - len(ref)) <= 3
+    np.testing.assert_allclose(hist[:m], ref[:m], rtol=1e-8)
+    assert hist[-1] == pytest.approx(ref[-1], rel=1e-9)
+    np.testing.assert_allclose(wls.coefficients, r["coefficients"], rtol=1e-7, atol=1e-8)
+    assert wls.intercept == pytest.approx(r["intercept"], rel=1e-7, abs=1e-9)
+
+
+@pytest.mark.parametrize("nf,mix", [(12, 0.8), (100, 0.6)])  # one register slot per lane, and two
+def test_qn_kernel_failed_search_resets_history(nf, mix):
+    """The recipe above scales the covariances of independent features, which are near zero: its
+    fits never fail a search.  Features that share a common factor do: scaled by 3 their system is
+    indefinite enough for s.y < 0 (the host driver's history repeats a value at both sizes), so the
+    one-wave kernel's failed pass and history reset run.  The objective is unbounded below there
+    and the path chaotic, so only the kernel's own properties are asserted: the same decisions on
+    every run, the pass bound, and a failed pass in the history."""
+    from _qn_flat import _corr_flat
+
+    from net.jgp.labs.sparkdq4ml_amd.ops import device
+
+    max_iter = 60
+    t = torch.tensor(_indefinite(_corr_flat(nf, 4000, nf, mix), nf, 3.0), device="cuda")
+    outs = [device.wls_qn_small(t, nf, True, 0.01, 1.0, True, True, max_iter, 1e-6) for _ in range(3)]
+    torch.cuda.synchronize()
+    assert int(outs[0][nf + 1]) == 0
+    H = int(outs[0][nf + 7])
+    assert 1 <= H <= 2 * max_iter + 8
+    for o in outs[1:]:
+        assert torch.equal(o[:nf + 9 + H], outs[0][:nf + 9 + H])
+    hist = outs[0][nf + 9:nf + 9 + H].cpu().numpy()
+    print(nf, "H", H, "reason", int(outs[0][nf + 8]), "failed passes", int(np.sum(hist[1:] == hist[:-1])))
+    assert np.any(hist[1:] == hist[:-1])
+
+
+@pytest.mark.parametrize("max_iter", [0, 1])
+@pytest.mark.parametrize("nf,reg,rtol", [(5, 0.1, 1e-7), (130, 0.01, 1e-6)])  # one wave, grid
+def test_qn_kernels_stop_at_max_iter(nf, reg, rtol, max_iter):
+    from _qn_flat import _flat
+
+    from net.jgp.labs.sparkdq4ml_amd.models.optim import owlqn_result
+    from net.jgp.labs.sparkdq4ml_amd.ops import device
+
+    flat = _flat(nf, 4000, nf) if nf == 5 else _wide_flat(nf, 20_000, nf).cpu().numpy()
+    out = device.wls_qn_small(torch.tensor(flat, device="cuda"), nf, True, reg, 1.0, True, True, max_iter, 1e-6)
+    host = out.cpu().numpy()
+    assert int(host[nf + 1]) == 0
+    assert int(host[nf + 7]) == max_iter + 1 and int(host[nf + 8]) == 0  # H, reason: max iterations
+    wls, _ = owlqn_result(host, nf)
+    r = _host(flat, nf, True, reg, 1.0, True, max_iter)
+    assert r["converged_reason"] == "max iterations" and len(r["objective_history"]) == max_iter + 1
+    np.testing.assert_allclose(wls.coefficients, r["coefficients"], rtol=rtol, atol=1e-8)
+    assert wls.intercept == pytest.approx(r["intercept"], rel=1e-7, abs=1e-9)
+
+
+@pytest.mark.parametrize("nf", [5, 130])  # one wave, grid
+def test_qn_kernels_report_history_overflow(nf):
+    """A history capacity the fit outgrows (the bindings called directly: ``device.wls_qn_small``
+    always sizes it from max_iter) ends the launch with status 8."""
+    from _qn_flat import _flat
+
+    from net.jgp.labs.sparkdq4ml_amd.ops import device, native
+
+    h = native.hip()
+    flat = torch.tensor(_flat(nf, 4000, nf), device="cuda") if nf == 5 else _wide_flat(nf, 20_000, nf)
+    cap, k = 1, nf + 1
+    out = torch.zeros(nf + 9 + cap, dtype=torch.float64, device="cuda")
+    st = device._stream()
+    if k <= int(h.WLS_QN_MAX_K):
+        h.wls_qn_small(flat.data_ptr(), nf, True, 0.05, 1.0, True, True, 10, 1e-6, cap, out.data_ptr(), st)
+    else:
+        nb = device._qn_grid_blocks(h, k)
+        work = torch.empty(int(h.wls_qn_grid_work(k, nb)), dtype=torch.float64, device="cuda")
+        h.wls_qn_grid(flat.data_ptr(), nf, True, 0.05, 1.0, True, True, 10, 1e-6, cap, work.data_ptr(), nb,
+                      out.data_ptr(), st)
+    assert int(out[nf + 1]) == 8
