@@ -861,17 +861,20 @@ void pack_wide(int eb, const PackSrcW* srcs_dev, int d, int64_t n, int nt, const
 }
 
 // statistics of a label shifted by t = aux[3] (y' = y - t) -> those of y, in place (f64), after the
-// head fold: Σy² += 2tΣy' + t²W, Σy += tW, Σx·y += tΣx (one thread per feature; thread 0 the
-// scalars, reading Σy' before anyone writes it)
+// head fold: Σy² += t²W, Σy = tW, Σx·y += tΣx (one thread per feature; thread 0 the scalars).
+// t is the live mean (wide_label_scales_kernel), so Σy' IS 0: the folded Σy' holds nothing but the
+// rounding of the two e4m3 digits, summed over the rows (the label takes few distinct values, so
+// it does not average out), and the features' un-shift would multiply it by every column's shift
+// (s·Σy in Σx·y).  The known 0 stands in for it.
 __global__ __launch_bounds__(256) void wide_unshift_label_kernel(double* __restrict__ out, int d,
                                                                  const double* __restrict__ aux) {
   const double t = aux[3];
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j < d) out[5 + d + j] += t * out[5 + j];
   if (j == 0) {
-    const double W = out[1], b = out[3];
-    out[4] += (2.0 * t) * b + (t * t) * W;
-    out[3] = b + t * W;
+    const double W = out[1];
+    out[4] += (t * t) * W;
+    out[3] = t * W;
   }
 }
 
