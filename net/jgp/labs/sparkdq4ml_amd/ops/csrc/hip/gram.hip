@@ -20,19 +20,18 @@
 //  * f64 mode (Spark-parity path) uses v_mfma_f64_16x16x4_f64 with 16-feature tiles and exact
 //    f64 side sums on the VALU.
 //  * Per-wave f32 (bf16 mode) / f64 accumulators -> deterministic in-block wave reduction in
-//    LDS -> one f64 partial slab per block -> ``gram_reduce`` sums slabs in a fixed order (no
-//    atomics: bit-reproducible run to run).
+//    LDS -> one f64 partial slab per block (format: gram_slab.h) -> ``gram_reduce`` sums slabs in
+//    a fixed order (no atomics: bit-reproducible run to run).
 #include <hip/hip_runtime.h>
 
 #include "common.h"
 #include "gram.h"
+#include "gram_slab.h"
 
 namespace dq4ml {
 
 namespace {
 
-constexpr int kBlock = 256;  // f64 kernel: 4 waves
-constexpr int kWavesPerBlock = kBlock / kWave;
 // bf16 kernel: 8 waves per block -- one per CU at <= 256 VGPRs for d <= 64, and for d <= 32
 // unmasked (NT 1, XMODE 0) two co-resident per CU at <= 128 VGPRs (since round 5 -- the 16-wave
 // block lost), so one block's ramp and reduction overlap the other's stream and the next pass's
@@ -64,11 +63,6 @@ __device__ __forceinline__ double load_as_f64(const void* p, int dt, int64_t i) 
 }
 
 // per-row scalars of row r (lane = row): liveness, weight, label
-struct RowVals {
-  bool live;
-  double w, y, wy;
-};
-
 __device__ __forceinline__ RowVals row_vals(const GramArgs& a, int64_t r) {
   RowVals v{false, 0.0, 0.0, 0.0};
   if (r < a.n) {
@@ -125,19 +119,6 @@ __device__ __forceinline__ RowVals row_vals(const GramArgs& a, int64_t r, LabelB
   }
   return v;
 }
-
-struct RowAcc {
-  double cnt = 0, ws = 0, wws = 0, bs = 0, bbs = 0;
-  __device__ __forceinline__ void add(const RowVals& v) {
-    if (v.live) {
-      cnt += 1.0;
-      ws += v.w;
-      wws += v.w * v.w;
-      bs += v.wy;
-      bbs += v.wy * v.y;
-    }
-  }
-};
 
 // ---- 32 rows of one feature as 4 bf16x8 fragments --------------------------------------------
 template <typename T>
@@ -220,7 +201,7 @@ __device__ __forceinline__ void weight_frags(bf16x8 (&fr)[4], const float* wl /*
 // slab element o (storage order: head, then T x T tiles of the row-major upper pairs I <= J < NT)
 // -> its packed-upper destination; lower halves of the diagonal tiles and padding features drop
 __device__ __forceinline__ void fold_store(int o, double t, int d, int T, int NT, double* __restrict__ out) {
-  const int head = 5 + 2 * d;
+  const int head = slab_head(d);
   if (o < head) {
     out[o] = t;
     return;
@@ -234,15 +215,6 @@ __device__ __forceinline__ void fold_store(int o, double t, int d, int T, int NT
   const int J = I + rem;
   const int64_t i = (int64_t)I * T + r, j = (int64_t)J * T + cc;
   if (i <= j && j < d) out[head + i + j * (j + 1) / 2] = t;
-}
-
-// Slab stores: the slabs are folded by gram_fold_kernel after the kernel boundary (an in-kernel
-// fold by the last block of each XCD group was measured slower at the 8-GPU shard: 155 us vs
-// 142-148 us per fit, profiles/r3_fixed_cost.md; removed in round 4).  Relaxed agent-scope
-// stores write through to memory (nothing is left dirty in this XCD's L2 for the fold kernel's
-// boundary to flush) -- the form the round-3 headline was measured with.
-__device__ __forceinline__ void slab_put(double* p, double v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // ---- 12-bit packed tiles (gram.h: pack_tiles) -------------------------------------------------
@@ -337,15 +309,8 @@ gram_tall_bf16_kernel(GramArgs a) {
   auto compute_rv = [&](const RowVals& rv, bf16x8 (&fr)[NT][4]) {
     // 1) per-row scalars, lane = row
     ra.add(rv);
-    {
-      const float w_hi = (float)(__bf16)(float)rv.w;
-      const __bf16 wy_hi = (__bf16)(float)rv.wy;
-      wl[0 * 64 + lane] = (__bf16)(float)rv.w;
-      wl[1 * 64 + lane] = (__bf16)(float)(rv.w - (double)w_hi);
-      wl[2 * 64 + lane] = wy_hi;
-      wl[3 * 64 + lane] = (__bf16)(float)(rv.wy - (double)(float)wy_hi);
-      if (XMODE == 2) wrow[lane] = (float)rv.w;
-    }
+    stage_w_stripe(wl, lane, rv);
+    if (XMODE == 2) wrow[lane] = (float)rv.w;
     const uint64_t live_bits = __ballot(rv.live);
     __builtin_amdgcn_wave_barrier();
     // 2) W fragments (lanes f < 4 read their column; everyone else multiplies zeros)
@@ -622,18 +587,20 @@ gram_tall_bf16_kernel(GramArgs a) {
   }
 
   // ---- block reduction: fixed-shape tree over the waves (deterministic), 4 rounds ------------
+  // (SlabTree32<NT, W>::reduce_and_store of gram_slab.h, kept in line here: behind the call this
+  // kernel's main loops get other registers)
+  typedef SlabTree32<NT, Geo::kWaves> Tree;
   constexpr int W = Geo::kWaves;
-  constexpr int NV = (NPAIR + NT) * 16;  // f32 accumulator values per lane
+  constexpr int NV = Tree::NV;
   const int d = a.d;
-  double sc[5] = {ra.cnt, ra.ws, ra.wws, ra.bs, ra.bbs};
-#pragma unroll
-  for (int k = 0; k < 5; ++k) sc[k] = wave_sum_f64(sc[k]);
+  double sc[kSlabScalars];
+  wave_scalars(ra, sc);
   __syncthreads();  // W stripes are dead from here on: reuse the LDS
   float* tr = reinterpret_cast<float*>(smem);
-  double* scl = reinterpret_cast<double*>(smem + (size_t)(W / 2) * NV * 64 * sizeof(float));
+  double* scl = reinterpret_cast<double*>(smem + Tree::kTreeBytes);
   if (lane == 0) {
 #pragma unroll
-    for (int k = 0; k < 5; ++k) scl[wave * 5 + k] = sc[k];
+    for (int k = 0; k < kSlabScalars; ++k) scl[wave * kSlabScalars + k] = sc[k];
   }
 #pragma unroll
   for (int step = W / 2; step >= 1; step >>= 1) {
@@ -666,9 +633,9 @@ gram_tall_bf16_kernel(GramArgs a) {
   }
   if (wave == 0) {
     double* out = a.partials + (int64_t)blockIdx.x * a.P;
-    if (lane < 5) {
+    if (lane < kSlabScalars) {
       double t = 0.0;
-      for (int w = 0; w < W; ++w) t += scl[w * 5 + lane];
+      for (int w = 0; w < W; ++w) t += scl[w * kSlabScalars + lane];
       slab_put(out + lane, t);
     }
     const int col = mfma32_col(lane);
@@ -681,8 +648,8 @@ gram_tall_bf16_kernel(GramArgs a) {
         const float vn = __shfl_down(v, 1, 64);  // col+1 (same row)
         const int feat = t * 32 + mfma32_row(lane, r);
         if (feat < d) {
-          if (col == 0) slab_put(out + 5 + feat, (double)v + (double)vn);
-          if (col == 2) slab_put(out + 5 + d + feat, (double)v + (double)vn);
+          if (col == 0) slab_put(out + kSlabScalars + feat, (double)v + (double)vn);
+          if (col == 2) slab_put(out + kSlabScalars + d + feat, (double)v + (double)vn);
         }
       }
     }
@@ -691,7 +658,7 @@ gram_tall_bf16_kernel(GramArgs a) {
     for (int I = 0; I < NT; ++I)
 #pragma unroll
       for (int J = I; J < NT; ++J, ++p) {
-        double* tile = out + 5 + 2 * d + p * 1024;
+        double* tile = slab_tile<32>(out, d, p);
 #pragma unroll
         for (int r = 0; r < 16; ++r) slab_put(tile + mfma32_row(lane, r) * 32 + col, (double)acc[p][r]);
       }
@@ -765,13 +732,7 @@ __global__ __launch_bounds__(256, (NT == 1 ? 3 : 2)) void gram_cols_kernel(GramA
     p.live = gptr<uint8_t>(a.sel)[r];
   };
   auto stage_w = [&](unsigned char* base, const RowVals& rv) {
-    __bf16* wl = reinterpret_cast<__bf16*>(base + FR);
-    const float w_hi = (float)(__bf16)(float)rv.w;
-    const __bf16 wy_hi = (__bf16)(float)rv.wy;
-    wl[0 * 64 + tid] = (__bf16)(float)rv.w;
-    wl[1 * 64 + tid] = (__bf16)(float)(rv.w - (double)w_hi);
-    wl[2 * 64 + tid] = wy_hi;
-    wl[3 * 64 + tid] = (__bf16)(float)(rv.wy - (double)(float)wy_hi);
+    stage_w_stripe(reinterpret_cast<__bf16*>(base + FR), tid, rv);
   };
   // x - s of the live rows to bf16 (dead rows and padding features exactly 0); sub = false: x
   // is already shifted and masked (the guarded last superstep)
@@ -863,104 +824,9 @@ __global__ __launch_bounds__(256, (NT == 1 ? 3 : 2)) void gram_cols_kernel(GramA
   }
 
   // ---- block reduction over the 4 waves (two tree rounds) + partial slab -----------------------
-  constexpr int NV = (NPAIR + NT) * 16;
-  double sc[5] = {ra.cnt, ra.ws, ra.wws, ra.bs, ra.bbs};
-#pragma unroll
-  for (int k = 0; k < 5; ++k) sc[k] = wave_sum_f64(sc[k]);
-  __syncthreads();
-  float* tr = reinterpret_cast<float*>(smem);
-  double* scl = reinterpret_cast<double*>(smem + (size_t)2 * NV * 64 * sizeof(float));
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < 5; ++k) scl[wave * 5 + k] = sc[k];
-  }
-#pragma unroll
-  for (int step = 2; step >= 1; step >>= 1) {
-    if (wave >= step && wave < 2 * step) {
-      float* dst = tr + (size_t)(wave - step) * NV * 64 + lane;
-      int v = 0;
-#pragma unroll
-      for (int p = 0; p < NPAIR; ++p)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) dst[(v++) * 64] = acc[p][r];
-#pragma unroll
-      for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) dst[(v++) * 64] = accw[t][r];
-    }
-    __syncthreads();
-    if (wave < step) {
-      const float* srcp = tr + (size_t)wave * NV * 64 + lane;
-      int v = 0;
-#pragma unroll
-      for (int p = 0; p < NPAIR; ++p)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[p][r] += srcp[(v++) * 64];
-#pragma unroll
-      for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) accw[t][r] += srcp[(v++) * 64];
-    }
-    __syncthreads();
-  }
-  if (wave == 0) {
-    const int d = a.d;
-    double* out = a.partials + (int64_t)blockIdx.x * a.P;
-    if (lane < 5) slab_put(out + lane, scl[lane] + scl[5 + lane] + scl[10 + lane] + scl[15 + lane]);
-    const int col = mfma32_col(lane);
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float v = accw[t][r];
-        const float vn = __shfl_down(v, 1, 64);
-        const int feat = t * 32 + mfma32_row(lane, r);
-        if (feat < d) {
-          if (col == 0) slab_put(out + 5 + feat, (double)v + (double)vn);
-          if (col == 2) slab_put(out + 5 + d + feat, (double)v + (double)vn);
-        }
-      }
-    }
-    int p = 0;
-#pragma unroll
-    for (int I = 0; I < NT; ++I)
-#pragma unroll
-      for (int J = I; J < NT; ++J, ++p) {
-        double* tile = out + 5 + 2 * d + p * 1024;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) slab_put(tile + mfma32_row(lane, r) * 32 + col, (double)acc[p][r]);
-      }
-  }
-}
-
-constexpr int kStageLd = 66;  // f64 staging row stride (doubles): 2-double pad spreads the banks
-
-// Cooperative load of features [f0, f0 + 16) x rows [r0, r0 + 64) of a feature-major matrix into a
-// per-wave LDS tile xs[f][row] (f64), zeros for features >= d.  Chunk c = i * 64 + lane.
-template <typename TX>
-__device__ __forceinline__ void stage_tile(const TX* __restrict__ X, int64_t ld, int d, int f0, int64_t r0, int lane,
-                                           double* xs) {
-  constexpr int kPer = 16 / sizeof(TX);     // elements per 16-byte chunk
-  constexpr int kChunksPerRow = 64 / kPer;  // chunks per feature row segment
-  constexpr int kIters = 16 * kChunksPerRow / 64;
-  typedef __attribute__((ext_vector_type(kPer))) TX vec;
-  vec v[kIters];
-#pragma unroll
-  for (int i = 0; i < kIters; ++i) {  // all loads in flight first
-    const int c = i * 64 + lane;
-    const int fl = c / kChunksPerRow, k = c % kChunksPerRow;
-    const int feat = f0 + fl;
-    const TX* src = X + (int64_t)(feat < d ? feat : 0) * ld + r0 + k * kPer;
-    v[i] = feat < d ? __builtin_nontemporal_load(reinterpret_cast<const vec*>(src)) : vec{};
-  }
-#pragma unroll
-  for (int i = 0; i < kIters; ++i) {
-    const int c = i * 64 + lane;
-    const int fl = c / kChunksPerRow, k = c % kChunksPerRow;
-    double* dst = xs + fl * kStageLd + k * kPer;
-#pragma unroll
-    for (int j = 0; j < kPer; j += 2) *reinterpret_cast<f64x2*>(dst + j) = f64x2{(double)v[i][j], (double)v[i][j + 1]};
-  }
+  double sc[kSlabScalars];
+  wave_scalars(ra, sc);
+  SlabTree32<NT, 4>::reduce_and_store(acc, accw, sc, smem, a.partials + (int64_t)blockIdx.x * a.P, a.d, lane, wave);
 }
 
 // =============================================================================================
@@ -1025,11 +891,9 @@ __global__ __launch_bounds__(kBlock) void gram_tall_f64_kernel(GramArgs a) {
       wyv[e] = lw[64 + 16 * q + e];
     }
     double x[NT][16];
+    // (load_superstep_f64 of gram_slab.h, kept in line here: behind the call the <float, 4>
+    // instantiation spills four more registers)
     if (s < a.nsuper) {
-      // full superstep: the wave loads each tile cooperatively — lane-contiguous 16-byte chunks,
-      // 512 B (f64) / 256 B (f32) runs per feature — and stages it in LDS, then every lane reads
-      // its 16 rows of its feature back (8 x ds_read_b128).  The per-lane strided scalar loads of
-      // the first version touched 64 cache lines per instruction (~3 TB/s at d = 16..32).
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
         stage_tile<TX>(X, a.ld, a.d, t * 16, r0, lane, xs);
@@ -1079,9 +943,8 @@ __global__ __launch_bounds__(kBlock) void gram_tall_f64_kernel(GramArgs a) {
   __syncthreads();
   double* red = reinterpret_cast<double*>(smem);
   for (int i = threadIdx.x; i < P; i += kBlock) red[i] = 0.0;
-  double sc[5] = {ra.cnt, ra.ws, ra.wws, ra.bs, ra.bbs};
-#pragma unroll
-  for (int k = 0; k < 5; ++k) sc[k] = wave_sum_f64(sc[k]);
+  double sc[kSlabScalars];
+  wave_scalars(ra, sc);
   // combine the 4 row-groups q of each feature
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
@@ -1095,15 +958,15 @@ __global__ __launch_bounds__(kBlock) void gram_tall_f64_kernel(GramArgs a) {
     if (wave == wvi) {
       if (lane == 0) {
 #pragma unroll
-        for (int k = 0; k < 5; ++k) red[k] += sc[k];
+        for (int k = 0; k < kSlabScalars; ++k) red[k] += sc[k];
       }
       if (q == 0) {
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
           const int feat = t * 16 + f;
           if (feat < d) {
-            red[5 + feat] += cs[t];
-            red[5 + d + feat] += ab[t];
+            red[kSlabScalars + feat] += cs[t];
+            red[kSlabScalars + d + feat] += ab[t];
           }
         }
       }
@@ -1112,7 +975,7 @@ __global__ __launch_bounds__(kBlock) void gram_tall_f64_kernel(GramArgs a) {
       for (int I = 0; I < NT; ++I)
 #pragma unroll
         for (int J = I; J < NT; ++J, ++p) {
-          double* tile = red + 5 + 2 * d + p * 256;
+          double* tile = slab_tile<16>(red, d, p);
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             double v = 0.0;
@@ -1186,7 +1049,7 @@ __device__ __forceinline__ void load4_as_f64(const void* p, int dt, int64_t r0, 
 template <typename TX, int D, bool COLS = false, bool VEC = false>
 __global__ __launch_bounds__(kBlock) void gram_skinny_f64_kernel(GramArgs a) {
   constexpr int NA = D * (D + 1) / 2;
-  constexpr int NV = 5 + 2 * D + NA;
+  constexpr int NV = slab_head(D) + NA;  // the slab head (d == D) + the packed upper products
   constexpr int UNR = 4;
   __shared__ double red[kWavesPerBlock][NV];
   double v[NV];
@@ -1255,11 +1118,11 @@ __global__ __launch_bounds__(kBlock) void gram_skinny_f64_kernel(GramArgs a) {
 #pragma unroll
       for (int i = 0; i < D; ++i) {
         const double xi = live[u] ? x[u][i] : 0.0;
-        v[5 + i] += w * xi;
-        v[5 + D + i] += wy * xi;
+        v[kSlabScalars + i] += w * xi;
+        v[kSlabScalars + D + i] += wy * xi;
         const double wxi = w * xi;
 #pragma unroll
-        for (int j = i; j < D; ++j, ++q) v[5 + 2 * D + q] += wxi * (live[u] ? x[u][j] : 0.0);
+        for (int j = i; j < D; ++j, ++q) v[slab_head(D) + q] += wxi * (live[u] ? x[u][j] : 0.0);
       }
     }
   }
@@ -1276,15 +1139,15 @@ __global__ __launch_bounds__(kBlock) void gram_skinny_f64_kernel(GramArgs a) {
 #pragma unroll
     for (int w = 0; w < kWavesPerBlock; ++w) t += red[w][k];
     int64_t dst;
-    if (k < 5 + 2 * D) {
+    if (k < slab_head(D)) {
       dst = k;  // scalars, Σw x (D), Σw x y (D): d == D
     } else {
-      int q = k - 5 - 2 * D, i = 0;
+      int q = k - slab_head(D), i = 0;
       while (q >= D - i) {
         q -= D - i;
         ++i;
       }
-      dst = 5 + 2 * D + i * 16 + (i + q);  // (i, j = i + q) of the 16 x 16 f64 tile
+      dst = slab_tile_offset<16>(D, 0) + i * 16 + (i + q);  // (i, j = i + q) of the 16 x 16 f64 tile
     }
     out[dst] = t;
   }
@@ -1659,12 +1522,7 @@ void patch_tiles_fill(const void* tiles, int64_t nent, const uint32_t* ovoff, ui
 }
 
 int64_t gram_partial_stride(int mode, int d) {
-  if (mode == GRAM_F64) {
-    const int NT = (d + 15) / 16;
-    return 5 + 2 * (int64_t)d + (int64_t)NT * (NT + 1) / 2 * 256;
-  }
-  const int NT = (d + 31) / 32;
-  return 5 + 2 * (int64_t)d + (int64_t)NT * (NT + 1) / 2 * 1024;
+  return mode == GRAM_F64 ? slab_stride<16>(d) : slab_stride<32>(d);
 }
 
 template <typename K>
@@ -1681,12 +1539,12 @@ static size_t bf16_lds(int d) {
   const int W = kBf16Block / kWave;
   const int NT = (d + 31) / 32;
   const size_t stripes = (size_t)W * (4 * 64 * 2 + 64 * 4);
-  const size_t tree = (size_t)(W / 2) * ((NT * (NT + 1) / 2 + NT) * 16) * 64 * sizeof(float) + (size_t)W * 5 * 8;
+  const size_t tree = NT == 1 ? SlabTree32<1, W>::kBytes : SlabTree32<2, W>::kBytes;
   return tree > stripes ? tree : stripes;
 }
 
 static size_t f64_lds(int d) {
-  size_t lds = kWavesPerBlock * (128 + 16 * kStageLd) * sizeof(double);
+  const size_t lds = kTallF64LoopBytes;
   const size_t red = (size_t)gram_partial_stride(GRAM_F64, d) * sizeof(double);
   return red > lds ? red : lds;
 }
@@ -1890,7 +1748,7 @@ void gram_tall(int mode, GramArgs a, int xmode, int blocks, double* out, hipStre
 
 static size_t cols_lds(int NT) {
   const size_t bufs = 2 * ((size_t)NT * 4 * 64 * 16 + 4 * 64 * 2);
-  const size_t tree = (size_t)2 * ((NT * (NT + 1) / 2 + NT) * 16) * 64 * sizeof(float) + 4 * 5 * sizeof(double);
+  const size_t tree = NT == 1 ? SlabTree32<1, 4>::kBytes : SlabTree32<2, 4>::kBytes;
   return bufs > tree ? bufs : tree;
 }
 

@@ -16,42 +16,11 @@
 #include "gram_folds.h"
 
 #include "common.h"
+#include "gram_slab.h"
 
 namespace dq4ml {
 
 namespace {
-
-constexpr int kBlock = 256;  // 4 waves, as the tall f64 kernel
-constexpr int kWavesPerBlock = kBlock / kWave;
-constexpr int kStageLd = 66;  // f64 staging row stride (doubles): 2-double pad spreads the banks
-
-// Cooperative load of features [f0, f0 + 16) x rows [r0, r0 + 64) of a feature-major matrix into a
-// per-wave LDS tile xs[f][row] (f64), zeros for features >= d (the tall f64 kernel's staging).
-template <typename TX>
-__device__ __forceinline__ void stage_tile(const TX* __restrict__ X, int64_t ld, int d, int f0, int64_t r0, int lane,
-                                           double* xs) {
-  constexpr int kPer = 16 / sizeof(TX);     // elements per 16-byte chunk
-  constexpr int kChunksPerRow = 64 / kPer;  // chunks per feature row segment
-  constexpr int kIters = 16 * kChunksPerRow / 64;
-  typedef __attribute__((ext_vector_type(kPer))) TX vec;
-  vec v[kIters];
-#pragma unroll
-  for (int i = 0; i < kIters; ++i) {  // all loads in flight first
-    const int c = i * 64 + lane;
-    const int fl = c / kChunksPerRow, k = c % kChunksPerRow;
-    const int feat = f0 + fl;
-    const TX* src = X + (int64_t)(feat < d ? feat : 0) * ld + r0 + k * kPer;
-    v[i] = feat < d ? __builtin_nontemporal_load(reinterpret_cast<const vec*>(src)) : vec{};
-  }
-#pragma unroll
-  for (int i = 0; i < kIters; ++i) {
-    const int c = i * 64 + lane;
-    const int fl = c / kChunksPerRow, k = c % kChunksPerRow;
-    double* dst = xs + fl * kStageLd + k * kPer;
-#pragma unroll
-    for (int j = 0; j < kPer; j += 2) *reinterpret_cast<f64x2*>(dst + j) = f64x2{(double)v[i][j], (double)v[i][j + 1]};
-  }
-}
 
 // per-row scalars of row r (lane = row): liveness and label; a dead row's label is never loaded
 struct RowVals {
@@ -134,31 +103,7 @@ __global__ __launch_bounds__(kBlock) void gram_folds_f64_kernel(GramArgs a, Fold
         yv[e] = lw[64 + 16 * q + e];
       }
       double x[NT][16];
-      if (s < nfull) {
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-          stage_tile<TX>(X, a.ld, d, t * 16, r0, lane, xs);
-          __builtin_amdgcn_wave_barrier();
-          const f64x2* src = reinterpret_cast<const f64x2*>(xs + f * kStageLd + 16 * q);
-#pragma unroll
-          for (int i = 0; i < 8; ++i) {
-            const f64x2 v = src[i];
-            x[t][2 * i] = v[0];
-            x[t][2 * i + 1] = v[1];
-          }
-          __builtin_amdgcn_wave_barrier();
-        }
-      } else {
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-#pragma unroll
-          for (int e = 0; e < 16; ++e) {
-            double v = 0.0;
-            if (fvalid[t] && e < rows_left) v = (double)fp[t][r0 + e];
-            x[t][e] = v;
-          }
-        }
-      }
+      load_superstep_f64<TX, NT>(X, a.ld, d, s < nfull, r0, rows_left, fp, fvalid, lane, xs, x);
       if (masked) {
         // dead rows: select, never multiply -- their stored features may be NaN
 #pragma unroll
@@ -212,8 +157,8 @@ __global__ __launch_bounds__(kBlock) void gram_folds_f64_kernel(GramArgs a, Fold
           for (int t = 0; t < NT; ++t) {
             const int feat = t * 16 + f;
             if (feat < d) {
-              red[5 + feat] += cs[t];
-              red[5 + d + feat] += ab[t];
+              red[kSlabScalars + feat] += cs[t];
+              red[kSlabScalars + d + feat] += ab[t];
             }
           }
         }
@@ -222,7 +167,7 @@ __global__ __launch_bounds__(kBlock) void gram_folds_f64_kernel(GramArgs a, Fold
         for (int I = 0; I < NT; ++I)
 #pragma unroll
           for (int J = I; J < NT; ++J, ++p) {
-            double* tile = red + 5 + 2 * d + p * 256;
+            double* tile = slab_tile<16>(red, d, p);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
               double v = 0.0;
@@ -248,7 +193,7 @@ __global__ __launch_bounds__(256) void fold_ids_kernel(int64_t n, int64_t granul
 }
 
 size_t folds_lds(int d) {
-  const size_t lds = kWavesPerBlock * (128 + 16 * kStageLd) * sizeof(double);
+  const size_t lds = kTallF64LoopBytes;
   const size_t red = (size_t)gram_partial_stride(GRAM_F64, d) * sizeof(double);
   return red > lds ? red : lds;
 }

@@ -28,6 +28,7 @@
 
 #include "common.h"
 #include "gram.h"
+#include "gram_slab.h"
 #endif
 
 namespace dq4ml {
@@ -54,23 +55,6 @@ __device__ __forceinline__ void wait_vm() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 __device__ __forceinline__ void wait_lgkm0() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-
-struct RowVals {
-  bool live;
-  double w, y, wy;
-};
-struct RowAcc {
-  double cnt = 0, ws = 0, wws = 0, bs = 0, bbs = 0;
-  __device__ __forceinline__ void add(const RowVals& v) {
-    if (v.live) {
-      cnt += 1.0;
-      ws += v.w;
-      wws += v.w * v.w;
-      bs += v.wy;
-      bbs += v.wy * v.y;
-    }
-  }
-};
 
 template <typename TX, int TF, int NT, int RS, int RING>
 struct SGeom {
@@ -257,13 +241,6 @@ __device__ __forceinline__ void stage_rows(const GramArgs& a, const unsigned cha
   wy_eff = rv.wy;
 }
 
-// per-lane RowAcc -> 5 wave sums
-__device__ __forceinline__ void wave_scalars(const RowAcc& ra, double sc[5]) {
-  sc[0] = ra.cnt, sc[1] = ra.ws, sc[2] = ra.wws, sc[3] = ra.bs, sc[4] = ra.bbs;
-#pragma unroll
-  for (int k = 0; k < 5; ++k) sc[k] = wave_sum_f64(sc[k]);
-}
-
 // The wave's stage loop: RING-deep DMA ring (RING - 1 stages in flight while one computes),
 // counted vmcnt waits, then the guarded tail stage on the last wave.
 template <typename G, typename SB, typename ISSUE, typename PROC, typename TAIL>
@@ -386,7 +363,7 @@ __global__ __launch_bounds__(kSB) void gram_stream_f64_kernel(GramArgs a) {
 
   // ---- block reduction into one f64 slab (serial over the waves: deterministic) --------------
   const int d = a.d, P = a.P;
-  double sc[5];
+  double sc[kSlabScalars];
   wave_scalars(ra, sc);
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
@@ -403,15 +380,15 @@ __global__ __launch_bounds__(kSB) void gram_stream_f64_kernel(GramArgs a) {
     if (wave == wvi) {
       if (lane == 0) {
 #pragma unroll
-        for (int k = 0; k < 5; ++k) red[k] += sc[k];
+        for (int k = 0; k < kSlabScalars; ++k) red[k] += sc[k];
       }
       if (q == 0) {
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
           const int feat = t * 16 + f;
           if (feat < d) {
-            red[5 + feat] += cs[t];
-            red[5 + d + feat] += ab[t];
+            red[kSlabScalars + feat] += cs[t];
+            red[kSlabScalars + d + feat] += ab[t];
           }
         }
       }
@@ -420,7 +397,7 @@ __global__ __launch_bounds__(kSB) void gram_stream_f64_kernel(GramArgs a) {
       for (int I = 0; I < NT; ++I)
 #pragma unroll
         for (int J = I; J < NT; ++J, ++p) {
-          double* tile = red + 5 + 2 * d + p * 256;
+          double* tile = slab_tile<16>(red, d, p);
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             double v = 0.0;
@@ -629,7 +606,7 @@ __device__ __forceinline__ void gram_stream_f32_body(const GramArgs& a) {
   flush();
 
   const int d = a.d, P = a.P;
-  double sc[5];
+  double sc[kSlabScalars];
   wave_scalars(ra, sc);
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
@@ -645,21 +622,21 @@ __device__ __forceinline__ void gram_stream_f32_body(const GramArgs& a) {
     if (wave == wvi) {
       if (lane == 0) {
 #pragma unroll
-        for (int k = 0; k < 5; ++k) red[k] += sc[k];
+        for (int k = 0; k < kSlabScalars; ++k) red[k] += sc[k];
       }
       if (h == 0) {
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
           const int feat = t * 32 + f;
           if (feat < d) {
-            red[5 + feat] += cs[t];
-            red[5 + d + feat] += ab[t];
+            red[kSlabScalars + feat] += cs[t];
+            red[kSlabScalars + d + feat] += ab[t];
           }
         }
       }
 #pragma unroll
       for (int p = 0; p < NPAIR; ++p) {
-        double* tile = red + 5 + 2 * d + p * 1024;
+        double* tile = slab_tile<32>(red, d, p);
 #pragma unroll
         for (int r = 0; r < 16; ++r) tile[mfma32_row(lane, r) * 32 + col] += acc64[p][r];
       }

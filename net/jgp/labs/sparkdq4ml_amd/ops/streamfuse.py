@@ -50,12 +50,12 @@ RAW16, RAW4 = 1024, 256
 
 
 def _device_text() -> str:
-    """common.h + gram.h + gram_stream.hip as one hipRTC translation unit (their host parts sit
-    behind ``#ifndef __HIPCC_RTC__``)."""
+    """common.h + gram.h + gram_slab.h + gram_stream.hip as one hipRTC translation unit (their host
+    parts, and the headers' ``#include`` lines, sit behind ``#ifndef __HIPCC_RTC__``)."""
     global _text
     if _text is None:
         parts = []
-        for name in ("common.h", "gram.h"):
+        for name in ("common.h", "gram.h", "gram_slab.h"):
             with open(os.path.join(_HERE, name)) as f:
                 parts.append(f.read().replace("#pragma once\n", ""))
         _text = "\n".join(parts)

@@ -1,6 +1,6 @@
 """The stream-Gram DQ prologue (ops/streamfuse.py) on the CPU: config 4's chain (range + not-null
 rule UDFs, their filter, 64 f32 features) lowers to a row predicate over a 4-region row-scalar
-layout, and the whole hipRTC translation unit (device parts of common.h / gram.h /
+layout, and the whole hipRTC translation unit (device parts of common.h / gram.h / gram_slab.h /
 gram_stream.hip + the generated predicate) compiles for gfx950 with hipRTC itself — only the
 module load needs the GPU.  Executed against the two-pass path in tests/test_gpu_streamfuse.py."""
 import pytest
