@@ -7,6 +7,7 @@ from .sql.session import SparkSession
 from .sql.dataframe import DataFrame, Row
 from .sql.column import Column
 from .sql.functions import callUDF, call_udf, col, lit, udf, when, expr, coalesce
+from .sql.window import Window, WindowSpec
 from .sql.types import DataTypes, StructType, StructField
 from .models.linalg import Vectors, DenseVector, SparseVector, Vector
 from .models.feature import VectorAssembler, Imputer, ImputerModel
@@ -24,5 +25,5 @@ __all__ = [
     "SparseVector", "Vector", "VectorAssembler", "LinearRegression", "LinearRegressionModel",
     "LinearRegressionTrainingSummary", "MinimumPriceDataQualityUdf", "PriceCorrelationDataQualityUdf",
     "ParamGridBuilder", "CrossValidator", "CrossValidatorModel", "TrainValidationSplit",
-    "TrainValidationSplitModel", "Imputer", "ImputerModel", "IqrRule",
+    "TrainValidationSplitModel", "Imputer", "ImputerModel", "IqrRule", "Window", "WindowSpec",
 ]

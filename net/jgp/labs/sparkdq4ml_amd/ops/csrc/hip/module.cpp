@@ -17,6 +17,7 @@
 #include "quantile.h"
 #include "groupby.h"
 #include "sort.h"
+#include "window.h"
 #include "join.h"
 #include "gram_wide.h"
 #include "gram_syrk.h"
@@ -323,6 +324,97 @@ PYBIND11_MODULE(_dq4ml_hip, m) {
     sort_pass(P<const unsigned long long>(keys_in), P<const unsigned>(idx_in), P<unsigned long long>(keys_out),
               P<unsigned>(idx_out), m_, digit, P<unsigned>(counts), stride, P<const unsigned long long>(hist_row),
               P<const unsigned>(base), blocks, as_stream(stream));
+  });
+  m.def("window_blocks", &window_blocks);
+  // threads per block, positions per thread, tile in positions, key columns per heads launch, words per pass
+  m.def("window_limits", []() { return py::make_tuple(kWinThreads, kWinRun, kWinTile, kWinMaxKeys, kWinMaxWords); });
+  // heads: [m] u8; part[c] != 0: column c is a partition column; accumulate: OR into heads
+  m.def("window_heads", [](const std::vector<uintptr_t>& cols, const std::vector<int>& dts, const std::vector<uintptr_t>& valids,
+                           const std::vector<int>& part, uintptr_t perm, int64_t n, int64_t m_, bool accumulate, uintptr_t heads,
+                           int blocks, uintptr_t stream) {
+    const size_t K = cols.size();
+    if (K > (size_t)kWinMaxKeys || dts.size() != K || valids.size() != K || part.size() != K)
+      throw std::invalid_argument("window_heads: at most " + std::to_string(kWinMaxKeys) +
+                                  " key columns per launch, one dtype, validity pointer and partition flag each");
+    WinKeyArgs a{};
+    for (size_t c = 0; c < K; ++c) {
+      a.col[c] = P<const void>(cols[c]);
+      a.valid[c] = P<const uint8_t>(valids[c]);
+      a.dt[c] = dts[c];
+      a.part[c] = part[c];
+    }
+    a.perm = P<const unsigned>(perm);
+    a.n = n;
+    a.m = m_;
+    a.K = (int)K;
+    a.accumulate = accumulate ? 1 : 0;
+    window_heads(a, P<uint8_t>(heads), blocks, as_stream(stream));
+  });
+  // bounds: [5][m] u32 (part_start, peer_start, part_end, peer_end, dense); totals: 2 * tiles * 16 bytes
+  m.def("window_bounds", [](uintptr_t heads, int64_t m_, uintptr_t bounds, uintptr_t totals, int blocks, uintptr_t stream) {
+    unsigned* b = P<unsigned>(bounds);
+    window_bounds(P<const uint8_t>(heads), m_, b, b + m_, b + 2 * m_, b + 3 * m_, b + 4 * m_, P<void>(totals), blocks,
+                  as_stream(stream));
+  });
+  // slots: (word kind, column, dtype, valid, e) each; prefix: [words][m] i64; totals: [words][tiles] i64
+  m.def("window_prefix", [](const std::vector<int>& ops, const std::vector<uintptr_t>& cols, const std::vector<int>& dts,
+                            const std::vector<uintptr_t>& valids, const std::vector<int>& es, uintptr_t perm, int64_t n,
+                            int64_t m_, uintptr_t prefix, uintptr_t totals, int blocks, uintptr_t stream) {
+    const size_t S = ops.size();
+    if (S < 1 || S > (size_t)kWinMaxWords || cols.size() != S || dts.size() != S || valids.size() != S || es.size() != S)
+      throw std::invalid_argument("window_prefix: between 1 and " + std::to_string(kWinMaxWords) +
+                                  " slots per pass, one column, dtype, validity pointer and exponent each");
+    WinPrefixArgs a{};
+    int words = 0;
+    for (size_t s = 0; s < S; ++s) {
+      a.op[s] = ops[s];
+      a.col[s] = P<const void>(cols[s]);
+      a.dt[s] = dts[s];
+      a.valid[s] = P<const uint8_t>(valids[s]);
+      a.e[s] = es[s];
+      a.woff[s] = words;
+      words += win_word_count(ops[s]);
+    }
+    a.perm = P<const unsigned>(perm);
+    a.n = n;
+    a.m = m_;
+    a.S = (int)S;
+    a.words = words;
+    window_prefix(a, P<long long>(prefix), P<long long>(totals), blocks, as_stream(stream));
+  });
+  // out: [m] u64 order keys; totals: tiles * 16 bytes
+  m.def("window_minmax", [](uintptr_t col, int dt, uintptr_t valid, uintptr_t perm, int64_t n, int64_t m_, uintptr_t heads,
+                            bool is_max, bool backward, uintptr_t out, uintptr_t totals, int blocks, uintptr_t stream) {
+    window_minmax(P<const void>(col), dt, P<const uint8_t>(valid), P<const unsigned>(perm), n, m_, P<const uint8_t>(heads),
+                  is_max, backward, P<unsigned long long>(out), P<void>(totals), blocks, as_stream(stream));
+  });
+  // frame: (is_range, lo_unbounded, hi_unbounded, lo_off, hi_off); words: (kind, source, arg) each; out: [n][words] i64
+  m.def("window_finish", [](uintptr_t bounds, uintptr_t perm, int64_t n, int64_t m_, bool is_range, bool lo_unbounded,
+                            bool hi_unbounded, long long lo_off, long long hi_off, const std::vector<int>& kinds,
+                            const std::vector<uintptr_t>& srcs, const std::vector<long long>& args, uintptr_t out, int blocks,
+                            uintptr_t stream) {
+    const size_t W = kinds.size();
+    if (W < 1 || W > (size_t)kWinMaxWords || srcs.size() != W || args.size() != W)
+      throw std::invalid_argument("window_finish: between 1 and " + std::to_string(kWinMaxWords) +
+                                  " words per launch, one source and argument each");
+    WinFinishArgs a{};
+    const unsigned* b = P<const unsigned>(bounds);
+    a.b = WinBounds{b, b + m_, b + 2 * m_, b + 3 * m_, b + 4 * m_};
+    a.perm = P<const unsigned>(perm);
+    for (size_t w = 0; w < W; ++w) {
+      a.kind[w] = kinds[w];
+      a.src[w] = P<const void>(srcs[w]);
+      a.arg[w] = args[w];
+    }
+    a.n = n;
+    a.m = m_;
+    a.words = (int)W;
+    a.is_range = is_range ? 1 : 0;
+    a.lo_unbounded = lo_unbounded ? 1 : 0;
+    a.hi_unbounded = hi_unbounded ? 1 : 0;
+    a.lo_off = lo_off;
+    a.hi_off = hi_off;
+    window_finish(a, P<long long>(out), blocks, as_stream(stream));
   });
   m.def("join_blocks", &join_blocks);
   m.def("join_expand_blocks", &join_expand_blocks);

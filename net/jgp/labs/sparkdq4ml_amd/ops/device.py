@@ -684,6 +684,133 @@ def sort_permutation(cols, valids, sel, ascending, nulls_first, blocks: Optional
 
 
 # ------------------------------------------------------------------------------------------
+# window functions over sorted positions (csrc/hip/window.hip); contracts and twins in ops/window.py
+# ------------------------------------------------------------------------------------------
+def _window(perm: torch.Tensor, n: int):
+    """``(extension, perm as the kernels' u32 row indices, m, tiles)`` of one window call."""
+    h = native.hip()
+    from . import window as wn
+
+    assert tuple(h.window_limits()) == wn.window_limits(), "window.py / window.h constants differ"
+    _check_dev(perm)
+    m = int(perm.numel())
+    if m > int(n) or int(n) >= 1 << 31:
+        raise ValueError("window: the positions are rows of a table of fewer than 2^31 rows")
+    return h, perm.to(torch.int32).contiguous(), m, (m + wn.WINDOW_TILE - 1) // wn.WINDOW_TILE
+
+
+def _window_totals(tiles: int, rows: int, dev) -> torch.Tensor:
+    """Tile totals of a scan: ``rows`` rows of 16 bytes per tile (torch allocations are 16-byte aligned)."""
+    return torch.empty(max(rows * tiles, 1) * 2, dtype=torch.int64, device=dev)
+
+
+def window_heads(cols, valids, part, perm, n: int, blocks: Optional[int] = None) -> torch.Tensor:
+    """Device form of ``ops.window.window_heads``: the key columns go by value in the kernarg, in
+    chunks of the launch's maximum that OR into the same bytes."""
+    h, p32, m, _ = _window(perm, n)
+    _check_dev(perm, *cols, *valids)
+    ks = [_KeyCol(c, v, None, n, "window_heads", "a") for c, v in zip(cols, valids)]
+    heads = torch.empty(m, dtype=torch.uint8, device=perm.device)
+    if m == 0:
+        return heads
+    nb, st = _blocks(blocks, h.window_blocks(m)), _stream()
+    per = int(h.window_limits()[3])
+    for i in range(0, max(len(ks), 1), per):
+        chunk = ks[i:i + per]
+        h.window_heads([k.col.data_ptr() for k in chunk], [dtype_code(k.col) for k in chunk], [_ptr(k.valid) for k in chunk],
+                       [1 if f else 0 for f in part[i:i + per]], p32.data_ptr(), int(n), m, i > 0, heads.data_ptr(), nb, st)
+    return heads
+
+
+def window_bounds(heads: torch.Tensor, blocks: Optional[int] = None) -> torch.Tensor:
+    """Device form of ``ops.window.window_bounds``: int32 ``[5, m]``."""
+    h = native.hip()
+    from . import window as wn
+
+    _check_dev(heads)
+    heads = heads.contiguous()
+    m = int(heads.numel())
+    bounds = torch.empty(5, m, dtype=torch.int32, device=heads.device)
+    if m == 0:
+        return bounds
+    tiles = (m + wn.WINDOW_TILE - 1) // wn.WINDOW_TILE
+    totals = _window_totals(tiles, 2, heads.device)
+    h.window_bounds(heads.data_ptr(), m, bounds.data_ptr(), totals.data_ptr(), _blocks(blocks, h.window_blocks(m)), _stream())
+    return bounds
+
+
+def window_prefix(slots, perm, n: int, words: int, blocks: Optional[int] = None) -> torch.Tensor:
+    """Device form of ``ops.window.window_prefix``: int64 ``[words, m]``, in passes of at most
+    ``window_limits()[4]`` words (a slot's words stay in one pass)."""
+    h, p32, m, tiles = _window(perm, n)
+    from . import window as wn
+
+    _check_dev(perm, *(s[1] for s in slots), *(s[2] for s in slots))
+    dev = perm.device
+    P = torch.empty(words, m, dtype=torch.int64, device=dev)
+    if m == 0:
+        return P
+    cols = [None if s[1] is None or s[0] in (wn.ROWS, wn.COUNT) else _group_col(s[1], n, "window_prefix") for s in slots]
+    valids = [None if s[0] == wn.ROWS else _mask_u8(s[2], n, "a validity mask", "window_prefix") for s in slots]
+    per = int(h.window_limits()[4])
+    totals = torch.empty(per * tiles, dtype=torch.int64, device=dev)
+    nb, st = _blocks(blocks, h.window_blocks(m)), _stream()
+    i, w0 = 0, 0
+    while i < len(slots):
+        j, w = i, 0
+        while j < len(slots) and w + wn.word_count(slots[j][0]) <= per:
+            w += wn.word_count(slots[j][0])
+            j += 1
+        ch = range(i, j)
+        h.window_prefix([int(slots[k][0]) for k in ch], [_ptr(cols[k]) for k in ch],
+                        [0 if cols[k] is None else dtype_code(cols[k]) for k in ch], [_ptr(valids[k]) for k in ch],
+                        [int(slots[k][3] or 0) for k in ch], p32.data_ptr(), int(n), m, P[w0:].data_ptr(), totals.data_ptr(),
+                        nb, st)
+        i, w0 = j, w0 + w
+    return P
+
+
+def window_minmax(col, valid, perm, heads, is_max: bool, backward: bool, blocks: Optional[int] = None) -> torch.Tensor:
+    """Device form of ``ops.window.window_minmax``: the u64 order keys as int64 ``[m]``."""
+    n = int(col.numel())
+    h, p32, m, tiles = _window(perm, n)
+    _check_dev(col, valid, perm, heads)
+    k = _KeyCol(col, valid, None, n, "window_minmax", "a")
+    out = torch.empty(m, dtype=torch.int64, device=perm.device)
+    if m == 0:
+        return out
+    heads = heads.contiguous()
+    totals = _window_totals(tiles, 1, perm.device)
+    h.window_minmax(k.col.data_ptr(), dtype_code(k.col), _ptr(k.valid), p32.data_ptr(), n, m, heads.data_ptr(), is_max, backward,
+                    out.data_ptr(), totals.data_ptr(), _blocks(blocks, h.window_blocks(m)), _stream())
+    return out
+
+
+def window_finish(bounds, perm, n: int, frame, outs, blocks: Optional[int] = None) -> torch.Tensor:
+    """Device form of ``ops.window.window_finish``: int64 ``[n, words]``, zero outside the
+    permutation; ``frame`` = ``(is_range, lo unbounded, hi unbounded, lo offset, hi offset)``."""
+    h, p32, m, _ = _window(perm, n)
+    _check_dev(bounds, perm, *(o[1] for o in outs))
+    bounds = bounds.contiguous()
+    srcs = [None if o[1] is None else o[1].contiguous() for o in outs]
+    out = torch.zeros(int(n), len(outs), dtype=torch.int64, device=perm.device)
+    if m == 0:
+        return out
+    per = int(h.window_limits()[4])
+    nb, st = _blocks(blocks, h.window_blocks(m)), _stream()
+    is_range, lo_unb, hi_unb, lo_off, hi_off = frame
+    parts = []
+    for i in range(0, len(outs), per):
+        ch = range(i, min(i + per, len(outs)))
+        o = out if len(outs) <= per else torch.zeros(int(n), len(ch), dtype=torch.int64, device=perm.device)
+        h.window_finish(bounds.data_ptr(), p32.data_ptr(), int(n), m, is_range, lo_unb, hi_unb, int(lo_off), int(hi_off),
+                        [int(outs[k][0]) for k in ch], [_ptr(srcs[k]) for k in ch], [int(outs[k][2]) for k in ch],
+                        o.data_ptr(), nb, st)
+        parts.append(o)
+    return out if len(outs) <= per else torch.cat(parts, dim=1)
+
+
+# ------------------------------------------------------------------------------------------
 # hash equi-join (csrc/hip/join.hip); the contract and its numpy twin are in ops/join.py
 # ------------------------------------------------------------------------------------------
 _JOIN_MODES = {"inner": 0, "left_outer": 1, "full_outer": 2, "semi": 3}

@@ -297,10 +297,17 @@ def group_encode_columns(cols, valids=None, sel=None, capacity: Optional[int] = 
 # ------------------------------------------------------------------------------------------
 # finalisation (G-sized torch integer code, the same for both engines)
 # ------------------------------------------------------------------------------------------
+def _pow2(k: torch.Tensor) -> torch.Tensor:
+    """2^k as a double built from its bits (k int64 in [-1022, 1023]).  ``torch.ldexp`` multiplies
+    by ``pow(2.0, k)``, and a device ``pow`` may be an ulp off, which a correctly rounded sum
+    cannot afford."""
+    return ((k + 1023) << 52).view(torch.float64)
+
+
 def _ldexp2(m: torch.Tensor, s: torch.Tensor) -> torch.Tensor:
-    """m * 2^s for |s| beyond one power's range: two exact-or-final steps."""
+    """m * 2^s for |s| beyond one power's range (s within +-2044): two exact-or-final steps."""
     h = torch.div(s, 2, rounding_mode="floor")
-    return torch.ldexp(torch.ldexp(m, h), s - h)
+    return m * _pow2(h) * _pow2(s - h)
 
 
 def finalize_sum(limbs: torch.Tensor, flags: torch.Tensor, e) -> torch.Tensor:

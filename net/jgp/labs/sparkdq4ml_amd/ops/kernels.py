@@ -12,6 +12,7 @@ Ops:
   K5q ``quantiles``          exact order statistics of C columns x Q probabilities (radix select)
   K5g ``group_encode`` / ``group_agg``  group ids of key columns, integer-word grouped aggregates
   K5s ``sort_permutation``   stable multi-column radix sort of the live rows (row indices)
+  K5w ``window_heads`` / ``window_bounds`` / ``window_prefix`` / ``window_minmax`` / ``window_finish``  scans over sorted positions
   K5j ``join_pairs`` / ``join_mask``  hash equi-join of two key columns: ordered (left, right) row pairs
   K7+K8 ``predict`` / ``regression_metrics``  fused GEMV + metric reductions
 """
@@ -26,11 +27,14 @@ from . import native
 from .layout import gram_layout_size
 from .groupby import group_agg, group_encode, group_encode_columns, group_limits, group_scale  # noqa: F401  (K5g)
 from .sort import sort_limits, sort_permutation  # noqa: F401  (K5s: dispatches by device itself)
+from .window import (window_bounds, window_finish, window_heads, window_limits, window_minmax,  # noqa: F401  (K5w:
+                     window_prefix)  # dispatches by device itself)
 from .join import join_key_columns, join_limits, join_mask, join_pairs  # noqa: F401  (K5j: dispatches by device itself)
 
 __all__ = ["selected_indices", "pack_columns", "gram_stats", "predict", "regression_metrics",
            "gram_layout_size", "gram_stats_folds", "fold_ids", "fold_thresholds", "fold_seed", "quantiles", "group_encode", "group_encode_columns",
-           "group_agg", "group_scale", "group_limits", "sort_permutation", "sort_limits", "join_pairs", "join_mask",
+           "group_agg", "group_scale", "group_limits", "sort_permutation", "sort_limits", "window_heads", "window_bounds",
+           "window_prefix", "window_minmax", "window_finish", "window_limits", "join_pairs", "join_mask",
            "join_key_columns", "join_limits"]
 
 

@@ -102,7 +102,13 @@ def build_aggregate(child, key_exprs: Sequence[Expr], agg_exprs: Sequence[Expr])
             have.add(name.lower())
             proj.append(e)
 
+    from .window import contains_window
+
     keys = []
+    for k in list(key_exprs) + list(agg_exprs):
+        if contains_window(k):
+            raise AnalysisException(f"window functions are not allowed in GROUP BY or inside an aggregate, but found "
+                                    f"{k.sql_name()}")
     for k in key_exprs:
         if contains_aggregate(k):
             raise AnalysisException(f"aggregate functions are not allowed in GROUP BY, but found {k.sql_name()}")

@@ -14,7 +14,8 @@ import torch
 from ..utils.javafmt import java_str
 from .column import Column
 from .expressions import (Alias, AnalysisException, ColRef, Expr, to_expr)
-from .plan import Filter, Limit, LocalRelation, LogicalPlan, Project, Union, execute, is_sharded, output_name
+from .plan import (Filter, Limit, LocalRelation, LogicalPlan, Project, Union, build_project, execute, is_sharded,
+                   output_name)
 from .skey import expr_key, exprs_key
 from .table import Table
 from .types import StructType, VectorUDT
@@ -263,7 +264,7 @@ class DataFrame:
 
         def build():
             self._check_refs(exprs)
-            return self._with(Project(self._plan, exprs))
+            return self._with(build_project(self._plan, exprs))
         return self._derive(("select", ek) if ek is not None else None, build)
 
     def selectExpr(self, *exprs):
@@ -294,7 +295,7 @@ class DataFrame:
         if not replaced:
             exprs.append(Alias(e, name))
         self._check_refs([e])
-        return self._with(Project(self._plan, exprs))
+        return self._with(build_project(self._plan, exprs))
 
     def withColumnRenamed(self, existing: str, new: str) -> "DataFrame":
         def build():

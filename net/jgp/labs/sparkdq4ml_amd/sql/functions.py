@@ -7,7 +7,8 @@ from .expressions import CaseWhen, Coalesce, ColRef, IsNull, Lit, UdfCall, to_ex
 
 __all__ = ["col", "column", "lit", "callUDF", "call_udf", "udf", "when", "coalesce", "isnull", "expr",
            "count", "sum", "avg", "mean", "min", "max", "asc", "desc", "asc_nulls_first", "asc_nulls_last",
-           "desc_nulls_first", "desc_nulls_last"]
+           "desc_nulls_first", "desc_nulls_last", "row_number", "rank", "dense_rank", "percent_rank", "cume_dist", "ntile",
+           "lag", "lead"]
 
 
 def col(name: str) -> Column:
@@ -101,6 +102,48 @@ def desc_nulls_first(c) -> Column:
 
 def desc_nulls_last(c) -> Column:
     return _order_col(c).desc_nulls_last()
+
+
+def _window_fn(fn: str, c=None, param: int = 0, default=None) -> Column:
+    from .window import WindowFn
+
+    child = None if c is None else (ColRef(c) if isinstance(c, str) else to_expr(c))
+    return Column(WindowFn(fn, child, param, default))
+
+
+def row_number() -> Column:
+    """The 1-based position of the row in its window partition; needs ``.over`` an ordered window."""
+    return _window_fn("row_number")
+
+
+def rank() -> Column:
+    return _window_fn("rank")
+
+
+def dense_rank() -> Column:
+    return _window_fn("dense_rank")
+
+
+def percent_rank() -> Column:
+    return _window_fn("percent_rank")
+
+
+def cume_dist() -> Column:
+    return _window_fn("cume_dist")
+
+
+def ntile(n: int) -> Column:
+    return _window_fn("ntile", None, n)
+
+
+def lag(c, offset: int = 1, default=None) -> Column:
+    """The value of ``c`` ``offset`` rows before the current row of its window partition
+    (``default`` where there is none)."""
+    return _window_fn("lag", c, offset, default)
+
+
+def lead(c, offset: int = 1, default=None) -> Column:
+    return _window_fn("lead", c, offset, default)
 
 
 def expr(text: str) -> Column:

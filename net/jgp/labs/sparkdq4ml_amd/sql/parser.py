@@ -19,7 +19,7 @@ from .expressions import (Alias, AnalysisException, BinOp, CaseWhen, Cast, ColRe
                           Expr, If, IsNotNull, IsNull, Lit, Neg, Not, SortOrder, UdfCall)
 from .aggregates import AggExpr, build_aggregate, contains_aggregate
 from .fn import MathFn, BUILTIN_MATH
-from .plan import Aggregate, Filter, Join, Limit, Project, build_sort, output_name
+from .plan import Aggregate, Filter, Join, Limit, Project, build_project, build_sort, output_name
 from .skey import expr_key
 
 __all__ = ["parse_expression", "parse_select_item", "plan_sql", "ParseException"]
@@ -42,6 +42,8 @@ _KEYWORDS = {"select", "from", "where", "as", "and", "or", "not", "cast", "is", 
              "case", "when", "then", "else", "end", "limit", "between", "in", "distinct", "like", "group", "by", "order"}
 
 
+_WINDOW_FNS = {"row_number", "rank", "dense_rank", "percent_rank", "cume_dist", "ntile", "lag", "lead", "first", "last",
+               "first_value", "last_value", "nth_value"}
 _JOIN_WORDS = {"inner", "left", "right", "full", "outer", "semi", "anti", "cross", "join", "on", "using"}
 _JOIN_TYPES = {(): "inner", ("inner",): "inner", ("left",): "left_outer", ("left", "outer"): "left_outer",
                ("right",): "right_outer", ("right", "outer"): "right_outer", ("full",): "full_outer",
@@ -183,6 +185,60 @@ class _Parser:
                 raise AnalysisException("cross joins are not implemented")
             raise ParseException(f"\nmismatched input '{' '.join(words)} join': not a join type")
         return how
+
+    def over(self, e: Expr) -> Expr:
+        """``fn(...) [OVER ([PARTITION BY e, ...] [ORDER BY e [ASC|DESC] [NULLS FIRST|LAST], ...]
+        [ROWS | RANGE BETWEEN bound AND bound])]``."""
+        if not self.accept("ident", "over"):
+            return e
+        from .window import WindowSpec, over
+
+        self.expect("op", "(")
+        partition, orders, frame = [], [], None
+        if self.accept("ident", "partition"):
+            self.expect("kw", "by")
+            partition = [self.expr()]
+            while self.accept("op", ","):
+                partition.append(self.expr())
+        if self.accept("kw", "order"):
+            self.expect("kw", "by")
+            orders = [SortOrder(*self.order_item())]
+            while self.accept("op", ","):
+                orders.append(SortOrder(*self.order_item()))
+        spec = WindowSpec(partition, orders)
+        t = self.peek()
+        if t[0] == "ident" and t[1].lower() in ("rows", "range"):
+            kind = self.next()[1].lower()
+            self.expect("kw", "between")
+            lo = self.frame_bound()
+            self.expect("kw", "and")
+            hi = self.frame_bound()
+            spec = spec.rowsBetween(lo, hi) if kind == "rows" else spec.rangeBetween(lo, hi)
+        self.expect("op", ")")
+        return over(e, spec)
+
+    def frame_bound(self) -> int:
+        """``UNBOUNDED PRECEDING | n PRECEDING | CURRENT ROW | n FOLLOWING | UNBOUNDED FOLLOWING``
+        as the integers ``rowsBetween`` takes."""
+        from .window import Window
+
+        def side():
+            t = self.expect("ident")
+            if t[1].lower() not in ("preceding", "following"):
+                raise ParseException(f"\nmismatched input '{t[1]}' expecting PRECEDING or FOLLOWING")
+            return t[1].lower() == "preceding"
+
+        if self.accept("ident", "unbounded"):
+            return Window.unboundedPreceding if side() else Window.unboundedFollowing
+        if self.accept("ident", "current"):
+            self.expect("ident", "row")
+            return Window.currentRow
+        neg = bool(self.accept("op", "-"))
+        t = self.expect("num")
+        if not t[1].isdigit():
+            raise ParseException(f"\nmismatched input '{t[1]}' expecting an integer frame offset")
+        v = -int(t[1]) if neg else int(t[1])
+        return -v if side() else v
 
     def order_item(self):
         """``expr [ASC|DESC] [NULLS FIRST|NULLS LAST]`` -> (expr, ascending, nulls_first or None)."""
@@ -351,14 +407,14 @@ class _Parser:
             if self.accept("op", "("):
                 if val.lower() == "count" and self.accept("op", "*"):
                     self.expect("op", ")")
-                    return AggExpr("count", None)
+                    return self.over(AggExpr("count", None))
                 args = []
                 if not self.accept("op", ")"):
                     args.append(self.expr())
                     while self.accept("op", ","):
                         args.append(self.expr())
                     self.expect("op", ")")
-                return _function(val, args)
+                return self.over(_function(val, args))
             if self.accept("op", "."):
                 field = self.expect("ident")[1]
                 return ColRef(val + "." + field)
@@ -366,8 +422,40 @@ class _Parser:
         raise ParseException(f"\nmismatched input '{val or '<EOF>'}'")
 
 
+def _int_arg(fn: str, e: Expr) -> int:
+    if not (isinstance(e, Lit) and isinstance(e.value, int) and not isinstance(e.value, bool)):
+        raise AnalysisException(f"{fn}: the offset / bucket count must be an integer literal, got {e.sql_name()}")
+    return e.value
+
+
+def _window_function(low: str, args: List[Expr]) -> Expr:
+    """``row_number()`` ... ``lead(c, k, default)``: a window function awaiting its OVER clause."""
+    from .window import WindowFn
+
+    if low not in ("row_number", "rank", "dense_rank", "percent_rank", "cume_dist", "ntile", "lag", "lead"):
+        return WindowFn(low)  # (raises: first / last / nth_value are not implemented)
+    if low in ("lag", "lead"):
+        if not 1 <= len(args) <= 3:
+            raise AnalysisException(f"Invalid number of arguments for function {low}")
+        default = None
+        if len(args) == 3:
+            if not isinstance(args[2], Lit):
+                raise AnalysisException(f"{low}: the default must be a literal, got {args[2].sql_name()}")
+            default = args[2].value
+        return WindowFn(low, args[0], _int_arg(low, args[1]) if len(args) > 1 else 1, default)
+    if low == "ntile":
+        if len(args) != 1:
+            raise AnalysisException("Invalid number of arguments for function ntile")
+        return WindowFn(low, None, _int_arg(low, args[0]))
+    if args:
+        raise AnalysisException(f"Invalid number of arguments for function {low}")
+    return WindowFn(low)
+
+
 def _function(name: str, args: List[Expr]) -> Expr:
     low = name.lower()
+    if low in _WINDOW_FNS:
+        return _window_function(low, args)
     if low == "coalesce":
         return Coalesce(*args)
     if low == "isnull":
@@ -397,6 +485,9 @@ def _strip_qual(e: Expr, quals) -> Expr:
             setattr(e, attr, _strip_qual(getattr(e, attr), quals))
     if hasattr(e, "args"):
         e.args = [_strip_qual(a, quals) for a in e.args]
+    if hasattr(e, "partition") and hasattr(e, "orders"):  # a window specification
+        e.partition = [_strip_qual(a, quals) for a in e.partition]
+        e.orders = [_strip_qual(a, quals) for a in e.orders]
     if hasattr(e, "branches"):
         e.branches = [(_strip_qual(c, quals), _strip_qual(v, quals)) for c, v in e.branches]
     return e
@@ -466,7 +557,12 @@ def _bind_query(syntax, text: str, session):
 
 
 def _bind_new(items, where, limit, plan, distinct=False, group=None, order=None):
+    from .window import contains_window
+
     if where is not None:
+        if contains_window(where):
+            raise AnalysisException("It is not allowed to use window functions inside WHERE and HAVING clauses: select the "
+                                    "window expression under an alias and filter on the alias")
         if contains_aggregate(where):
             raise AnalysisException("Aggregate/Window/Generate expressions are not valid in where clause of the query.")
         plan = Filter(plan, where)
@@ -477,8 +573,16 @@ def _bind_new(items, where, limit, plan, distinct=False, group=None, order=None)
         else:
             exprs.append(e)
     grouped = group is not None or any(contains_aggregate(e) for e in exprs)
+    windowed = any(contains_window(e) for e in exprs)
+    if any(contains_window(g) for g in group or []):
+        raise AnalysisException("window functions are not allowed in GROUP BY")
+    if grouped and windowed:
+        raise AnalysisException("a window function over the result of GROUP BY / aggregates in one SELECT is not "
+                                "implemented: aggregate in a first statement and window over its result")
     if grouped:
         plan = _bind_grouped(exprs, group or [], plan)
+    elif windowed:
+        plan = build_project(plan, exprs)
     else:
         plan = Project(plan, exprs)
         cs = plan.child.schema()

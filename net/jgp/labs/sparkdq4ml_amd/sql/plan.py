@@ -19,7 +19,7 @@ from .table import ColumnData, Table
 from .types import BooleanType, StructField, StructType, VectorUDT
 
 __all__ = ["LogicalPlan", "LocalRelation", "CsvScanRelation", "Project", "Filter", "Limit", "Union", "Join", "Aggregate", "Deduplicate",
-           "Sort", "build_sort", "execute", "prune_columns"]
+           "Sort", "build_sort", "Window", "build_project", "execute", "prune_columns"]
 
 
 class LogicalPlan:
@@ -227,6 +227,11 @@ class Filter(LogicalPlan):
         k = self.skey()
         if k is not None and k in _CHECKED:
             return
+        from .window import contains_window
+
+        if contains_window(cond):
+            raise AnalysisException("It is not allowed to use window functions inside WHERE and HAVING clauses: select the "
+                                    "window expression under an alias and filter on the alias")
         dt = cond.data_type(child.schema())
         if not isinstance(dt, BooleanType):
             raise AnalysisException(f"filter expression '{cond.sql_name()}' of type {dt.simpleString()} "
@@ -513,6 +518,68 @@ class Sort(LogicalPlan):
         return "Sort [" + ", ".join(o.sql_name() for o in self.orders) + "]"
 
 
+class Window(LogicalPlan):
+    """The child's table with one column per window expression appended: ``wexprs`` =
+    ``(WindowExpr, output name)`` (``sql/window.py``).  No row is moved and the selection vector is
+    kept.  ``build_project`` puts this node under a ``Project`` whose expressions contain window
+    expressions and replaces each by a reference to its (hidden) column."""
+
+    def __init__(self, child: LogicalPlan, wexprs: Sequence[Tuple]):
+        if is_sharded(child):
+            raise AnalysisException("a window function over a data-parallel (sharded) input: the rows of a partition may "
+                                    "lie on several ranks, and a shuffle across ranks is not implemented")
+        self.child = child
+        self.wexprs = [(w, str(name)) for w, name in wexprs]
+        self._schema = None
+
+    def children(self):
+        return [self.child]
+
+    def skey(self):
+        k = self._skey
+        if k == 0:
+            ck = self.child.skey()
+            ek = exprs_key([w for w, _ in self.wexprs]) if ck is not None else None
+            k = self._skey = intern(("Window", ck, ek, tuple(n for _, n in self.wexprs))) if ek is not None else None
+        return k
+
+    def schema(self):
+        if self._schema is None:
+            from .window import window_fields
+
+            cs = self.child.schema()
+            self._schema = StructType(list(cs.fields) + window_fields(cs, self.wexprs))
+        return self._schema
+
+    def references(self) -> set:
+        out = set()
+        for w, _ in self.wexprs:
+            out |= w.references()
+        return out
+
+    def _compute(self, session):
+        from .window import window_table
+
+        return window_table(execute(self.child, session), self.wexprs, self.schema(), session)
+
+    def _label(self):
+        return "Window [" + ", ".join(w.sql_name() for w, _ in self.wexprs) + "]"
+
+
+def build_project(child: LogicalPlan, exprs: Sequence[Expr]) -> LogicalPlan:
+    """``Project`` over ``child``.  A window expression anywhere inside ``exprs`` is computed by a
+    ``Window`` node underneath, under a hidden name, and replaced by a reference."""
+    from .window import contains_window, extract_windows
+
+    if not any(contains_window(e) for e in exprs):
+        return Project(child, exprs)
+    cs = child.schema()
+    for e in exprs:
+        e.data_type(cs)
+    out, found = extract_windows(exprs)
+    return Project(Window(child, found), out)
+
+
 def _orderable(o: SortOrder, dt) -> None:
     if isinstance(dt, VectorUDT):
         raise AnalysisException(f"cannot resolve '{o.sql_name()}' due to data type mismatch: cannot sort data type "
@@ -550,7 +617,8 @@ def build_sort(child: LogicalPlan, orders: Sequence[SortOrder], global_sort: boo
 def prune_columns(plan: LogicalPlan, required) -> LogicalPlan:
     """Catalyst-style ColumnPruning: a plan whose Projects compute only the output columns some
     consumer needs (``required``: column names, case-insensitive; None = all).  Filters keep
-    what their condition references, Sorts what their orders reference; leaves, Limit, Union and Join are
+    what their condition references, Sorts what their orders reference, Windows what their kept
+    expressions reference (a window column nobody reads is dropped); leaves, Limit, Union and Join are
     not pruned through.  Unchanged
     subtrees are returned as-is, so their memoized tables are reused.
 
@@ -585,6 +653,17 @@ def prune_columns(plan: LogicalPlan, required) -> LogicalPlan:
         if any(n.lower() not in req for n in names):  # columns only the orders need
             return Project(srt, [ColRef(n) for n in names if n.lower() in req])
         return srt
+    if isinstance(plan, Window):
+        keep = [(w, n) for w, n in plan.wexprs if n.lower() in req]
+        child_req = req - {n.lower() for _, n in plan.wexprs}
+        for w, _ in keep:
+            child_req |= {r.lower() for r in w.references()}
+        child = prune_columns(plan.child, child_req)
+        if not keep:
+            return child
+        if len(keep) == len(plan.wexprs) and child is plan.child:
+            return plan
+        return Window(child, keep)
     if isinstance(plan, Aggregate):
         # exactly the key and input references pass through, whatever the consumer asks for
         child = prune_columns(plan.child, plan.references())
