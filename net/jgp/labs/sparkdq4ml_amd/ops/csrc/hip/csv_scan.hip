@@ -5,8 +5,8 @@
 // line again on every action.  Here the file bytes go to HBM once and three kernels produce typed
 // columns in one parse:
 //   1. line terminators (\n, \r, \r\n — Hadoop LineRecordReader semantics; the lab's files are
-//      CR-only with no trailing terminator): per-block wave-ballot counts -> one-block scan ->
-//      ordered line-end offsets;
+//      CR-only with no trailing terminator): per-block wave-ballot counts -> one-block scan
+//      (scan_counts of scan.hip) -> ordered line-end offsets;
 //   2. one thread per line: split on the separator, parse every field to its exact f64 value
 //      (Clinger's fast path: mantissa < 2^53 and |exp10| <= 22, i.e. correctly rounded like
 //      java.lang.Double.parseDouble; integers up to 2^53), classify it into the lattice null < int
@@ -22,6 +22,8 @@
 
 #include "common.h"
 #include "csv_scan.h"
+#include "scan.h"
+#include "scan_host.h"
 
 namespace dq4ml {
 
@@ -98,46 +100,6 @@ __global__ __launch_bounds__(256) void csv_count_kernel(const uint8_t* __restric
   if (threadIdx.x == 0) counts[blockIdx.x] = (int64_t)ws[0] + ws[1] + ws[2] + ws[3];
 }
 
-// Exclusive scan of the per-block counts in place, total at counts[nb].  One block walks the
-// array in 4096-entry tiles: each thread owns 4 consecutive entries, a wave shfl_up scan and the
-// 16 wave totals in LDS give the tile prefix, a running carry joins the tiles.  (The first version
-// had each thread sum a contiguous 1/1024 of the array serially: 150 us for a 0.9 GB input.)
-__global__ __launch_bounds__(1024) void csv_scan_counts_kernel(int64_t* __restrict__ counts, int64_t nb) {
-  __shared__ int wsum[16];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int64_t carry = 0;
-  for (int64_t t0 = 0; t0 < nb; t0 += 4096) {
-    const int64_t i0 = t0 + 4 * (int64_t)threadIdx.x;
-    int v[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = i0 + k < nb ? (int)counts[i0 + k] : 0;  // <= kChunk each
-    const int s = v[0] + v[1] + v[2] + v[3];
-    int inc = s;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int t = __shfl_up(inc, o, 64);
-      if (lane >= o) inc += t;
-    }
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    int64_t before = carry + (inc - s), tot = 0;
-#pragma unroll
-    for (int w = 0; w < 16; ++w) {
-      const int x = wsum[w];
-      before += w < wave ? x : 0;
-      tot += x;
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      if (i0 + k < nb) counts[i0 + k] = before;
-      before += v[k];
-    }
-    carry += tot;
-    __syncthreads();  // wsum is rewritten by the next tile
-  }
-  if (threadIdx.x == 0) counts[nb] = carry;
-}
-
 constexpr int kEndsStage = 8192;  // line ends per block staged in LDS (block-relative int32)
 
 // Each thread finds its window's line ends; a block with at most kEndsStage of them collects them
@@ -171,13 +133,9 @@ __global__ __launch_bounds__(256) void csv_ends_kernel(const uint8_t* __restrict
     m = term_mask(b, n, base);
   }
   const int c = __popcll(m);
-  // exclusive prefix of the per-thread counts: wave scan (shfl_up) + wave totals in LDS
-  int inc = c;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += t;
-  }
+  // exclusive prefix of the per-thread counts: wave scan (scan.h) + wave totals in LDS, under the
+  // one barrier that the facts need anyway
+  const int inc = wave_inclusive<Add<int>>(c, lane);
   if (lane == 63) wtot[wave] = inc;
   __syncthreads();
   if (facts != nullptr && threadIdx.x < 4)
@@ -518,7 +476,7 @@ void csv_line_ends(const uint8_t* buf, int64_t n, int64_t* counts, void* ends, h
   if (facts != nullptr && (sep < 0 || sep > 255)) throw std::invalid_argument("csv_line_ends: facts need a separator byte");
   if (ends == nullptr) {  // pass 1: per-block counts -> exclusive offsets, total at counts[nb]
     hipLaunchKernelGGL(csv_count_kernel, dim3(nb), dim3(256), 0, st, buf, n, counts);
-    hipLaunchKernelGGL(csv_scan_counts_kernel, dim3(1), dim3(1024), 0, st, counts, nb);
+    scan_counts(counts, nb, st);
   } else if (csv_ends_i32(n)) {  // pass 2 (ends sized from counts[nb]); int32 offsets below 2 GiB
     hipLaunchKernelGGL((csv_ends_kernel<int32_t>), dim3(nb), dim3(256), 0, st, buf, n, counts,
                        static_cast<int32_t*>(ends), sep4, facts);

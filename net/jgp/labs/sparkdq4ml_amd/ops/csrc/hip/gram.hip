@@ -27,6 +27,7 @@
 #include "common.h"
 #include "gram.h"
 #include "gram_slab.h"
+#include "scan.h"
 
 namespace dq4ml {
 
@@ -1368,12 +1369,7 @@ __global__ __launch_bounds__(256) void patch_tiles_kernel(const u32x4* __restric
 #pragma unroll
       for (int j = 0; j < 4; ++j)
         c += (((r[i][j] >> 7) & 0xFFu) < base ? 1u : 0u) + (((r[i][j] >> 23) & 0xFFu) < base ? 1u : 0u);
-    uint32_t incl = c;  // inclusive scan of the lanes' counts
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t up = (uint32_t)__shfl_up((int)incl, o, 64);
-      if (lane >= o) incl += up;
-    }
+    const uint32_t incl = wave_inclusive<AddU32>(c, lane);  // inclusive scan of the lanes' counts
     const uint32_t tot = (uint32_t)__shfl((int)incl, 63, 64);
     if constexpr (!FILL) {
       if (lane == 0) counts[e] = tot;

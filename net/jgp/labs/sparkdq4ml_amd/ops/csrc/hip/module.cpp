@@ -24,6 +24,7 @@
 #include "wls_small.h"
 #include "wls_large.h"
 #include "rowops.h"
+#include "scan_host.h"
 #include "lsq.h"
 
 namespace py = pybind11;
@@ -388,6 +389,10 @@ PYBIND11_MODULE(_dq4ml_hip, m) {
     window_minmax(P<const void>(col), dt, P<const uint8_t>(valid), P<const unsigned>(perm), n, m_, P<const uint8_t>(heads),
                   is_max, backward, P<unsigned long long>(out), P<void>(totals), blocks, as_stream(stream));
   });
+  // self-test of the row walker of scan.h (the kinds: window.h); a: [rows][len], scanned in place
+  m.def("scan_rows", [](int kind, uintptr_t a, int64_t rows, int64_t len, uintptr_t stream) {
+    scan_rows(kind, P<void>(a), rows, len, as_stream(stream));
+  });
   // frame: (is_range, lo_unbounded, hi_unbounded, lo_off, hi_off); words: (kind, source, arg) each; out: [n][words] i64
   m.def("window_finish", [](uintptr_t bounds, uintptr_t perm, int64_t n, int64_t m_, bool is_range, bool lo_unbounded,
                             bool hi_unbounded, long long lo_off, long long hi_off, const std::vector<int>& kinds,
@@ -601,6 +606,10 @@ PYBIND11_MODULE(_dq4ml_hip, m) {
   });
 
   // ---- compaction (K3) -----------------------------------------------------------------------
+  // counts: [nb + 1] i64: the exclusive scan in place, the total at [nb]
+  m.def("scan_counts", [](uintptr_t counts, int64_t nb, uintptr_t stream) {
+    scan_counts(P<int64_t>(counts), nb, as_stream(stream));
+  });
   m.def("compact_blocks", &compact_blocks);
   m.def("compact_count_scan", [](uintptr_t sel, int64_t n, uintptr_t counts, uintptr_t stream) {
     compact_count_scan(P<const uint8_t>(sel), n, P<int64_t>(counts), as_stream(stream));

@@ -23,6 +23,7 @@
 
 #include "common.h"
 #include "keys.h"
+#include "scan.h"
 
 namespace dq4ml {
 namespace {
@@ -102,11 +103,12 @@ __global__ __launch_bounds__(kQuantThreads) void quantile_hist_kernel(QuantCols 
   }
 }
 
-// One block per column.  Thread t owns bin t of the target's slot.
+// One block per column.  Thread t owns bin t of the target's slot; the counts below a bin come
+// from scan.h's block scan, once per target.
 __global__ __launch_bounds__(kQuantBins) void quantile_pick_kernel(int Q, int pass, const double* probs, int64_t* state,
                                                                    unsigned long long* hist, double* values,
                                                                    int64_t* counts) {
-  __shared__ unsigned long long scan[kQuantBins];
+  __shared__ unsigned long long red[kQuantBins / kWave];
   __shared__ uint64_t npref[kMaxQuantiles];
   __shared__ int64_t nrank[kMaxQuantiles];
   __shared__ int64_t ntot;
@@ -119,22 +121,15 @@ __global__ __launch_bounds__(kQuantBins) void quantile_pick_kernel(int Q, int pa
   for (int q = 0; q < Q; ++q) {
     const int slot = pass == 0 ? 0 : (int)s[2 + Q + q];
     const unsigned long long cnt = H[slot * kQuantBins + t];
-    scan[t] = cnt;
-    __syncthreads();
-    for (int o = 1; o < kQuantBins; o <<= 1) {
-      const unsigned long long v = t >= o ? scan[t - o] : 0ull;
-      __syncthreads();
-      scan[t] += v;
-      __syncthreads();
-    }
-    const int64_t inc = (int64_t)scan[t];
-    const int64_t excl = inc - (int64_t)cnt;
+    unsigned long long total;
+    const int64_t excl = (int64_t)block_exclusive<AddU64, kQuantBins / kWave>(cnt, total, red);
+    const int64_t inc = excl + (int64_t)cnt;
     int64_t rank;
     uint64_t pref = 0;
     if (pass == 0) {
       // QuantileSummaries.query on an exact summary: p = 0 the minimum, p = 1 the maximum, else
       // the 1-based rank ceil(p * n) of one double multiply
-      const int64_t n = (int64_t)scan[kQuantBins - 1];
+      const int64_t n = (int64_t)total;
       const double p = probs[q];
       if (p <= 0.0) rank = 1;
       else if (p >= 1.0) rank = n;
@@ -149,8 +144,8 @@ __global__ __launch_bounds__(kQuantBins) void quantile_pick_kernel(int Q, int pa
       npref[q] = (pref << kQuantBits) | (uint64_t)t;
       nrank[q] = rank - excl;
     }
-    __syncthreads();  // scan is rewritten by the next target
   }
+  __syncthreads();
   // every read of state and hist is done: thread 0 regroups the targets by prefix, all re-zero
   if (t == 0) {
     int U = 0;

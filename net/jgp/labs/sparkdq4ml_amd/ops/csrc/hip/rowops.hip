@@ -3,7 +3,8 @@
 //
 //  * compact: Spark materializes filtered rows through ``take``/collect (show(n) = take(n+1),
 //    SURVEY.md S05).  Two passes: per-block live counts (wave ballot + popcount), one-block
-//    exclusive scan, then each block writes its indices at its offset — order preserving.
+//    exclusive scan (scan_counts of scan.hip), then each block writes its indices at its offset —
+//    order preserving.
 //  * pack: VectorAssembler.transform (DataQuality4MachineLearningApp.java:110-113) — each input
 //    column becomes one contiguous row of the feature-major [d, ld] output, cast to the output
 //    dtype; dead rows (selection false) can be written as zeros so the Gram kernel needs no mask.
@@ -14,6 +15,7 @@
 
 #include "common.h"
 #include "rowops.h"
+#include "scan_host.h"
 
 namespace dq4ml {
 
@@ -60,33 +62,6 @@ __global__ __launch_bounds__(256) void compact_count_kernel(const uint8_t* __res
   if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
   __syncthreads();
   if (threadIdx.x == 0) counts[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-}
-
-// exclusive scan in place + total at counts[nb]; single block
-__global__ __launch_bounds__(1024) void compact_scan_kernel(int64_t* __restrict__ counts, int64_t nb) {
-  __shared__ int64_t part[1024];
-  const int64_t per = (nb + 1023) / 1024;
-  const int64_t b0 = threadIdx.x * per, b1 = min(nb, b0 + per);
-  int64_t s = 0;
-  for (int64_t b = b0; b < b1; ++b) s += counts[b];
-  part[threadIdx.x] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int64_t run = 0;
-    for (int i = 0; i < 1024; ++i) {
-      const int64_t v = part[i];
-      part[i] = run;
-      run += v;
-    }
-    counts[nb] = run;
-  }
-  __syncthreads();
-  int64_t run = part[threadIdx.x];
-  for (int64_t b = b0; b < b1; ++b) {
-    const int64_t v = counts[b];
-    counts[b] = run;
-    run += v;
-  }
 }
 
 __global__ __launch_bounds__(256) void compact_write_kernel(const uint8_t* __restrict__ sel, int64_t n,
@@ -403,8 +378,7 @@ void compact_count_scan(const uint8_t* sel, int64_t n, int64_t* counts, hipStrea
     return;
   }
   hipLaunchKernelGGL(compact_count_kernel, dim3(nb), dim3(256), 0, st, sel, n, counts);
-  hipLaunchKernelGGL(compact_scan_kernel, dim3(1), dim3(1024), 0, st, counts, nb);
-  DQ_HIP_CHECK(hipGetLastError());
+  scan_counts(counts, nb, st);
 }
 
 void compact_write(const uint8_t* sel, int64_t n, const int64_t* offsets, int64_t limit, int64_t* out,

@@ -18,12 +18,14 @@
 //            tile is written to LDS in digit order and stored from there, so that consecutive
 //            lanes store consecutive positions of a digit value's run.
 // No kernel waits on another block; only integer LDS / global atomics and plain stores are used.
+// Both scans (the tiles of a digit value, the digit values of a tile) are scan.h's.
 #include "sort.h"
 
 #include <stdexcept>
 
 #include "common.h"
 #include "keys.h"
+#include "scan.h"
 
 namespace dq4ml {
 namespace {
@@ -115,44 +117,12 @@ __global__ __launch_bounds__(kSortThreads) void sort_count_kernel(const u64* key
 // block d: counts[d][0 .. tiles) -> base[d] + its exclusive scan, in place
 __global__ __launch_bounds__(kSortThreads) void sort_scan_kernel(unsigned* counts, int64_t stride, int64_t tiles,
                                                                  const u64* hist_row, const unsigned* base) {
-  __shared__ unsigned wsum[kSortWaves];
+  __shared__ unsigned red[kSortWaves];
   const int d = blockIdx.x;
   if (gptr<u64>(hist_row)[d] == 0) return;  // (block-uniform) no pair carries this digit value: its row is never read
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-  unsigned* row = counts + (int64_t)d * stride;
-  unsigned carry = gptr<unsigned>(base)[d];
-  for (int64_t t0 = 0; t0 < tiles; t0 += kSortThreads * 4) {
-    const int64_t t = t0 + (int64_t)threadIdx.x * 4;
-    const bool in = t < stride;  // (stride is a multiple of 4: the whole quad is inside the row)
-    u32x4 v = {0u, 0u, 0u, 0u};
-    if (in) v = *reinterpret_cast<const u32x4*>(row + t);
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      if (t + k >= tiles) v[k] = 0;  // the row's padding was never written
-    const unsigned s = v[0] + v[1] + v[2] + v[3];
-    unsigned inc = s;
-#pragma unroll
-    for (int o = 1; o < kWave; o <<= 1) {
-      const unsigned u = __shfl_up(inc, o, kWave);
-      if (lane >= o) inc += u;
-    }
-    if (lane == kWave - 1) wsum[wave] = inc;
-    __syncthreads();
-    unsigned before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < kSortWaves; ++w) {
-      const unsigned x = wsum[w];
-      if (w < wave) before += x;
-      total += x;
-    }
-    unsigned ex = carry + before + inc - s;
-    u32x4 o4;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) o4[k] = ex, ex += v[k];
-    if (in) *reinterpret_cast<u32x4*>(row + t) = o4;
-    carry += total;
-    __syncthreads();
-  }
+  // a thread owns a quad (stride is a multiple of 4: the whole quad is inside the row, and its
+  // padding, which the count kernel never wrote, reads as 0)
+  scan_row<AddU32, kSortWaves, 4>(counts + (int64_t)d * stride, tiles, gptr<unsigned>(base)[d], red);
 }
 
 __global__ __launch_bounds__(kSortThreads) void sort_scatter_kernel(const u64* keys_in, const unsigned* idx_in, u64* keys_out,
@@ -160,7 +130,7 @@ __global__ __launch_bounds__(kSortThreads) void sort_scatter_kernel(const u64* k
                                                                     const unsigned* counts, int64_t stride) {
   // per wave and digit value: the pairs ranked so far, then the wave's first slot in the staged tile
   __shared__ unsigned cnt[kSortWaves][kSortBins];
-  __shared__ unsigned dbase[kSortBins], wsum[kSortWaves];
+  __shared__ unsigned dbase[kSortBins], red[kSortWaves];
   __shared__ u64 skey[kSortTile];  // the tile staged in digit order (24 KiB with the indices)
   __shared__ unsigned sidx[kSortTile];
   const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
@@ -207,19 +177,8 @@ __global__ __launch_bounds__(kSortThreads) void sort_scatter_kernel(const u64* k
       unsigned tot = 0, pre[kSortWaves];
 #pragma unroll
       for (int w = 0; w < kSortWaves; ++w) pre[w] = tot, tot += cnt[w][threadIdx.x];
-      unsigned inc = tot;
-#pragma unroll
-      for (int o = 1; o < kWave; o <<= 1) {
-        const unsigned u = __shfl_up(inc, o, kWave);
-        if (lane >= o) inc += u;
-      }
-      if (lane == kWave - 1) wsum[wave] = inc;
-      __syncthreads();
-      unsigned before = 0;
-#pragma unroll
-      for (int w = 0; w < kSortWaves; ++w)
-        if (w < wave) before += wsum[w];
-      const unsigned start = before + inc - tot;  // first slot of digit value d in the staged tile
+      unsigned all;  // (the pairs of the tile)
+      const unsigned start = block_exclusive<AddU32, kSortWaves>(tot, all, red);  // first slot of digit value d in the staged tile
 #pragma unroll
       for (int w = 0; w < kSortWaves; ++w) cnt[w][threadIdx.x] = start + pre[w];
       // slot p of the staged tile goes to position dbase[d] + p (unsigned wrap-around is intended)

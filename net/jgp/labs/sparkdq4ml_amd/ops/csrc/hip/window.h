@@ -90,6 +90,12 @@ void window_prefix(const WinPrefixArgs& a, long long* prefix, long long* totals,
 void window_minmax(const void* col, int dt, const uint8_t* valid, const unsigned* perm, int64_t n, int64_t m,
                    const uint8_t* heads, bool is_max, bool backward, unsigned long long* out, void* totals, int blocks,
                    hipStream_t st);
+// Self-test of the row walker of scan.h under the operators it runs with: the exclusive scan of
+// every row of a [rows][len] array, in place.  kind 0: i64 add; 1: u32 add, four entries per thread
+// (the rows pitched at len rounded up to 4); 2 / 3: the forward / backward bounds triples of
+// window_bounds, 16 bytes (a, b, c, -) each; 4: the segmented min of window_minmax, 16 bytes (u64
+// key, u32 flag, -) each.
+void scan_rows(int kind, void* a, int64_t rows, int64_t len, hipStream_t st);
 // out: [n][words] i64, row perm[i] receives position i's words
 void window_finish(const WinFinishArgs& a, long long* out, int blocks, hipStream_t st);
 

@@ -26,36 +26,34 @@
 // thread owns kWinRun consecutive ones): tile totals, one block scanning the totals (kWinThreads
 // per trip), then the tile scan with its carry-in.  A backward scan counts its positions from the
 // end, so it is the same three launches.  No block waits on another, there is no atomic, every
-// loop is bounded, and every store is an ordinary vector store.
+// loop is bounded, and every store is an ordinary vector store.  The scans themselves (the block
+// scan of the tile kernels, the row walker over the totals) are scan.h's; the operators Bnd and
+// Seg below are the window semantics they run with.
 #include "window.h"
 
 #include <stdexcept>
 
 #include "common.h"
 #include "keys.h"
+#include "scan.h"
 
 namespace dq4ml {
 namespace {
 
 constexpr int kWinWaves = kWinThreads / kWave;
 
-template <class T>
-__device__ __forceinline__ T shfl_up_any(T v, int o) {
-  static_assert(sizeof(T) % 4 == 0, "shuffled in 32-bit words");
-  int w[sizeof(T) / 4];
-  __builtin_memcpy(w, &v, sizeof(T));
-#pragma unroll
-  for (unsigned k = 0; k < sizeof(T) / 4; ++k) w[k] = __shfl_up(w[k], o, kWave);
-  __builtin_memcpy(&v, w, sizeof(T));
-  return v;
+// block r: the exclusive scan of row r of a [rows][pitch] array, in place (scan.h's row walker, E
+// entries per thread): the step between the tile totals and the tile scan
+template <class S, int E>
+__global__ __launch_bounds__(kWinThreads) void scan_rows_kernel(typename S::T* a, int64_t pitch, int64_t len) {
+  __shared__ typename S::T red[kWinWaves];
+  scan_row<S, kWinWaves, E>(a + (int64_t)blockIdx.x * pitch, len, S::id(), red);
 }
 
-// the scan operators: T, its identity, and an associative op(earlier, later)
-struct AddI64 {
-  typedef long long T;
-  static __device__ __forceinline__ T id() { return 0; }
-  static __device__ __forceinline__ T op(T a, T b) { return a + b; }
-};
+template <class S, int E>
+void launch_scan_rows(typename S::T* a, int64_t rows, int64_t pitch, int64_t len, hipStream_t st) {
+  hipLaunchKernelGGL((scan_rows_kernel<S, E>), dim3((unsigned)rows), dim3(kWinThreads), 0, st, a, pitch, len);
+}
 
 // forward: (max, max, add) over (partition head position, peer head position, peer head);
 // backward: (min, min, -) over (partition end position, peer end position, -)
@@ -83,51 +81,6 @@ struct Seg {
     return T{x.key < y.key ? x.key : y.key, x.flag, 0u};
   }
 };
-
-// The exclusive scan of `agg` over the block's threads in thread order, and the block's total.
-// Every thread of the block calls this; red: [kWinWaves] in LDS.
-template <class S>
-__device__ __forceinline__ typename S::T block_exclusive(typename S::T agg, typename S::T& total, typename S::T* red) {
-  typedef typename S::T T;
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-  T inc = agg;
-#pragma unroll
-  for (int o = 1; o < kWave; o <<= 1) {
-    const T u = shfl_up_any(inc, o);
-    if (lane >= o) inc = S::op(u, inc);
-  }
-  T ex = shfl_up_any(inc, 1);
-  if (lane == 0) ex = S::id();
-  __syncthreads();  // the last call's readers are done with red
-  if (lane == kWave - 1) red[wave] = inc;
-  __syncthreads();
-  T before = S::id();
-  total = S::id();
-#pragma unroll
-  for (int w = 0; w < kWinWaves; ++w) {
-    const T x = red[w];
-    if (w < wave) before = S::op(before, x);
-    total = S::op(total, x);
-  }
-  return S::op(before, ex);
-}
-
-// block r: the exclusive scan of row r of totals [rows][tiles], in place
-template <class S>
-__global__ __launch_bounds__(kWinThreads) void win_totals_kernel(typename S::T* totals, int64_t tiles) {
-  typedef typename S::T T;
-  __shared__ T red[kWinWaves];
-  T* row = totals + (int64_t)blockIdx.x * tiles;
-  T carry = S::id();
-  for (int64_t t0 = 0; t0 < tiles; t0 += kWinThreads) {  // block-uniform
-    const int64_t t = t0 + threadIdx.x;
-    const T v = t < tiles ? row[t] : S::id();
-    T total;
-    const T ex = block_exclusive<S>(v, total, red);
-    if (t < tiles) row[t] = S::op(carry, ex);
-    carry = S::op(carry, total);
-  }
-}
 
 __global__ __launch_bounds__(kWinThreads) void win_heads_kernel(WinKeyArgs a, uint8_t* heads) {
   const int64_t tiles = (a.m + kWinTile - 1) / kWinTile;
@@ -187,7 +140,7 @@ __global__ __launch_bounds__(kWinThreads) void win_bounds_kernel(const uint8_t* 
       v[k] = agg;
     }
     T total;
-    const T ex = block_exclusive<S>(agg, total, red);
+    const T ex = block_exclusive<S, kWinWaves>(agg, total, red);
     if (!SCAN) {
       if (threadIdx.x == 0) totals[t] = total;
     } else {
@@ -261,7 +214,7 @@ __global__ __launch_bounds__(kWinThreads) void win_prefix_kernel(WinPrefixArgs a
           v[k] = agg;
         }
         long long total;
-        const long long ex = block_exclusive<AddI64>(agg, total, red);
+        const long long ex = block_exclusive<AddI64, kWinWaves>(agg, total, red);
         const int64_t W = a.woff[s] + w;
         if (!SCAN) {
           if (threadIdx.x == 0) totals[W * tiles + t] = total;
@@ -309,7 +262,7 @@ __global__ __launch_bounds__(kWinThreads) void win_minmax_kernel(const void* col
       v[k] = agg;
     }
     T total;
-    const T ex = block_exclusive<Seg>(agg, total, red);
+    const T ex = block_exclusive<Seg, kWinWaves>(agg, total, red);
     if (!SCAN) {
       if (threadIdx.x == 0) totals[t] = total;
     } else {
@@ -417,10 +370,10 @@ void window_bounds(const uint8_t* heads, int64_t m, unsigned* part_start, unsign
   Bnd<false>::T* tf = reinterpret_cast<Bnd<false>::T*>(totals);
   Bnd<true>::T* tb = reinterpret_cast<Bnd<true>::T*>(totals) + tiles;
   hipLaunchKernelGGL((win_bounds_kernel<false, false>), grid, block, 0, st, heads, m, part_start, peer_start, dense, tf);
-  hipLaunchKernelGGL(win_totals_kernel<Bnd<false>>, dim3(1), block, 0, st, tf, tiles);
+  launch_scan_rows<Bnd<false>, 1>(tf, 1, tiles, tiles, st);
   hipLaunchKernelGGL((win_bounds_kernel<false, true>), grid, block, 0, st, heads, m, part_start, peer_start, dense, tf);
   hipLaunchKernelGGL((win_bounds_kernel<true, false>), grid, block, 0, st, heads, m, part_end, peer_end, dense, tb);
-  hipLaunchKernelGGL(win_totals_kernel<Bnd<true>>, dim3(1), block, 0, st, tb, tiles);
+  launch_scan_rows<Bnd<true>, 1>(tb, 1, tiles, tiles, st);
   hipLaunchKernelGGL((win_bounds_kernel<true, true>), grid, block, 0, st, heads, m, part_end, peer_end, dense, tb);
   DQ_HIP_CHECK(hipGetLastError());
 }
@@ -448,7 +401,7 @@ void window_prefix(const WinPrefixArgs& a, long long* prefix, long long* totals,
   const int64_t tiles = win_tiles(a.m);
   const dim3 grid((unsigned)blocks), block(kWinThreads);
   hipLaunchKernelGGL(win_prefix_kernel<false>, grid, block, 0, st, a, prefix, totals, tiles);
-  hipLaunchKernelGGL(win_totals_kernel<AddI64>, dim3((unsigned)words), block, 0, st, totals, tiles);
+  launch_scan_rows<AddI64, 1>(totals, words, tiles, tiles, st);
   hipLaunchKernelGGL(win_prefix_kernel<true>, grid, block, 0, st, a, prefix, totals, tiles);
   DQ_HIP_CHECK(hipGetLastError());
 }
@@ -467,8 +420,23 @@ void window_minmax(const void* col, int dt, const uint8_t* valid, const unsigned
   Seg::T* tt = reinterpret_cast<Seg::T*>(totals);
   const int mx = is_max ? 1 : 0, bw = backward ? 1 : 0;
   hipLaunchKernelGGL(win_minmax_kernel<false>, grid, block, 0, st, col, dt, valid, perm, n, m, heads, mx, bw, out, tt);
-  hipLaunchKernelGGL(win_totals_kernel<Seg>, dim3(1), block, 0, st, tt, tiles);
+  launch_scan_rows<Seg, 1>(tt, 1, tiles, tiles, st);
   hipLaunchKernelGGL(win_minmax_kernel<true>, grid, block, 0, st, col, dt, valid, perm, n, m, heads, mx, bw, out, tt);
+  DQ_HIP_CHECK(hipGetLastError());
+}
+
+void scan_rows(int kind, void* a, int64_t rows, int64_t len, hipStream_t st) {
+  if (rows < 0 || len < 0) throw std::invalid_argument("scan_rows: negative shape");
+  if (rows == 0 || len == 0) return;
+  if (a == nullptr || (reinterpret_cast<uintptr_t>(a) & 15) != 0) throw std::invalid_argument("scan_rows: a 16-byte aligned buffer");
+  switch (kind) {
+    case 0: launch_scan_rows<AddI64, 1>(static_cast<long long*>(a), rows, len, len, st); break;
+    case 1: launch_scan_rows<AddU32, 4>(static_cast<unsigned*>(a), rows, (len + 3) & ~(int64_t)3, len, st); break;
+    case 2: launch_scan_rows<Bnd<false>, 1>(static_cast<Bnd<false>::T*>(a), rows, len, len, st); break;
+    case 3: launch_scan_rows<Bnd<true>, 1>(static_cast<Bnd<true>::T*>(a), rows, len, len, st); break;
+    case 4: launch_scan_rows<Seg, 1>(static_cast<Seg::T*>(a), rows, len, len, st); break;
+    default: throw std::invalid_argument("scan_rows: unknown kind");
+  }
   DQ_HIP_CHECK(hipGetLastError());
 }
 

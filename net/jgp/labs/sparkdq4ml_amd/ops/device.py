@@ -1176,6 +1176,16 @@ def _gram_syrk(h, X, y, w, sel, compute_f64: bool):
 
 
 # ------------------------------------------------------------------------------------------
+def scan_counts(counts: torch.Tensor) -> torch.Tensor:
+    """``counts``: int64 ``[nb + 1]``.  Its first ``nb`` entries become their exclusive scan, in
+    place, and entry ``nb`` their total (the step between a count pass and a write pass)."""
+    _check_dev(counts)
+    if counts.dtype != torch.int64 or counts.dim() != 1 or counts.numel() < 1 or not counts.is_contiguous():
+        raise ValueError("scan_counts: a contiguous int64 vector of nb + 1 entries")
+    native.hip().scan_counts(counts.data_ptr(), counts.numel() - 1, _stream())
+    return counts
+
+
 def compact_indices(sel: torch.Tensor, limit: Optional[int] = None) -> torch.Tensor:
     h = native.hip()
     _check_dev(sel)
