@@ -13,6 +13,8 @@ from .models.linalg import Vectors, DenseVector, SparseVector, Vector
 from .models.feature import VectorAssembler, Imputer, ImputerModel
 from .models.regression import (LinearRegression, LinearRegressionModel,
                                 LinearRegressionTrainingSummary)
+from .models.glm import (GeneralizedLinearRegression, GeneralizedLinearRegressionModel,
+                         GeneralizedLinearRegressionSummary, GeneralizedLinearRegressionTrainingSummary)
 from .models.tuning import (ParamGridBuilder, CrossValidator, CrossValidatorModel, TrainValidationSplit,
                             TrainValidationSplitModel)
 from .dq.rules import MinimumPriceDataQualityUdf, PriceCorrelationDataQualityUdf, IqrRule
@@ -26,4 +28,6 @@ __all__ = [
     "LinearRegressionTrainingSummary", "MinimumPriceDataQualityUdf", "PriceCorrelationDataQualityUdf",
     "ParamGridBuilder", "CrossValidator", "CrossValidatorModel", "TrainValidationSplit",
     "TrainValidationSplitModel", "Imputer", "ImputerModel", "IqrRule", "Window", "WindowSpec",
+    "GeneralizedLinearRegression", "GeneralizedLinearRegressionModel", "GeneralizedLinearRegressionSummary",
+    "GeneralizedLinearRegressionTrainingSummary",
 ]

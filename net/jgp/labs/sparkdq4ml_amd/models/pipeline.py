@@ -14,6 +14,7 @@ _CLASS_OF = {
     "VectorAssembler": "org.apache.spark.ml.feature.VectorAssembler",
     "LinearRegression": "org.apache.spark.ml.regression.LinearRegression",
     "LinearRegressionModel": "org.apache.spark.ml.regression.LinearRegressionModel",
+    "GeneralizedLinearRegression": "org.apache.spark.ml.regression.GeneralizedLinearRegression",
     "Pipeline": "org.apache.spark.ml.Pipeline",
     "PipelineModel": "org.apache.spark.ml.PipelineModel",
 }
@@ -21,12 +22,14 @@ _CLASS_OF = {
 
 def _stage_loader(cls_name: str):
     from .feature import VectorAssembler
+    from .glm import GeneralizedLinearRegression
     from .regression import LinearRegression, LinearRegressionModel
 
     return {
         "org.apache.spark.ml.feature.VectorAssembler": VectorAssembler,
         "org.apache.spark.ml.regression.LinearRegression": LinearRegression,
         "org.apache.spark.ml.regression.LinearRegressionModel": LinearRegressionModel,
+        "org.apache.spark.ml.regression.GeneralizedLinearRegression": GeneralizedLinearRegression,
         "org.apache.spark.ml.Pipeline": Pipeline,
         "org.apache.spark.ml.PipelineModel": PipelineModel,
     }[cls_name]

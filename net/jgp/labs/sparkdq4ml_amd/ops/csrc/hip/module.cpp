@@ -14,6 +14,7 @@
 #include "dqvm.h"
 #include "gram.h"
 #include "gram_folds.h"
+#include "glm_irls.h"
 #include "quantile.h"
 #include "groupby.h"
 #include "sort.h"
@@ -220,6 +221,23 @@ PYBIND11_MODULE(_dq4ml_hip, m) {
   m.def("fold_ids", [fold_rule](int64_t n, int64_t granule, const std::vector<uint32_t>& thr, uint64_t seed,
                                 uintptr_t out, uintptr_t stream) {
     fold_ids(n, granule, fold_rule(thr, seed), P<uint8_t>(out), as_stream(stream));
+  });
+  // ---- GLM IRLS (K5i): the fused reweighting + Gram pass and the iteration step ---------------
+  m.def("glm_irls_blocks", &glm_irls_blocks);
+  m.def("glm_irls_pass", [](uintptr_t X, int64_t ld, int d, int64_t n, int xdt, uintptr_t y, int ydt, uintptr_t w,
+                            int wdt, uintptr_t sel, uintptr_t beta, uintptr_t state, int family, int link, int mode,
+                            uintptr_t partials, int blocks, uintptr_t stream) {
+    GramArgs a{};
+    a.X = P<const void>(X);
+    a.ld = ld;
+    a.d = d;
+    a.n = n;
+    a.xdt = xdt;
+    set_rows(a, y, ydt, w, wdt, sel, partials);
+    glm_irls_pass(a, P<const double>(beta), P<const double>(state), family, link, mode, blocks, as_stream(stream));
+  });
+  m.def("glm_step", [](uintptr_t sol, int d, double tol, bool init, uintptr_t beta, uintptr_t state, uintptr_t stream) {
+    glm_step(P<const double>(sol), d, tol, init ? 1 : 0, P<double>(beta), P<double>(state), as_stream(stream));
   });
   m.def("quantile_blocks", &quantile_blocks);
   m.def("quantile_limits", []() { return py::make_tuple(kMaxQuantiles, kMaxQuantCols, kQuantPasses, kQuantBins); });

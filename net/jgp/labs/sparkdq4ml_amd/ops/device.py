@@ -436,6 +436,126 @@ def gram_stats_folds(X, y, sel, k_or_weights, seed: int, granule: int, compute: 
 
 
 # ------------------------------------------------------------------------------------------
+# GLM IRLS: the fused reweighting + Gram pass (csrc/hip/glm_irls.hip)
+# ------------------------------------------------------------------------------------------
+class _GlmPlan:
+    """Validated operands of the fused pass for one (X, y, w, sel): views, codes, grid, slabs."""
+
+    def __init__(self, X, y, w, sel, family: str, link: str, blocks: Optional[int]):
+        from . import glm
+
+        self.h = native.hip()
+        if not (torch.is_tensor(X) and X.dim() == 2 and X.dtype in (torch.float32, torch.float64)):
+            raise ValueError("glm_pass: dense f32 / f64 feature-major features only")
+        _check_dev(X, y, w, sel)
+        self.d, self.n = int(X.shape[0]), int(X.shape[1])
+        if not 1 <= self.d <= 64 or self.n < 1:
+            raise ValueError("glm_pass: needs 1 <= d <= 64 and n >= 1")
+        link = glm.resolve_link(family, link)
+        self.family, self.link = glm.FAMILIES[family], glm.LINKS[link]
+        self.Xv, self.ld = _feature_view(X, 16 // X.element_size())
+        self.y, self.w, self.sel = _prep_rows(y, w, sel, self.n)
+        self.xdt = dtype_code(self.Xv)
+        nb = blocks
+        if not nb:
+            key = (torch.cuda.current_device(), "glm", self.d, self.n, self.xdt)
+            nb = _plan_cache.get(key)
+            if nb is None:
+                nb = _plan_cache[key] = int(self.h.glm_irls_blocks(self.d, self.n, self.xdt))
+        self.nb = int(nb)
+        if self.nb < 1:
+            raise ValueError("glm_pass: blocks must be >= 1")
+        self.P = int(self.h.gram_partial_stride(0, self.d))
+        self.partials = torch.empty(self.nb * self.P, dtype=torch.float64, device=X.device)
+        self.flat = torch.empty(gram_layout_size(self.d), dtype=torch.float64, device=X.device)
+
+    def run(self, beta: Optional[torch.Tensor], state: Optional[torch.Tensor], mode: int) -> torch.Tensor:
+        """Enqueue pass + slab fold; returns ``self.flat`` (this rank's statistics)."""
+        st = _stream()
+        self.h.glm_irls_pass(self.Xv.data_ptr(), int(self.ld), self.d, self.n, self.xdt, self.y.data_ptr(),
+                             dtype_code(self.y), _ptr(self.w), _wdt(self.w), _ptr(self.sel), _ptr(beta), _ptr(state),
+                             self.family, self.link, int(mode), self.partials.data_ptr(), self.nb, st)
+        self.h.gram_reduce(0, self.partials.data_ptr(), self.nb, self.d, self.flat.data_ptr(), st)
+        return self.flat
+
+
+def glm_pass(X, y, w, sel, beta, family: str, link: str, mode: int, blocks: Optional[int] = None) -> torch.Tensor:
+    """One fused IRLS pass: the reduced statistics of ``(x, z, w')`` in the ``gram_stats`` layout.
+    ``beta``: ``[coef(d), intercept]`` (any array-like; read in STEP mode only)."""
+    plan = _GlmPlan(X, y, w, sel, family, link, blocks)
+    b = state = None
+    if int(mode) == 1:
+        b = _coef_dev(beta.detach().cpu().numpy() if torch.is_tensor(beta) else beta, X.device)
+        if b.numel() != plan.d + 1:
+            raise ValueError("glm_pass: beta must hold d coefficients and the intercept")
+        state = torch.zeros(4, dtype=torch.float64, device=X.device)
+    return plan.run(b, state, mode)
+
+
+def glm_step(sol: torch.Tensor, d: int, tol: float, init: bool, beta: torch.Tensor, state: torch.Tensor) -> None:
+    """Close an IRLS iteration on the device (``glm_step_kernel``): ``sol`` is ``wls_small``'s output,
+    ``beta`` ``[d + 1]`` and ``state`` ``[iter, done, status, max |delta|]`` are updated in place."""
+    _check_dev(sol, beta, state)
+    if (sol.dtype != torch.float64 or beta.dtype != torch.float64 or state.dtype != torch.float64
+            or sol.numel() < d + 2 or beta.numel() != d + 1 or state.numel() != 4
+            or not (sol.is_contiguous() and beta.is_contiguous() and state.is_contiguous())):
+        raise ValueError("glm_step: sol [>= d + 2], beta [d + 1], state [4] must be contiguous f64")
+    native.hip().glm_step(sol.data_ptr(), int(d), float(tol), bool(init), beta.data_ptr(), state.data_ptr(), _stream())
+
+
+class GlmLoop:
+    """The enqueued IRLS loop of one fit: device ``beta`` and ``state``, no host read inside
+    :meth:`start` / :meth:`iterate`.  In a data-parallel run the flat statistics are summed over
+    the ranks between the slab fold and the solve."""
+
+    def __init__(self, X, y, w, sel, family: str, link: str, fit_icpt: bool, reg: float, tol: float,
+                 blocks: Optional[int] = None):
+        self.plan = _GlmPlan(X, y, w, sel, family, link, blocks)
+        self.fit_icpt, self.reg, self.tol = bool(fit_icpt), float(reg), float(tol)
+        self.beta = torch.zeros(self.plan.d + 1, dtype=torch.float64, device=X.device)
+        self.state = torch.zeros(4, dtype=torch.float64, device=X.device)
+        self.flat = None
+
+    def _close(self, mode: int) -> None:
+        self.flat = comm.all_reduce_sum(self.plan.run(self.beta, self.state, mode))
+        sol = wls_small(self.flat, self.plan.d, self.fit_icpt, self.reg, 0.0, False, False)
+        glm_step(sol, self.plan.d, self.tol, mode == 0, self.beta, self.state)
+
+    def start(self) -> None:
+        self._close(0)
+
+    def iterate(self, k: int) -> None:
+        for _ in range(int(k)):
+            self._close(1)
+
+
+def glm_fit(X, y, w, sel, family: str, link: str, fit_icpt: bool, reg: float, max_iter: int, tol: float,
+            batch: int, blocks: Optional[int] = None) -> dict:
+    """IRLS on the device: the starting model, then reweighted iterations in batches of ``batch``
+    with one host read of the state after each.  Returns ``beta`` (host, ``[coef, intercept]``),
+    ``iterations``, ``done``, ``status`` (``wls_small``'s; non-zero: the caller re-runs on the host
+    route) and ``flat``, the device statistics of the last solve."""
+    loop = GlmLoop(X, y, w, sel, family, link, fit_icpt, reg, tol, blocks)
+    loop.start()
+    single = family == "gaussian" and loop.plan.link == 0  # gaussian / identity: the starting solve is the fit
+    left = 0 if single else max(int(max_iter), 0)
+    batch = max(int(batch), 1)
+    st = None
+    while left > 0:
+        k = min(batch, left)
+        loop.iterate(k)
+        left -= k
+        st = loop.state.cpu().numpy()
+        if st[1] != 0.0:
+            break
+    if st is None:
+        st = loop.state.cpu().numpy()
+    status = int(st[2])
+    return {"beta": loop.beta.cpu().numpy(), "iterations": int(st[0]), "done": status == 0 and (single or st[1] != 0.0),
+            "status": status, "max_delta": float(st[3]), "flat": loop.flat}
+
+
+# ------------------------------------------------------------------------------------------
 # exact quantiles: radix select (csrc/hip/quantile.hip)
 # ------------------------------------------------------------------------------------------
 # (the relational kernels below -- quantiles, groupby, sort, join -- share the key reader of keys.h;

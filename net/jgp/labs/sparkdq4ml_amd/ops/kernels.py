@@ -9,6 +9,7 @@ Ops:
   K3  ``selected_indices``   stream compaction of a selection vector
   K4  ``pack_columns``       columns -> feature-major [d, n] matrix (cast)
   K5  ``gram_stats``         WLS sufficient statistics (MFMA Gram) of [X | 1 | y] with weights/mask
+  K5i ``glm_pass``           one IRLS pass of a generalized linear model: statistics of (x, z, w')
   K5q ``quantiles``          exact order statistics of C columns x Q probabilities (radix select)
   K5g ``group_encode`` / ``group_agg``  group ids of key columns, integer-word grouped aggregates
   K5s ``sort_permutation``   stable multi-column radix sort of the live rows (row indices)
@@ -32,7 +33,7 @@ from .window import (window_bounds, window_finish, window_heads, window_limits, 
 from .join import join_key_columns, join_limits, join_mask, join_pairs  # noqa: F401  (K5j: dispatches by device itself)
 
 __all__ = ["selected_indices", "pack_columns", "gram_stats", "predict", "regression_metrics",
-           "gram_layout_size", "gram_stats_folds", "fold_ids", "fold_thresholds", "fold_seed", "quantiles", "group_encode", "group_encode_columns",
+           "gram_layout_size", "glm_pass", "gram_stats_folds", "fold_ids", "fold_thresholds", "fold_seed", "quantiles", "group_encode", "group_encode_columns",
            "group_agg", "group_scale", "group_limits", "sort_permutation", "sort_limits", "window_heads", "window_bounds",
            "window_prefix", "window_minmax", "window_finish", "window_limits", "join_pairs", "join_mask",
            "join_key_columns", "join_limits"]
@@ -161,6 +162,24 @@ def gram_stats(X: torch.Tensor, y: torch.Tensor, w: Optional[torch.Tensor], sel:
     out[5 + d:5 + 2 * d] = Xw @ yd
     out[5 + 2 * d:] = packed_upper(aa)
     return out
+
+
+# ------------------------------------------------------------------------------------------
+# K5i — one IRLS pass of a generalized linear model
+# ------------------------------------------------------------------------------------------
+def glm_pass(X: torch.Tensor, y: torch.Tensor, w: Optional[torch.Tensor], sel: Optional[torch.Tensor], beta,
+             family: str, link: str, mode: int, blocks: Optional[int] = None) -> torch.Tensor:
+    """Flat f64 statistics (the ``gram_stats`` layout) of ``(x, z, w')``: the working response and
+    weights of ``ops/glm.py`` from ``beta = [coef(d), intercept]`` (``mode`` 1, STEP) or of the
+    starting model (``mode`` 0, INIT).  Device tensors: the fused pass (d <= 64, f32 / f64
+    features); host tensors: its fp64 twin."""
+    if _on_gpu(X):
+        from . import device
+
+        return device.glm_pass(X, y, w, sel, beta, family, link, mode, blocks)
+    from . import glm
+
+    return glm.glm_pass_host(X, y, w, sel, beta, family, link, mode)
 
 
 # ------------------------------------------------------------------------------------------
