@@ -42,6 +42,15 @@ inline int grid_for(int per_cu, int64_t want) {
   return (int)(want < full ? want : full);
 }
 
+// the same with per_cu = the blocks of `kern` (block threads, lds bytes of dynamic LDS) that the
+// runtime reports co-resident on one CU
+template <typename K>
+inline int occupancy_grid(K kern, int block, size_t lds, int64_t want) {
+  int per = 0;
+  DQ_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kern, block, lds));
+  return grid_for(per < 1 ? 1 : per, want);
+}
+
 // launcher-side check of an open-addressing table's capacity (hashtable.h): a power of two in
 // [2, max]; the caller words the message, since each names its own bound
 inline void check_table(int64_t capacity, int64_t max, const char* msg) {

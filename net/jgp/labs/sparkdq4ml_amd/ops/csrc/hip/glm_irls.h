@@ -1,5 +1,5 @@
 // K5i: one IRLS (iteratively reweighted least squares) pass of a generalized linear model, fused
-// into the tall f64 Gram pass (see glm_irls.hip), and the one-block step that closes an iteration.
+// into a staged f64 Gram pass (see glm_irls.hip), and the one-block step that closes an iteration.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,14 +1,14 @@
 // K5i: one IRLS pass of a generalized linear model (Spark 2.4 GeneralizedLinearRegression) fused
-// into the tall f64 Gram pass: X is read once per iteration.
+// into a staged f64 Gram pass: X is read once per iteration.
 //
 // An IRLS iteration is a weighted least-squares fit of the working response z with the working
-// weights w', both functions of eta = x . beta + b of the row.  The tall f64 kernel (gram.hip,
-// gram_tall_f64_kernel) stages every 16-feature x 64-row tile of a superstep in LDS before the
-// MFMAs, so eta is formed right there: lane = row reads xs[f * kStageLd + lane] of the 16 staged
-// features (one bank per lane) against beta in LDS.  After the last tile the lane derives
-// mu, z, w' of its row in registers (plain f64 exp / log / sqrt / divide), writes w' and w'z to the
-// row-scalar area, and the pass goes on exactly as the plain kernel: column sums, X'z and the MFMA
-// Gram with x . w'.  The per-block slabs are gram_slab.h's, so gram_reduce and wls_small take them
+// weights w', both functions of eta = x . beta + b of the row.  The staged f64 loop (gram_slab.h
+// section 5; this kernel and gram_folds.hip's keep it) stages every 16-feature x 64-row tile of a
+// superstep in LDS before the MFMAs, so eta is formed right there: lane = row reads
+// xs[f * kStageLd + lane] of the 16 staged features (one bank per lane) against beta in LDS.
+// After the last tile the lane derives mu, z, w' of its row in registers (plain f64 exp / log /
+// sqrt / divide), writes w' and w'z to the row-scalar area, and the pass goes on as a plain
+// weighted statistics pass: column sums, X'z and the MFMA Gram with x . w'.  The per-block slabs are gram_slab.h's, so gram_reduce and wls_small take them
 // unchanged.  Dead rows (selection) and rows >= n are selected to zero, never multiplied: their
 // features and label may be NaN.  The ragged last superstep is staged through LDS too (guarded,
 // zero-filled), so one eta path serves both.  Plain launches, no atomics: bit-identical run to run.
@@ -307,11 +307,7 @@ __global__ __launch_bounds__(kWave) void glm_step_kernel(const double* __restric
   }
 }
 
-size_t glm_lds(int d) {
-  const size_t lds = kTallF64LoopBytes + 65 * sizeof(double);
-  const size_t red = (size_t)gram_partial_stride(GRAM_F64, d) * sizeof(double);
-  return red > lds ? red : lds;
-}
+size_t glm_lds(int d) { return staged_f64_lds(d, 65 * sizeof(double)); }  // (+ beta[65])
 
 template <typename TX, int FAM, int LINK, typename F>
 void with_glm_nt(int NT, F&& f) {
@@ -363,36 +359,22 @@ bool glm_pair_ok(int family, int link) {
 
 int glm_irls_blocks(int d, int64_t n, int xdt) {
   if (d < 1 || d > 64) throw std::invalid_argument("glm_irls: d must be in [1, 64]");
-  int per = 0;
+  int nb = 1;
   // (the register count, and so the occupancy, is the Gram loop's: one pair stands for all)
-  with_glm_kernel(xdt, d, GLM_BINOMIAL, GLM_LOGIT, [&](auto kern) {
-    DQ_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kern, kBlock, glm_lds(d)));
-  });
-  const int64_t nsuper = (n + 63) / 64;
-  return grid_for(per < 1 ? 1 : per, (nsuper + 4 * kWavesPerBlock - 1) / (4 * kWavesPerBlock));
+  with_glm_kernel(xdt, d, GLM_BINOMIAL, GLM_LOGIT, [&](auto kern) { nb = staged_f64_blocks(kern, glm_lds(d), n); });
+  return nb;
 }
 
 void glm_irls_pass(GramArgs a, const double* beta, const double* state, int family, int link, int mode, int blocks,
                    hipStream_t st) {
-  if (a.d < 1 || a.d > 64) throw std::invalid_argument("glm_irls: d must be in [1, 64]");
-  if (blocks < 1) throw std::invalid_argument("glm_irls: blocks must be >= 1");
-  if (a.n < 1) throw std::invalid_argument("glm_irls: n must be >= 1");
+  staged_f64_plan(a, blocks, "glm_irls");
   if (!glm_pair_ok(family, link)) throw std::invalid_argument("glm_irls: unsupported (family, link) pair");
   if (mode != GLM_INIT && mode != GLM_STEP) throw std::invalid_argument("glm_irls: mode must be INIT (0) or STEP (1)");
   if (mode == GLM_STEP && (beta == nullptr || state == nullptr))
     throw std::invalid_argument("glm_irls: a STEP pass needs beta and state");
-  if (a.ydt != DT_F64 && a.ydt != DT_F32) throw std::invalid_argument("glm_irls: label must be f32 or f64");
   if (a.w != nullptr && a.wdt != DT_F64 && a.wdt != DT_F32)
     throw std::invalid_argument("glm_irls: weights must be f32 or f64");
   if (a.partials == nullptr || a.X == nullptr || a.y == nullptr) throw std::invalid_argument("glm_irls: null operand");
-  const int64_t esz = a.xdt == DT_F64 ? 8 : 4;
-  if ((reinterpret_cast<uintptr_t>(a.X) & 15) || (a.d > 1 && (a.ld * esz) % 16) || a.ld < a.n)
-    throw std::invalid_argument("glm_irls: feature rows must be 16-byte aligned and ld >= n");
-  a.nsuper = (a.n + 63) / 64;
-  const int64_t total_waves = (int64_t)blocks * kWavesPerBlock;
-  a.spw = (a.nsuper + total_waves - 1) / total_waves;
-  if (a.spw < 1) a.spw = 1;
-  a.P = (int)gram_partial_stride(GRAM_F64, a.d);
   const GlmArgs g{beta, state, mode};
   const size_t lds = glm_lds(a.d);
   with_glm_kernel(a.xdt, a.d, family, link,

@@ -26,8 +26,13 @@ struct GramArgs {
   const uint8_t* sel;  // selection [n] (bool) or null
   double* partials;    // [blocks][P]
   int P;
-  int64_t spw;         // supersteps (64 rows) per wave, one contiguous range (the tall bf16 kernel has its own map)
-  int64_t nsuper;      // n / 64
+  // Set by each launcher for its kernel.  spw: supersteps (64 rows; gram_cols: per block; the
+  // stream kernels: stages of 64 or 32 rows) of a wave's one contiguous range; the tall bf16 kernel
+  // interleaves the waves and does not read it.  nsuper: the supersteps the ranges cover -- full
+  // ones only, n / 64 (gram_tall) or n / stage rows (gram_stream), the ragged rest handled apart;
+  // the ragged one included, ceil(n / 64), for gram_cols, gram_folds and glm_irls_pass.
+  int64_t spw;
+  int64_t nsuper;
   int tiled;           // X is MFMA-fragment-ordered bf16 (tile_bf16 layout)
   // columnar skinny f64 mode (cols = d <= 8, X unused): feature f is the source column colp[f]
   // of DType coldt[f] — a VectorAssembler output read straight from its inputs, never packed

@@ -17,8 +17,9 @@
 //  * Column sums and Xᵀy ride on a second MFMA with B = [w_hi, w_lo, wy_hi, wy_lo, 0...]: the
 //    per-row scalars are computed lane = row (coalesced), split hi/lo into bf16 (≈16-bit
 //    mantissa for the label) and handed to the fragment layout through a 512-byte LDS stripe.
-//  * f64 mode (Spark-parity path) uses v_mfma_f64_16x16x4_f64 with 16-feature tiles and exact
-//    f64 side sums on the VALU.
+//  * f64 mode (Spark-parity path): d <= 8 takes the lane-per-row skinny kernel below, d > 8 the
+//    stream kernel (gram_stream.hip: v_mfma_f64_16x16x4_f64 on 16-feature tiles), which also takes
+//    the f32 modes and bf16 mode on row-major f32 storage.  This file's MFMA kernels are bf16 only.
 //  * Per-wave f32 (bf16 mode) / f64 accumulators -> deterministic in-block wave reduction in
 //    LDS -> one f64 partial slab per block (format: gram_slab.h) -> ``gram_reduce`` sums slabs in
 //    a fixed order (no atomics: bit-reproducible run to run).
@@ -144,31 +145,6 @@ __device__ __forceinline__ void load_rows32_bf16<uint16_t>(const uint16_t* p, in
         fr[i][j] = __builtin_bit_cast(__bf16, b);
       }
     }
-  }
-}
-
-template <>
-__device__ __forceinline__ void load_rows32_bf16<float>(const float* p, int64_t rows_left, bf16x8 (&fr)[4]) {
-  if (rows_left >= 32) {
-    const f32x4* q = reinterpret_cast<const f32x4*>(p);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      f32x4 a = __builtin_nontemporal_load(q + 2 * i);
-      f32x4 b = __builtin_nontemporal_load(q + 2 * i + 1);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        fr[i][j] = (__bf16)a[j];
-        fr[i][4 + j] = (__bf16)b[j];
-      }
-    }
-  } else {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int e = 8 * i + j;
-        fr[i][j] = (__bf16)(e < rows_left ? p[e] : 0.0f);
-      }
   }
 }
 
@@ -831,168 +807,6 @@ __global__ __launch_bounds__(256, (NT == 1 ? 3 : 2)) void gram_cols_kernel(GramA
 }
 
 // =============================================================================================
-// f64 MFMA kernel (v_mfma_f64_16x16x4_f64): Spark-parity precision
-// =============================================================================================
-template <typename TX, int NT>
-__global__ __launch_bounds__(kBlock) void gram_tall_f64_kernel(GramArgs a) {
-  constexpr int NPAIR = NT * (NT + 1) / 2;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  const int f = lane & 15, q = lane >> 4;
-  double* lw = reinterpret_cast<double*>(smem) + wave * 128;  // [w(64), wy(64)]
-  // per-wave staging of one 16-feature x 64-row tile, rows padded to kStageLd doubles
-  double* xs = reinterpret_cast<double*>(smem) + kWavesPerBlock * 128 + wave * (16 * kStageLd);
-
-  // kChains independent accumulators per tile pair: 16 back-to-back dependent f64 MFMAs per
-  // superstep otherwise serialize on the MFMA latency
-  constexpr int kChains = NT >= 2 ? 2 : 4;  // fewer for many pairs: VGPRs -> occupancy
-  f64x4 acc[NPAIR][kChains];
-#pragma unroll
-  for (int p = 0; p < NPAIR; ++p)
-#pragma unroll
-    for (int c = 0; c < kChains; ++c) acc[p][c] = f64x4{};
-  double cs[NT], ab[NT];
-#pragma unroll
-  for (int t = 0; t < NT; ++t) cs[t] = ab[t] = 0.0;
-  RowAcc ra;
-
-  const TX* X = reinterpret_cast<const TX*>(a.X);
-  const TX* fp[NT];
-  bool fvalid[NT];
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    const int feat = t * 16 + f;
-    fvalid[t] = feat < a.d;
-    fp[t] = X + (int64_t)(fvalid[t] ? feat : 0) * a.ld + 16 * q;
-  }
-  const bool weighted = (a.sel != nullptr) || (a.w != nullptr);
-
-  const int64_t gw = (int64_t)blockIdx.x * kWavesPerBlock + wave;
-  const int64_t total_waves = (int64_t)gridDim.x * kWavesPerBlock;
-  int64_t s0 = gw * a.spw;
-  int64_t s1 = s0 + a.spw;
-  if (s1 > a.nsuper) s1 = a.nsuper;
-  const bool do_tail = (gw == total_waves - 1) && (a.n > a.nsuper * 64);
-  const int64_t s_end = do_tail ? a.nsuper + 1 : s1;
-  if (do_tail && s0 > a.nsuper) s0 = a.nsuper;
-
-  for (int64_t s = s0; s < s_end; ++s) {
-    const int64_t r0 = s * 64;
-    RowVals rv = row_vals(a, r0 + lane);
-    ra.add(rv);
-    lw[lane] = rv.live ? rv.w : 0.0;
-    lw[64 + lane] = rv.live ? rv.wy : 0.0;
-    __builtin_amdgcn_wave_barrier();
-    const int64_t rows_left = a.n - (r0 + 16 * q);
-    double wv[16], wyv[16];
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      wv[e] = lw[16 * q + e];
-      wyv[e] = lw[64 + 16 * q + e];
-    }
-    double x[NT][16];
-    // (load_superstep_f64 of gram_slab.h, kept in line here: behind the call the <float, 4>
-    // instantiation spills four more registers)
-    if (s < a.nsuper) {
-#pragma unroll
-      for (int t = 0; t < NT; ++t) {
-        stage_tile<TX>(X, a.ld, a.d, t * 16, r0, lane, xs);
-        __builtin_amdgcn_wave_barrier();
-        const f64x2* src = reinterpret_cast<const f64x2*>(xs + f * kStageLd + 16 * q);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          const f64x2 v = src[i];
-          x[t][2 * i] = v[0];
-          x[t][2 * i + 1] = v[1];
-        }
-        __builtin_amdgcn_wave_barrier();
-      }
-    } else {
-#pragma unroll
-      for (int t = 0; t < NT; ++t) {
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          double v = 0.0;
-          if (fvalid[t] && e < rows_left) v = (double)fp[t][r0 + e];
-          x[t][e] = v;
-        }
-      }
-    }
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        cs[t] += x[t][e] * wv[e];
-        ab[t] += x[t][e] * wyv[e];
-      }
-    int p = 0;
-#pragma unroll
-    for (int I = 0; I < NT; ++I)
-#pragma unroll
-      for (int J = I; J < NT; ++J, ++p)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const double b = weighted ? x[J][e] * wv[e] : x[J][e];
-          acc[p][e % kChains] = __builtin_amdgcn_mfma_f64_16x16x4f64(x[I][e], b, acc[p][e % kChains], 0, 0, 0);
-        }
-    __builtin_amdgcn_wave_barrier();
-  }
-
-  const int d = a.d;
-  const int P = a.P;
-  __syncthreads();
-  double* red = reinterpret_cast<double*>(smem);
-  for (int i = threadIdx.x; i < P; i += kBlock) red[i] = 0.0;
-  double sc[kSlabScalars];
-  wave_scalars(ra, sc);
-  // combine the 4 row-groups q of each feature
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    cs[t] += __shfl_xor(cs[t], 16, 64);
-    cs[t] += __shfl_xor(cs[t], 32, 64);
-    ab[t] += __shfl_xor(ab[t], 16, 64);
-    ab[t] += __shfl_xor(ab[t], 32, 64);
-  }
-  __syncthreads();
-  for (int wvi = 0; wvi < kWavesPerBlock; ++wvi) {
-    if (wave == wvi) {
-      if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < kSlabScalars; ++k) red[k] += sc[k];
-      }
-      if (q == 0) {
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-          const int feat = t * 16 + f;
-          if (feat < d) {
-            red[kSlabScalars + feat] += cs[t];
-            red[kSlabScalars + d + feat] += ab[t];
-          }
-        }
-      }
-      int p = 0;
-#pragma unroll
-      for (int I = 0; I < NT; ++I)
-#pragma unroll
-        for (int J = I; J < NT; ++J, ++p) {
-          double* tile = slab_tile<16>(red, d, p);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            double v = 0.0;
-#pragma unroll
-            for (int c = 0; c < kChains; ++c) v += acc[p][c][r];
-            tile[mfma16d_row(lane, r) * 16 + mfma16d_col(lane)] += v;
-          }
-        }
-    }
-    __syncthreads();
-  }
-  double* out = a.partials + (int64_t)blockIdx.x * P;
-  for (int i = threadIdx.x; i < P; i += kBlock) out[i] = red[i];
-}
-
-// =============================================================================================
 // f64 "skinny" kernel, d <= 8 (the lab's own shape: d = 1): lane = row, every statistic a running
 // f64 register sum on the VALU.  The MFMA kernel maps 16 features to lanes, so at d = 1 15/16 of
 // its lanes idle and each load instruction fetches 4 x 8 B (0.9 TB/s measured); here every lane
@@ -1521,16 +1335,6 @@ int64_t gram_partial_stride(int mode, int d) {
   return mode == GRAM_F64 ? slab_stride<16>(d) : slab_stride<32>(d);
 }
 
-template <typename K>
-static int occupancy_blocks(K kern, size_t lds, int block) {
-  int per = 0, dev = 0, cus = 0;
-  DQ_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kern, block, lds));
-  DQ_HIP_CHECK(hipGetDevice(&dev));
-  DQ_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  if (per < 1) per = 1;
-  return per * cus;
-}
-
 static size_t bf16_lds(int d) {
   const int W = kBf16Block / kWave;
   const int NT = (d + 31) / 32;
@@ -1539,51 +1343,29 @@ static size_t bf16_lds(int d) {
   return tree > stripes ? tree : stripes;
 }
 
-static size_t f64_lds(int d) {
-  const size_t lds = kTallF64LoopBytes;
-  const size_t red = (size_t)gram_partial_stride(GRAM_F64, d) * sizeof(double);
-  return red > lds ? red : lds;
-}
-
-// Dispatch table: call F with the kernel instantiation for (mode, xdt, d, xmode, storage, companion).
+// Dispatch table of the bf16 kernel: call F with its instantiation for (xdt, d, xmode, storage,
+// companion).  Row-major f32 storage is not here: it rides the stream kernel (gram_stream.hip).
 template <typename F>
 static void with_kernel(int mode, int xdt, int d, int xmode, bool tiled, Companion comp, F&& f) {
-  if (mode == GRAM_BF16) {
-    const int NT = (d + 31) / 32;
-    constexpr Companion kRaw = Companion::kRaw, kMixed = Companion::kMixed, kPatched = Companion::kPatched;
-#define DQ_BF16_CASE(TX, NTV, TL, CO)                                    \
-    if (xmode == 0) return f(gram_tall_bf16_kernel<TX, NTV, 0, TL, CO>); \
-    if (xmode == 1) return f(gram_tall_bf16_kernel<TX, NTV, 1, TL, CO>); \
-    return f(gram_tall_bf16_kernel<TX, NTV, 2, TL, CO>);
-    if (comp != kRaw && !(xdt == DT_BF16 && tiled)) throw std::invalid_argument("gram_tall: packed tiles need tiled bf16 storage");
-    if (comp == kPatched) {  // (XMODE 0 only: check_companion)
-      if (NT == 1) return f(gram_tall_bf16_kernel<uint16_t, 1, 0, true, kPatched>);
-      return f(gram_tall_bf16_kernel<uint16_t, 2, 0, true, kPatched>);
-    }
-    if (comp == kMixed) { if (NT == 1) { DQ_BF16_CASE(uint16_t, 1, true, kMixed) } else { DQ_BF16_CASE(uint16_t, 2, true, kMixed) } }
-    if (xdt == DT_BF16 && tiled) { if (NT == 1) { DQ_BF16_CASE(uint16_t, 1, true, kRaw) } else { DQ_BF16_CASE(uint16_t, 2, true, kRaw) } }
-    if (tiled) throw std::invalid_argument("gram_tall: tiled storage must be bf16");
-    if (xdt == DT_BF16) { if (NT == 1) { DQ_BF16_CASE(uint16_t, 1, false, kRaw) } else { DQ_BF16_CASE(uint16_t, 2, false, kRaw) } }
-    if (xdt == DT_F32) { if (NT == 1) { DQ_BF16_CASE(float, 1, false, kRaw) } else { DQ_BF16_CASE(float, 2, false, kRaw) } }
-    if (xdt == DT_F64) { if (NT == 1) { DQ_BF16_CASE(double, 1, false, kRaw) } else { DQ_BF16_CASE(double, 2, false, kRaw) } }
+  if (mode != GRAM_BF16) throw std::invalid_argument("gram_tall: no kernel for this mode and feature dtype");
+  const int NT = (d + 31) / 32;
+  constexpr Companion kRaw = Companion::kRaw, kMixed = Companion::kMixed, kPatched = Companion::kPatched;
+#define DQ_BF16_CASE(TX, NTV, TL, CO)                                  \
+  if (xmode == 0) return f(gram_tall_bf16_kernel<TX, NTV, 0, TL, CO>); \
+  if (xmode == 1) return f(gram_tall_bf16_kernel<TX, NTV, 1, TL, CO>); \
+  return f(gram_tall_bf16_kernel<TX, NTV, 2, TL, CO>);
+  if (comp != kRaw && !(xdt == DT_BF16 && tiled)) throw std::invalid_argument("gram_tall: packed tiles need tiled bf16 storage");
+  if (comp == kPatched) {  // (XMODE 0 only: check_companion)
+    if (NT == 1) return f(gram_tall_bf16_kernel<uint16_t, 1, 0, true, kPatched>);
+    return f(gram_tall_bf16_kernel<uint16_t, 2, 0, true, kPatched>);
+  }
+  if (comp == kMixed) { if (NT == 1) { DQ_BF16_CASE(uint16_t, 1, true, kMixed) } else { DQ_BF16_CASE(uint16_t, 2, true, kMixed) } }
+  if (xdt == DT_BF16 && tiled) { if (NT == 1) { DQ_BF16_CASE(uint16_t, 1, true, kRaw) } else { DQ_BF16_CASE(uint16_t, 2, true, kRaw) } }
+  if (tiled) throw std::invalid_argument("gram_tall: tiled storage must be bf16");
+  if (xdt == DT_BF16) { if (NT == 1) { DQ_BF16_CASE(uint16_t, 1, false, kRaw) } else { DQ_BF16_CASE(uint16_t, 2, false, kRaw) } }
+  if (xdt == DT_F64) { if (NT == 1) { DQ_BF16_CASE(double, 1, false, kRaw) } else { DQ_BF16_CASE(double, 2, false, kRaw) } }
 #undef DQ_BF16_CASE
-    throw std::invalid_argument("gram_tall(bf16): unsupported feature dtype");
-  }
-  if (mode == GRAM_F64) {
-    const int NT = (d + 15) / 16;
-#define DQ_F64_CASE(TX)                                        \
-    switch (NT) {                                              \
-      case 1: return f(gram_tall_f64_kernel<TX, 1>);           \
-      case 2: return f(gram_tall_f64_kernel<TX, 2>);           \
-      case 3: return f(gram_tall_f64_kernel<TX, 3>);           \
-      default: return f(gram_tall_f64_kernel<TX, 4>);          \
-    }
-    if (xdt == DT_F64) { DQ_F64_CASE(double) }
-    if (xdt == DT_F32) { DQ_F64_CASE(float) }
-#undef DQ_F64_CASE
-    throw std::invalid_argument("gram_tall(f64): unsupported feature dtype");
-  }
-  throw std::invalid_argument("gram_tall: unsupported mode");
+  throw std::invalid_argument("gram_tall(bf16): unsupported feature dtype");
 }
 
 constexpr int kSkinnyMaxD = 8;
@@ -1642,24 +1424,19 @@ int gram_plan_blocks(int mode, int d, int64_t n, int xdt, int xmode) {
       (mode == GRAM_F64 && !use_skinny(mode, d, xdt, 0) && (xdt == DT_F64 || xdt == DT_F32)) ||
       (mode == GRAM_BF16 && xdt == DT_F32))
     return gram_stream_blocks(mode, d, n, xdt);
+  int nb = 1;
   if (use_skinny(mode, d, xdt, 0)) {
-    int full = 1;
-    with_skinny(xdt, d, [&](auto kern) { full = occupancy_blocks(kern, 0, kBlock); });
     // >= 8 iterations of 4 rows per thread, at most one resident wave of blocks
-    int64_t want = (n + (int64_t)kBlock * 4 * 8 - 1) / ((int64_t)kBlock * 4 * 8);
-    if (want < 1) want = 1;
-    return (int)(want < full ? want : full);
+    const int64_t want = (n + (int64_t)kBlock * 4 * 8 - 1) / ((int64_t)kBlock * 4 * 8);
+    with_skinny(xdt, d, [&](auto kern) { nb = occupancy_grid(kern, kBlock, 0, want); });
+    return nb;
   }
-  const size_t lds = mode == GRAM_BF16 ? bf16_lds(d) : f64_lds(d);
-  int full = 1;
-  const int block = mode == GRAM_BF16 ? kBf16Block : kBlock;
-  with_kernel(mode, xdt, d, xmode, false, Companion::kRaw, [&](auto kern) { full = occupancy_blocks(kern, lds, block); });
-  // at least ~4 supersteps per wave, at most one full residency wave of blocks
+  // the bf16 kernel: at least ~4 supersteps per wave, at most one full residency wave of blocks
   const int64_t nsuper = (n + 63) / 64;
-  const int wpb = block / kWave;
-  int64_t want = (nsuper + 4 * wpb - 1) / (4 * wpb);
-  if (want < 1) want = 1;
-  return (int)(want < full ? want : full);
+  constexpr int wpb = kBf16Block / kWave;
+  with_kernel(mode, xdt, d, xmode, false, Companion::kRaw,
+              [&](auto kern) { nb = occupancy_grid(kern, kBf16Block, bf16_lds(d), (nsuper + 4 * wpb - 1) / (4 * wpb)); });
+  return nb;
 }
 
 void gram_window_fold(const double* part, int64_t rows, int gw, double* flat, hipStream_t st) {
@@ -1705,13 +1482,8 @@ static Companion check_companion(int mode, const GramArgs& a, int xmode) {
 void gram_tall(int mode, GramArgs a, int xmode, int blocks, double* out, hipStream_t st, bool reduce) {
   if (a.d < 1 || a.d > 64) throw std::invalid_argument("gram_tall: d must be in [1, 64]");
   if (blocks < 1) throw std::invalid_argument("gram_tall: blocks must be >= 1");
-  a.nsuper = a.n / 64;
-  const int block = mode == GRAM_BF16 ? kBf16Block : kBlock;
-  const int64_t total_waves = (int64_t)blocks * (block / kWave);
-  a.spw = (a.nsuper + total_waves - 1) / total_waves;
-  if (a.spw < 1) a.spw = 1;
+  a.nsuper = a.n / 64;  // (the bf16 kernel's wave -> superstep map needs no spw)
   a.P = (int)gram_partial_stride(mode, a.d);
-  const size_t lds = mode == GRAM_BF16 ? bf16_lds(a.d) : f64_lds(a.d);
   if (a.tiled && mode != GRAM_BF16) throw std::invalid_argument("gram_tall: tiled storage needs bf16 mode");
   const Companion comp = check_companion(mode, a, xmode);
   if (a.xshift) {
@@ -1734,9 +1506,13 @@ void gram_tall(int mode, GramArgs a, int xmode, int blocks, double* out, hipStre
     return;
   } else if (mode == GRAM_F32 || mode == GRAM_F32S) {
     throw std::invalid_argument("gram_tall(f32): needs 16-byte aligned f32 features and f32/f64 labels");
+  } else if (mode == GRAM_F64) {  // (past the skinny kernel the stream kernel is this mode's only one)
+    throw std::invalid_argument("gram_tall(f64): needs 16-byte aligned f32/f64 features and f32/f64 labels");
+  } else if (mode == GRAM_BF16 && a.xdt == DT_F32) {
+    throw std::invalid_argument("gram_tall(bf16): f32 storage needs 16-byte aligned features and f32/f64 labels");
   } else {
     with_kernel(mode, a.xdt, a.d, xmode, a.tiled != 0, comp,
-                [&](auto kern) { hipLaunchKernelGGL(kern, dim3(blocks), dim3(block), lds, st, a); });
+                [&](auto kern) { hipLaunchKernelGGL(kern, dim3(blocks), dim3(kBf16Block), bf16_lds(a.d), st, a); });
   }
   DQ_HIP_CHECK(hipGetLastError());
   if (reduce) gram_reduce(mode, a.partials, blocks, a.d, out, st);
@@ -1766,12 +1542,11 @@ static void with_cols_kernel(int NT, int sdt, int ydt, F&& f) {
 
 int gram_cols_blocks(int d, int64_t n) {
   const int NT = (d + 31) / 32;
-  int full = 1;
-  with_cols_kernel(NT, DT_F32, DT_F64, [&](auto k) { full = occupancy_blocks(k, cols_lds(NT), 256); });
+  int nb = 1;
   const int64_t nsup = (n + 63) / 64;
-  int64_t want = (nsup + 3) / 4;  // >= 4 supersteps per block
-  if (want < 1) want = 1;
-  return (int)(want < full ? want : full);
+  // >= 4 supersteps per block
+  with_cols_kernel(NT, DT_F32, DT_F64, [&](auto k) { nb = occupancy_grid(k, 256, cols_lds(NT), (nsup + 3) / 4); });
+  return nb;
 }
 
 void gram_cols(GramArgs a, const PackSrcG* srcs_dev, int sdt, int blocks, double* out, hipStream_t st) {

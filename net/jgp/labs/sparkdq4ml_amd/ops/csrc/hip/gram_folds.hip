@@ -6,13 +6,13 @@
 //
 // Fold rule (gram_folds.h): rows are grouped in granules of G rows, granule g hashes to a uint32,
 // thresholds cut the uint32 range into k classes.  The one-pass kernel fixes G = 64 = one
-// superstep of the tall f64 kernel (gram.hip, gram_tall_f64_kernel), so a superstep's fold is
-// wave-uniform: a wave keeps its contiguous superstep range and ONE accumulator set, and sweeps
-// the range once per fold, loading only that fold's supersteps.  Every row is read once; MFMA
-// work, VGPRs and LDS are those of the plain kernel; the extras are the hash (scalar values) and
-// k block reductions + slab stores per block.  Slabs: partials[fold][block][P] in the plain
-// kernel's layout, so gram_reduce folds each fold's slabs unchanged, in fixed order (no atomics:
-// bit-identical run to run).
+// superstep of the staged f64 loop (gram_slab.h section 5; this kernel and glm_irls.hip's keep
+// it), so a superstep's fold is wave-uniform: a wave keeps its contiguous superstep range and ONE
+// accumulator set, and sweeps the range once per fold, loading only that fold's supersteps.
+// Every row is read once; MFMA work, VGPRs and LDS are those of one plain pass of that loop; the
+// extras are the hash (scalar values) and k block reductions + slab stores per block.  Slabs:
+// partials[fold][block][P] in the f64 slab layout (gram_slab.h), so gram_reduce folds each fold's
+// slabs unchanged, in fixed order (no atomics: bit-identical run to run).
 #include "gram_folds.h"
 
 #include "common.h"
@@ -192,12 +192,6 @@ __global__ __launch_bounds__(256) void fold_ids_kernel(int64_t n, int64_t granul
     out[r] = (uint8_t)fold_of(fr, (uint64_t)(r / granule));
 }
 
-size_t folds_lds(int d) {
-  const size_t lds = kTallF64LoopBytes;
-  const size_t red = (size_t)gram_partial_stride(GRAM_F64, d) * sizeof(double);
-  return red > lds ? red : lds;
-}
-
 template <typename F>
 void with_folds_kernel(int xdt, int d, F&& f) {
   const int NT = (d + 15) / 16;
@@ -224,35 +218,16 @@ void check_rule(const FoldRule& fr) {
 
 int gram_folds_blocks(int d, int64_t n, int xdt) {
   if (d < 1 || d > 64) throw std::invalid_argument("gram_folds: d must be in [1, 64]");
-  int per = 0, dev = 0, cus = 0;
-  with_folds_kernel(xdt, d, [&](auto kern) {
-    DQ_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kern, kBlock, folds_lds(d)));
-  });
-  DQ_HIP_CHECK(hipGetDevice(&dev));
-  DQ_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  const int64_t full = (int64_t)(per < 1 ? 1 : per) * cus;
-  const int64_t ngran = (n + 63) / 64;
-  int64_t want = (ngran + 4 * kWavesPerBlock - 1) / (4 * kWavesPerBlock);
-  if (want < 1) want = 1;
-  return (int)(want < full ? want : full);
+  int nb = 1;
+  with_folds_kernel(xdt, d, [&](auto kern) { nb = staged_f64_blocks(kern, staged_f64_lds(d), n); });
+  return nb;
 }
 
 void gram_folds(GramArgs a, const FoldRule& fr, int blocks, double* out, hipStream_t st) {
-  if (a.d < 1 || a.d > 64) throw std::invalid_argument("gram_folds: d must be in [1, 64]");
-  if (blocks < 1) throw std::invalid_argument("gram_folds: blocks must be >= 1");
-  if (a.n < 1) throw std::invalid_argument("gram_folds: n must be >= 1");
+  staged_f64_plan(a, blocks, "gram_folds");  // (granules = supersteps: a.nsuper, a.spw)
   if (a.w != nullptr) throw std::invalid_argument("gram_folds: instance weights are not supported");
-  if (a.ydt != DT_F64 && a.ydt != DT_F32) throw std::invalid_argument("gram_folds: label must be f32 or f64");
-  const int64_t esz = a.xdt == DT_F64 ? 8 : 4;
-  if ((reinterpret_cast<uintptr_t>(a.X) & 15) || (a.d > 1 && (a.ld * esz) % 16) || a.ld < a.n)
-    throw std::invalid_argument("gram_folds: feature rows must be 16-byte aligned and ld >= n");
   check_rule(fr);
-  a.nsuper = (a.n + 63) / 64;
-  const int64_t total_waves = (int64_t)blocks * kWavesPerBlock;
-  a.spw = (a.nsuper + total_waves - 1) / total_waves;
-  if (a.spw < 1) a.spw = 1;
-  a.P = (int)gram_partial_stride(GRAM_F64, a.d);
-  const size_t lds = folds_lds(a.d);
+  const size_t lds = staged_f64_lds(a.d);
   with_folds_kernel(a.xdt, a.d,
                     [&](auto kern) { hipLaunchKernelGGL(kern, dim3(blocks), dim3(kBlock), lds, st, a, fr); });
   DQ_HIP_CHECK(hipGetLastError());

@@ -7,16 +7,16 @@
 // T = 16 for the f64 MFMA kernels (v_mfma_f64_16x16x4_f64) and 32 for the f32-accumulator kernels
 // (v_mfma_f32_32x32x*); the pairs are stored row-major over I <= J < NT = ceil(d / T), each tile
 // row-major, lower halves of the diagonal tiles and padding features included (the fold drops them).
-// Writers: gram_tall_bf16_kernel, gram_cols_kernel, gram_tall_f64_kernel, gram_skinny_f64_kernel
-// (gram.hip), gram_folds_f64_kernel (gram_folds.hip) and the stream kernels' two bodies
-// (gram_stream.hip).  Reader: fold_store (gram.hip).
+// Writers: gram_tall_bf16_kernel, gram_cols_kernel, gram_skinny_f64_kernel (gram.hip),
+// gram_folds_f64_kernel (gram_folds.hip), glm_irls_f64_kernel (glm_irls.hip) and the stream
+// kernels' two bodies (gram_stream.hip).  Reader: fold_store (gram.hip).
 //
 // What is NOT here: the serial f64 reduction over the waves (zero an LDS slab, waves 0..NW-1 add
-// in order between barriers, copy out) stays written out in its four kernels, and the tall bf16
-// and tall f64 kernels keep SlabTree32::reduce_and_store / load_superstep_f64 in line.  A call,
-// even force-inlined around the verbatim text, lets the compiler order its passes differently, and
-// those kernels' main loops then get other VGPR / AGPR / spill counts.  They still take every
-// offset from the functions below.
+// in order between barriers, copy out) stays written out in its four kernels (the folds and GLM
+// kernels and the stream kernels' two bodies), and the tall bf16 kernel keeps
+// SlabTree32::reduce_and_store in line.  A call, even force-inlined around the verbatim text, lets
+// the compiler order its passes differently, and those kernels' main loops then get other VGPR /
+// AGPR / spill counts.  They still take every offset from the functions below.
 #pragma once
 #ifndef __HIPCC_RTC__  // (ops/streamfuse.py compiles the device part below with hipRTC too)
 #include <hip/hip_runtime.h>
@@ -25,6 +25,7 @@
 #include <cstdint>
 
 #include "common.h"
+#include "gram.h"
 #endif
 
 namespace dq4ml {
@@ -181,12 +182,49 @@ struct SlabTree32 {
   }
 };
 
-// ---- 5. the tall f64 kernels' staging (gram_tall_f64_kernel, gram_folds_f64_kernel) ----------
+// ---- 5. the staged f64 passes (gram_folds_f64_kernel, glm_irls_f64_kernel): staging + launch plan
+// A wave keeps one contiguous range of 64-row supersteps and stages every 16-feature tile of a
+// superstep in LDS before the f64 MFMAs.  (The plain f64 statistics took this loop too, in
+// gram_tall_f64_kernel, until the stream kernel served every call; the constants keep its name.)
 constexpr int kBlock = 256;  // 4 waves
 constexpr int kWavesPerBlock = kBlock / kWave;
 constexpr int kStageLd = 66;  // f64 staging row stride (doubles): 2-double pad spreads the banks
 // LDS of the loop: per wave 128 row scalars + one staged 16-feature x 64-row tile
 constexpr size_t kTallF64LoopBytes = kWavesPerBlock * (128 + 16 * kStageLd) * sizeof(double);
+
+#ifndef __HIPCC_RTC__
+// dynamic LDS of a block: the loop's bytes (+ `extra` that the kernel keeps beside them), reused
+// for the block reduction's slab
+inline size_t staged_f64_lds(int d, size_t extra = 0) {
+  const size_t loop = kTallF64LoopBytes + extra, red = (size_t)slab_stride<16>(d) * sizeof(double);
+  return red > loop ? red : loop;
+}
+
+// grid: a full residency wave of `kern` at that LDS, at least ~4 supersteps per wave
+template <typename K>
+inline int staged_f64_blocks(K kern, size_t lds, int64_t n) {
+  const int64_t nsuper = (n + 63) / 64;
+  return occupancy_grid(kern, kBlock, lds, (nsuper + 4 * kWavesPerBlock - 1) / (4 * kWavesPerBlock));
+}
+
+// The refusals that the passes share (`who` heads the message), then the fields the kernels plan
+// by: nsuper = ceil(n / 64) (the ragged superstep included), spw = supersteps per wave, P.
+inline void staged_f64_plan(GramArgs& a, int blocks, const char* who) {
+  auto bad = [who](const char* what) { throw std::invalid_argument(std::string(who) + ": " + what); };
+  if (a.d < 1 || a.d > 64) bad("d must be in [1, 64]");
+  if (blocks < 1) bad("blocks must be >= 1");
+  if (a.n < 1) bad("n must be >= 1");
+  if (a.ydt != DT_F64 && a.ydt != DT_F32) bad("label must be f32 or f64");
+  const int64_t esz = a.xdt == DT_F64 ? 8 : 4;
+  if ((reinterpret_cast<uintptr_t>(a.X) & 15) || (a.d > 1 && (a.ld * esz) % 16) || a.ld < a.n)
+    bad("feature rows must be 16-byte aligned and ld >= n");
+  a.nsuper = (a.n + 63) / 64;
+  const int64_t total_waves = (int64_t)blocks * kWavesPerBlock;
+  a.spw = (a.nsuper + total_waves - 1) / total_waves;
+  if (a.spw < 1) a.spw = 1;
+  a.P = (int)slab_stride<16>(a.d);
+}
+#endif
 
 // Cooperative load of features [f0, f0 + 16) x rows [r0, r0 + 64) of a feature-major matrix into a
 // per-wave LDS tile xs[f][row] (f64), zeros for features >= d.  Chunk c = i * 64 + lane.

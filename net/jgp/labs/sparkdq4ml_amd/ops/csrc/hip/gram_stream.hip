@@ -749,20 +749,15 @@ bool gram_stream_ok(int mode, const GramArgs& a) {
 }
 
 int gram_stream_blocks(int mode, int d, int64_t n, int xdt) {
-  int full = 1;
+  int nb = 1;
+  const int64_t nstage = n / stream_rs(mode, xdt, d);
+  const int64_t want = (nstage + 4 * kSW - 1) / (4 * kSW);  // >= 4 stages per wave
   with_stream_kernel(mode, xdt, d, 0, [&](auto kern, int wave_bytes) {
-    int per = 0, dev = 0, cus = 0;
     DQ_HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)stream_lds(wave_bytes, mode, d)));
-    DQ_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kern, kSB, stream_lds(wave_bytes, mode, d)));
-    DQ_HIP_CHECK(hipGetDevice(&dev));
-    DQ_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    full = (per < 1 ? 1 : per) * cus;
+    nb = occupancy_grid(kern, kSB, stream_lds(wave_bytes, mode, d), want);
   });
-  const int64_t nstage = n / stream_rs(mode, xdt, d);
-  int64_t want = (nstage + 4 * kSW - 1) / (4 * kSW);  // >= 4 stages per wave
-  if (want < 1) want = 1;
-  return (int)(want < full ? want : full);
+  return nb;
 }
 
 void gram_stream(int mode, GramArgs a, int xmode, int blocks, double* out, hipStream_t st, bool reduce) {

@@ -32,7 +32,6 @@ struct WideArgs {
 constexpr int kWideZeroBytes = 32768;  // >= the largest panel-relative piece offset (bf16 tiles: 30 KiB)
 
 int64_t wide_tiled_bytes(int eb, int d, int64_t n);
-int64_t gram_wide_partials(int d, int splitk);
 // shift (null: none): per-feature f32 shift s; the amax is that of x - s and the pack stores
 // (x - s) [* inv_scale] (the Gram statistics are un-shifted in f64 afterwards: gram.h stats_unshift)
 void feature_amax(const PackSrcW* srcs_dev, int d, int64_t n, const uint8_t* sel, float* amax, hipStream_t st,

@@ -900,12 +900,6 @@ void wide_label_aug(int eb, const void* y, int ydt, int64_t n, const uint8_t* se
   DQ_HIP_CHECK(hipGetLastError());
 }
 
-int64_t gram_wide_partials(int d, int splitk) {
-  const int P = (d + kPanel - 1) / kPanel;
-  const int npair = (P + 1) * (P + 2) / 2;
-  return (int64_t)npair * splitk * kPanel * kPanel;
-}
-
 template <int EB, int RING>
 static void launch_wide(const WideArgs& a, int nblocks, hipStream_t st) {
   const size_t lds = (size_t)RING * kStageBytes;

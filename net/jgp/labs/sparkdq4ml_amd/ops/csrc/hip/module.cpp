@@ -533,7 +533,6 @@ PYBIND11_MODULE(_dq4ml_hip, m) {
   m.attr("WLS_SMALL_MAX_FEATURES") = kWlsSmallMaxFeatures;
   m.def("wide_tiled_bytes", &wide_tiled_bytes);
   m.attr("WIDE_ZERO_BYTES") = kWideZeroBytes;
-  m.def("gram_wide_partials", &gram_wide_partials);
   m.def("pack_wide", [](int eb, uintptr_t srcs_dev, int d, int64_t n, int nt, uintptr_t sel, uintptr_t inv_scale,
                         uintptr_t out, uintptr_t stream, uintptr_t shift) {
     pack_wide(eb, P<const PackSrcW>(srcs_dev), d, n, nt, P<const uint8_t>(sel), P<const float>(inv_scale), P<void>(out),
@@ -804,8 +803,5 @@ PYBIND11_MODULE(_dq4ml_hip, m) {
     if (bi.itemsize != 8 || bi.ndim != 1 || (bi.ndim == 1 && bi.strides[0] != 8))
       throw std::invalid_argument("rtc_launch_args: ptrs must be a contiguous 1-d int64 array");
     rtc_launch_args(handle, grid, block, static_cast<const int64_t*>(bi.ptr), (int)bi.size, n, as_stream(stream));
-  });
-  m.def("rtc_launch", [](int64_t handle, int grid, int block, uintptr_t ptrs_dev, int64_t n, uintptr_t stream) {
-    rtc_launch(handle, grid, block, P<void* const>(ptrs_dev), n, as_stream(stream));
   });
 }

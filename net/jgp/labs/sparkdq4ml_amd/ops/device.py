@@ -57,18 +57,29 @@ def _cus(h) -> int:
     return c
 
 
-def _plan_blocks(h, mode, d, n, xdt, xmode):
-    reserve = gram_reserve()
-    key = (torch.cuda.current_device(), mode, d, n, xdt, xmode, reserve)
+def _grid(blocks: Optional[int], key, plan) -> int:
+    """The caller's ``blocks``, else the planned grid: ``plan()`` once per ``key`` (the current
+    device is part of every key), then from the cache."""
+    if blocks:
+        return int(blocks)
+    key = (torch.cuda.current_device(),) + key
     nb = _plan_cache.get(key)
     if nb is None:
+        nb = _plan_cache[key] = int(plan())
+    return nb
+
+
+def _plan_blocks(h, mode, d, n, xdt, xmode, blocks: Optional[int] = None) -> int:
+    reserve = gram_reserve()
+
+    def plan():
         nb = int(h.gram_plan_blocks(mode, int(d), int(n), xdt, xmode))
         cus = _cus(h)
         if reserve > 0 and nb >= cus:  # a full residency wave of blocks: give `reserve` CUs back
-            per = nb // cus
-            nb = max(1, nb - reserve * per)
-        _plan_cache[key] = nb
-    return nb
+            nb = max(1, nb - reserve * (nb // cus))
+        return nb
+
+    return _grid(blocks, (mode, d, n, xdt, xmode, reserve), plan)
 
 
 def _h2d(arr: np.ndarray, dev) -> torch.Tensor:
@@ -346,7 +357,7 @@ def gram_stats(X, y, w, sel, compute: str = "fp64", x_zero_dead: bool = False, b
     xmode = _xmode(w, sel, x_zero_dead)
     if shift is not None:
         xmode = max(xmode, 1)  # dead / padding rows must weigh 0: their stored zeros are -s after the shift
-    nb = int(blocks or _plan_blocks(h, mode, d, n, dtype_code(Xv), xmode))
+    nb = _plan_blocks(h, mode, d, n, dtype_code(Xv), xmode, blocks)
     P = int(h.gram_partial_stride(mode, d))
     partials = torch.empty(nb * P, dtype=torch.float64, device=X.device)
     h.gram_tall(mode, Xv.data_ptr(), int(ld), int(d), int(n), dtype_code(Xv), 0, _sptr(shift), 0, 0, 0, 0,
@@ -379,6 +390,20 @@ def onepass_ok(X, granule: int, compute: str) -> bool:
             and X.dtype in (torch.float32, torch.float64) and ONEPASS_MIN_D <= X.shape[0] <= ONEPASS_MAX_D)
 
 
+def _staged_features(X, rows, who: str, needs: str, ok: bool = True):
+    """The feature operand of a staged f64 pass (gram_folds.hip, glm_irls.hip): a dense f32 / f64
+    ``[d, n]`` matrix with 1 <= d <= 64 and n >= 1, on the device of the row operands ``rows``.
+    ``ok``: the caller's own conditions, refused with the same ``needs`` message.  Returns the
+    16-byte-aligned view, its ``ld`` and its dtype code."""
+    if not (torch.is_tensor(X) and X.dim() == 2 and X.dtype in (torch.float32, torch.float64)):
+        raise ValueError(f"{who}: dense f32 / f64 feature-major features only")
+    _check_dev(X, *rows)
+    if not (ok and 1 <= X.shape[0] <= 64 and X.shape[1] >= 1):
+        raise ValueError(f"{who}: needs {needs}")
+    Xv, ld = _feature_view(X, 16 // X.element_size())
+    return Xv, ld, dtype_code(Xv)
+
+
 def gram_stats_folds(X, y, sel, k_or_weights, seed: int, granule: int, compute: str = "fp64", route: str = "auto",
                      blocks: Optional[int] = None) -> torch.Tensor:
     """Per-fold WLS statistics ``[k, P]`` (unit weights).  ``route``: "auto" (one-pass where
@@ -404,33 +429,18 @@ def gram_stats_folds(X, y, sel, k_or_weights, seed: int, granule: int, compute: 
             outs.append(gram_stats(X, y, None, m, compute))
         return torch.stack(outs)
     h = native.hip()
-    if not (torch.is_tensor(X) and X.dim() == 2 and X.dtype in (torch.float32, torch.float64)):
-        raise ValueError("gram_stats_folds(onepass): dense f32 / f64 feature-major features only")
-    _check_dev(X, y, sel)
+    Xv, ld, xdt = _staged_features(X, (y, sel), "gram_stats_folds(onepass)",
+                                   "granule 64, fp64 statistics, 1 <= d <= 64, n >= 1",
+                                   int(granule) == FOLD_GRANULE and compute == "fp64")
     d = int(X.shape[0])
     if int(X.shape[1]) != n or (sel is not None and sel.numel() != n):
         raise ValueError("gram_stats_folds: row-count mismatch")
-    if int(granule) != FOLD_GRANULE or compute != "fp64" or not 1 <= d <= 64 or n < 1:
-        raise ValueError("gram_stats_folds(onepass): needs granule 64, fp64 statistics, 1 <= d <= 64, n >= 1")
-    Xv, ld = _feature_view(X, 16 // X.element_size())
-    y = y.contiguous()
-    if y.dtype not in (torch.float64, torch.float32):
-        y = y.to(torch.float64)
-    if sel is not None:
-        sel = sel.contiguous()
-        if sel.dtype != torch.bool:
-            sel = sel.to(torch.bool)
-    nb = blocks
-    if not nb:
-        key = (torch.cuda.current_device(), "folds", d, n, dtype_code(Xv))
-        nb = _plan_cache.get(key)
-        if nb is None:
-            nb = _plan_cache[key] = int(h.gram_folds_blocks(d, n, dtype_code(Xv)))
-    nb = int(nb)
+    y, _, sel = _prep_rows(y, None, sel, n)
+    nb = _grid(blocks, ("folds", d, n, xdt), lambda: h.gram_folds_blocks(d, n, xdt))
     P = int(h.gram_partial_stride(0, d))
     partials = torch.empty(k * nb * P, dtype=torch.float64, device=X.device)
     out = torch.empty(k, gram_layout_size(d), dtype=torch.float64, device=X.device)
-    h.gram_folds(Xv.data_ptr(), int(ld), d, n, dtype_code(Xv), y.data_ptr(), dtype_code(y), _ptr(sel),
+    h.gram_folds(Xv.data_ptr(), int(ld), d, n, xdt, y.data_ptr(), dtype_code(y), _ptr(sel),
                  [int(t) for t in thr], int(seed64), partials.data_ptr(), nb, out.data_ptr(), _stream())
     return out
 
@@ -445,24 +455,13 @@ class _GlmPlan:
         from . import glm
 
         self.h = native.hip()
-        if not (torch.is_tensor(X) and X.dim() == 2 and X.dtype in (torch.float32, torch.float64)):
-            raise ValueError("glm_pass: dense f32 / f64 feature-major features only")
-        _check_dev(X, y, w, sel)
+        self.Xv, self.ld, self.xdt = _staged_features(X, (y, w, sel), "glm_pass", "1 <= d <= 64 and n >= 1")
         self.d, self.n = int(X.shape[0]), int(X.shape[1])
-        if not 1 <= self.d <= 64 or self.n < 1:
-            raise ValueError("glm_pass: needs 1 <= d <= 64 and n >= 1")
         link = glm.resolve_link(family, link)
         self.family, self.link = glm.FAMILIES[family], glm.LINKS[link]
-        self.Xv, self.ld = _feature_view(X, 16 // X.element_size())
         self.y, self.w, self.sel = _prep_rows(y, w, sel, self.n)
-        self.xdt = dtype_code(self.Xv)
-        nb = blocks
-        if not nb:
-            key = (torch.cuda.current_device(), "glm", self.d, self.n, self.xdt)
-            nb = _plan_cache.get(key)
-            if nb is None:
-                nb = _plan_cache[key] = int(self.h.glm_irls_blocks(self.d, self.n, self.xdt))
-        self.nb = int(nb)
+        self.nb = _grid(blocks, ("glm", self.d, self.n, self.xdt),
+                        lambda: self.h.glm_irls_blocks(self.d, self.n, self.xdt))
         if self.nb < 1:
             raise ValueError("glm_pass: blocks must be >= 1")
         self.P = int(self.h.gram_partial_stride(0, self.d))
@@ -1062,7 +1061,7 @@ def gram_skinny_cols(parts: List[torch.Tensor], y, w, sel, blocks: Optional[int]
     if n == 0:
         out.zero_()
         return out
-    nb = int(blocks or _plan_blocks(h, 0, d, n, 0, _xmode(w, sel)))
+    nb = _plan_blocks(h, 0, d, n, 0, _xmode(w, sel), blocks)
     P = int(h.gram_partial_stride(0, d))
     partials = torch.empty(nb * P, dtype=torch.float64, device=dev)
     h.gram_skinny_cols([r.data_ptr() for r in rows], [dtype_code(r) for r in rows], int(n), y.data_ptr(),
@@ -1092,7 +1091,7 @@ def gram_cols(parts: List[torch.Tensor], y, sel, blocks: Optional[int] = None):
         sel = _ones_sel(n, dev)
     shift = column_shift(rows)
     desc = _srcw_desc(h, rows, dev)
-    nb = int(blocks or _cols_blocks(h, d, n))
+    nb = _cols_blocks(h, d, n, blocks)
     P = int(h.gram_partial_stride(2, d))
     partials = torch.empty(nb * P, dtype=torch.float64, device=dev)
     out = torch.empty(gram_layout_size(d), dtype=torch.float64, device=dev)
@@ -1105,7 +1104,6 @@ def gram_cols(parts: List[torch.Tensor], y, sel, blocks: Optional[int] = None):
     return _unshift(h, out, shift, d)
 
 
-_cols_plan = {}
 _ones = {}
 
 
@@ -1138,10 +1136,7 @@ def gram_stream_cols(parts, y, w, sel, compute: str):
         return out.zero_()
     desc = _srcw_desc(h, rows, dev)
     xc = dtype_code(rows[0])
-    key = ("stream", torch.cuda.current_device(), mode, d, n, xc)
-    nb = _cols_plan.get(key)
-    if nb is None:
-        nb = _cols_plan[key] = int(h.gram_stream_blocks(mode, d, n, xc))
+    nb = _grid(None, ("stream", mode, d, n, xc), lambda: h.gram_stream_blocks(mode, d, n, xc))
     P = int(h.gram_partial_stride(mode, d))
     partials = torch.empty(nb * P, dtype=torch.float64, device=dev)
     shift = column_shift(rows) if mode in (1, 2, 4) else None  # rounded / f32-accumulated modes
@@ -1157,12 +1152,8 @@ def _ones_sel(n, dev):
     return t[:n]
 
 
-def _cols_blocks(h, d, n):
-    key = (torch.cuda.current_device(), d, n)
-    nb = _cols_plan.get(key)
-    if nb is None:
-        nb = _cols_plan[key] = int(h.gram_cols_blocks(int(d), int(n)))
-    return nb
+def _cols_blocks(h, d, n, blocks: Optional[int] = None) -> int:
+    return _grid(blocks, ("cols", d, n), lambda: h.gram_cols_blocks(int(d), int(n)))
 
 
 def _prep_rows(y, w, sel, n):
@@ -1214,7 +1205,7 @@ class TiledGramPlan:
         y, w, sel = _prep_rows(y, w, sel, n)
         xmode = _xmode(w, sel, x_zero_dead)
         self.h, self.T, self.y, self.w, self.sel, self.d, self.dev = h, T, y, w, sel, d, T.device
-        self.nb = int(blocks or _plan_blocks(h, 2, d, n, 2, xmode))
+        self.nb = _plan_blocks(h, 2, d, n, 2, xmode, blocks)
         self.flat_len = gram_layout_size(d)
         self.part_len = self.nb * int(h.gram_partial_stride(2, d))
         # kind: the companion this launch reads ("patched", "mixed" or None); packed: T has one

@@ -101,7 +101,8 @@ def _tall_path(args):
         return "skinny", "fp64", DT_NAME[xdt]
     if (mode in (0, 1, 4) or (mode == 2 and xdt == 1)) and stream_ok:
         return "stream", MODE_NAME[mode], DT_NAME[xdt]
-    assert mode == 2, "the f32 modes have no other kernel"
+    assert mode == 2, "the fp64 and f32 modes have no other kernel: the f64 fallback is gone, gram_tall refuses"
+    assert xdt != 1, "bf16 mode on f32 storage has no kernel but the stream kernel: gram_tall refuses"
     comp = "patched" if xrec else ("mixed" if xdir else None)
     assert (xpack != 0) == (comp is not None)
     return "tall_bf16", ("tiled" if tiled else DT_NAME[xdt]), comp, xmode

@@ -168,3 +168,58 @@ def test_gram_tall_rejects_bad_companions():
     for Tc in (Tm, Tp):
         launch(_args(Tc, y))
         assert torch.equal(out, device.gram_stats(Tc, y, None, None, "bf16", blocks=1))
+
+
+def _dense_args(mode, feats, n, label, select, **over):
+    """``gram_tall``'s positional arguments for a dense feature-major ``feats[:, :n]`` (row stride:
+    the buffer's) with a selection; ``over`` replaces single ones."""
+    device = _device()
+    a = dict(mode=mode, X=feats.data_ptr(), ld=feats.stride(0), d=feats.shape[0], n=n, xdt=device.dtype_code(feats),
+             tiled=0, xshift=0, xpack=0, xdir=0, xrec=0, xovf=0, y=label.data_ptr(), ydt=device.dtype_code(label), w=0,
+             wdt=0, sel=select.data_ptr(), xmode=1)
+    assert set(over) <= set(a)
+    a.update(over)
+    return tuple(a.values())
+
+
+def test_gram_tall_rejects_unstreamable_dense_operands():
+    """fp64 mode above the skinny kernel's d and bf16 mode on f32 storage have one kernel, the
+    stream kernel: operands that it cannot take (16-byte alignment, f32 / f64 dtypes) are refused
+    on the host before a launch, where a fallback kernel used to take them.  Every buffer is longer
+    than the rows used (labels and selection by two elements, each feature row by four, which
+    keeps f32 and f64 rows 16-byte aligned), so an accepted call would still read in bounds.  The
+    last lines run the same argument builder unchanged with the aligned operands."""
+    from net.jgp.labs.sparkdq4ml_amd.ops import native
+
+    device, h = _device(), native.hip()
+    n = 128
+    g = torch.Generator(device="cuda").manual_seed(7)
+    sel = torch.arange(n + 2, device="cuda") % 3 != 0
+    st = torch.cuda.current_stream().cuda_stream
+    ops = {}
+    for name, mode, d, xdt, ydt in (("fp64", 0, 16, torch.float64, torch.float64), ("bf16", 2, 32, torch.float32, torch.float32)):
+        X = torch.randn(d, n + 4, device="cuda", generator=g).to(xdt)
+        y = torch.randn(n + 2, device="cuda", generator=g).to(ydt)
+        ops[name] = (mode, X, y)
+    (m64, X64, y64), (m16, X32, y32) = ops["fp64"], ops["bf16"]
+    bad = {
+        "fp64, label not 16-byte aligned": (X64, _dense_args(m64, X64, n, y64, sel, y=y64.data_ptr() + 8)),
+        "fp64, feature rows not 16-byte aligned": (X64, _dense_args(m64, X64, n, y64, sel, ld=n + 1)),
+        "fp64, selection not word aligned": (X64, _dense_args(m64, X64, n, y64, sel, sel=sel.data_ptr() + 1)),
+        "bf16 on f32 storage, label not 16-byte aligned": (X32, _dense_args(m16, X32, n, y32, sel, y=y32.data_ptr() + 4)),
+    }
+
+    def launch(X, args):
+        mode, d = args[0], X.shape[0]
+        partials = torch.empty(int(h.gram_partial_stride(mode, d)), dtype=torch.float64, device="cuda")
+        out = torch.empty(device.gram_layout_size(d), dtype=torch.float64, device="cuda")
+        h.gram_tall(*args, partials.data_ptr(), 1, out.data_ptr(), st, True)
+        return out
+
+    for what, (X, args) in bad.items():
+        with pytest.raises(ValueError):
+            launch(X, args)
+            pytest.fail(f"gram_tall accepted: {what}")
+    for name, (mode, X, y) in ops.items():
+        out = launch(X, _dense_args(mode, X, n, y, sel))
+        assert torch.equal(out, device.gram_stats(X[:, :n], y[:n], None, sel[:n], name, blocks=1))
