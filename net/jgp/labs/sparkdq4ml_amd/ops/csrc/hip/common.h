@@ -63,6 +63,22 @@ enum DType : int { DT_F64 = 0, DT_F32 = 1, DT_BF16 = 2, DT_I32 = 3, DT_I64 = 4, 
 
 __device__ __forceinline__ float bf16_bits_to_f32(uint16_t b) { return __uint_as_float(uint32_t(b) << 16); }
 
+// eight bf16 in 16 bytes (element 0 in the low half of dword 0) -> f32
+__device__ __forceinline__ void bf16x8_to_f32(const u32x4 v, float x[8]) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    x[2 * j] = __uint_as_float(v[j] << 16);
+    x[2 * j + 1] = __uint_as_float(v[j] & 0xffff0000u);
+  }
+}
+
+// one source column of a packer (VectorAssembler input): device pointer + dtype code
+struct PackSrc {
+  const void* ptr;
+  int dt;
+  int pad;
+};
+
 // Generic pointers that reach a kernel through a descriptor table compile to FLAT loads, which
 // count on lgkmcnt too — every LDS wait/barrier would then drain the prefetch.  All descriptor
 // pointers point at device global memory: load through the global address space.
@@ -92,12 +108,7 @@ __device__ __forceinline__ void load8_f32(const void* p, int dt, int64_t r0, int
     return;
   }
   if (full && dt == DT_BF16) {
-    const u32x4 v = *gptr<u32x4>(reinterpret_cast<const uint16_t*>(p) + r0);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      x[2 * j] = __uint_as_float(v[j] << 16);
-      x[2 * j + 1] = __uint_as_float(v[j] & 0xffff0000u);
-    }
+    bf16x8_to_f32(*gptr<u32x4>(reinterpret_cast<const uint16_t*>(p) + r0), x);
     return;
   }
 #pragma unroll
@@ -137,12 +148,7 @@ __device__ __forceinline__ void load8_typed(const void* p, int64_t r0, int64_t n
         x[j] = (float)v[0], x[j + 1] = (float)v[1];
       }
     } else {
-      const u32x4 v = *gptr<u32x4>(reinterpret_cast<const uint16_t*>(p) + r0);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        x[2 * j] = __uint_as_float(v[j] << 16);
-        x[2 * j + 1] = __uint_as_float(v[j] & 0xffff0000u);
-      }
+      bf16x8_to_f32(*gptr<u32x4>(reinterpret_cast<const uint16_t*>(p) + r0), x);
     }
     return;
   }

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+
+#include "common.h"  // PackSrc
 #endif
 
 namespace dq4ml {
@@ -142,14 +144,9 @@ void gram_stream(int mode, GramArgs a, int xmode, int blocks, double* out, hipSt
 // a.srcs set the features are d separate f32 columns (fused VectorAssembler + Gram)
 
 // fused VectorAssembler + bf16 Gram over d <= 64 source columns (a.X unused; a.sel masks rows)
-struct PackSrcG {
-  const void* ptr;
-  int dt;
-  int pad;
-};
 int gram_cols_blocks(int d, int64_t n);
 // sdt: the common source dtype (DT_F32 / DT_F64 / DT_BF16, 16-byte aligned columns) or -1 (mixed)
-void gram_cols(GramArgs a, const PackSrcG* srcs_dev, int sdt, int blocks, double* out, hipStream_t st);
+void gram_cols(GramArgs a, const PackSrc* srcs_dev, int sdt, int blocks, double* out, hipStream_t st);
 
 // a stream kernel compiled by hipRTC with a DQ row predicate (ops/streamfuse.py): the same
 // argument setup as gram_stream (mode GRAM_F32 / GRAM_BF16, binary row mask), launched through

@@ -29,6 +29,7 @@
 #include "gram.h"
 #include "gram_slab.h"
 #include "scan.h"
+#include "tile_layout.h"
 
 namespace dq4ml {
 
@@ -652,7 +653,7 @@ gram_tall_bf16_kernel(GramArgs a) {
 // double-buffered LDS, one barrier per superstep.  Partials use the bf16 kernel's slab layout.
 // =============================================================================================
 template <int NT, int SDT, int YDT>  // SDT: common source dtype (-1 mixed); YDT: label dtype (F32/F64)
-__global__ __launch_bounds__(256, (NT == 1 ? 3 : 2)) void gram_cols_kernel(GramArgs a, const PackSrcG* __restrict__ srcs) {
+__global__ __launch_bounds__(256, (NT == 1 ? 3 : 2)) void gram_cols_kernel(GramArgs a, const PackSrc* __restrict__ srcs) {
   constexpr int NPAIR = NT * (NT + 1) / 2;
   constexpr int FR = NT * 4 * 64 * 16;   // fragment bytes per superstep
   constexpr int BUF = FR + 4 * 64 * 2;   // + W stripe [4 cols][64 rows] bf16
@@ -669,7 +670,7 @@ __global__ __launch_bounds__(256, (NT == 1 ? 3 : 2)) void gram_cols_kernel(GramA
   for (int t = 0; t < NT; ++t) accw[t] = f32x16{};
   RowAcc ra;
 
-  PackSrcG src[NT];
+  PackSrc src[NT];
   bool fv[NT];
   float sh[NT];  // the thread's feature shifts (GramArgs::xshift; 0 without one)
 #pragma unroll
@@ -1274,14 +1275,11 @@ void stats_unshift(double* flat, const float* shift, int d, hipStream_t st) {
   DQ_HIP_CHECK(hipGetLastError());
 }
 
-int64_t tiled_elems(int d, int64_t n) {
-  const int NT = (d + 31) / 32;
-  return ((n + 63) / 64) * NT * 4 * 64 * 8;
-}
+int64_t tiled_elems(int d, int64_t n) { return tile::bytes(tile::kTall, d, n) / 2; }
 
 void tile_bf16(const void* X, int xdt, int64_t ld, int d, int64_t n, void* out, hipStream_t st, const float* shift) {
-  const int NT = (d + 31) / 32;
-  const int64_t nsup = (n + 63) / 64;
+  const int NT = tile::tiles(tile::kTall, d);
+  const int64_t nsup = tile::supersteps(n);
   const int64_t nchunks = nsup * NT * 256;
   int64_t g = (nchunks + 255) / 256;
   if (g > 8192) g = 8192;
@@ -1300,7 +1298,7 @@ void tile_bf16(const void* X, int xdt, int64_t ld, int d, int64_t n, void* out, 
 void pack_tiles(const void* tiles, int d, int64_t n, uint8_t* dir, uint32_t* slots, uint32_t* npacked,
                 hipStream_t st) {
   if (d < 1 || d > 64) throw std::invalid_argument("pack_tiles: d must be in [1, 64]");
-  const int64_t nent = ((n + 63) / 64) * ((d + 31) / 32);
+  const int64_t nent = tile::supersteps(n) * tile::tiles(tile::kTall, d);
   if (nent < 1) return;
   int64_t g = (nent + 3) / 4;
   if (g > 16384) g = 16384;
@@ -1337,7 +1335,7 @@ int64_t gram_partial_stride(int mode, int d) {
 
 static size_t bf16_lds(int d) {
   const int W = kBf16Block / kWave;
-  const int NT = (d + 31) / 32;
+  const int NT = tile::tiles(tile::kTall, d);
   const size_t stripes = (size_t)W * (4 * 64 * 2 + 64 * 4);
   const size_t tree = NT == 1 ? SlabTree32<1, W>::kBytes : SlabTree32<2, W>::kBytes;
   return tree > stripes ? tree : stripes;
@@ -1348,7 +1346,7 @@ static size_t bf16_lds(int d) {
 template <typename F>
 static void with_kernel(int mode, int xdt, int d, int xmode, bool tiled, Companion comp, F&& f) {
   if (mode != GRAM_BF16) throw std::invalid_argument("gram_tall: no kernel for this mode and feature dtype");
-  const int NT = (d + 31) / 32;
+  const int NT = tile::tiles(tile::kTall, d);
   constexpr Companion kRaw = Companion::kRaw, kMixed = Companion::kMixed, kPatched = Companion::kPatched;
 #define DQ_BF16_CASE(TX, NTV, TL, CO)                                  \
   if (xmode == 0) return f(gram_tall_bf16_kernel<TX, NTV, 0, TL, CO>); \
@@ -1432,7 +1430,7 @@ int gram_plan_blocks(int mode, int d, int64_t n, int xdt, int xmode) {
     return nb;
   }
   // the bf16 kernel: at least ~4 supersteps per wave, at most one full residency wave of blocks
-  const int64_t nsuper = (n + 63) / 64;
+  const int64_t nsuper = tile::supersteps(n);
   constexpr int wpb = kBf16Block / kWave;
   with_kernel(mode, xdt, d, xmode, false, Companion::kRaw,
               [&](auto kern) { nb = occupancy_grid(kern, kBf16Block, bf16_lds(d), (nsuper + 4 * wpb - 1) / (4 * wpb)); });
@@ -1541,25 +1539,25 @@ static void with_cols_kernel(int NT, int sdt, int ydt, F&& f) {
 }
 
 int gram_cols_blocks(int d, int64_t n) {
-  const int NT = (d + 31) / 32;
+  const int NT = tile::tiles(tile::kTall, d);
   int nb = 1;
-  const int64_t nsup = (n + 63) / 64;
+  const int64_t nsup = tile::supersteps(n);
   // >= 4 supersteps per block
   with_cols_kernel(NT, DT_F32, DT_F64, [&](auto k) { nb = occupancy_grid(k, 256, cols_lds(NT), (nsup + 3) / 4); });
   return nb;
 }
 
-void gram_cols(GramArgs a, const PackSrcG* srcs_dev, int sdt, int blocks, double* out, hipStream_t st) {
+void gram_cols(GramArgs a, const PackSrc* srcs_dev, int sdt, int blocks, double* out, hipStream_t st) {
   if (a.sel == nullptr) throw std::invalid_argument("gram_cols: pass an all-ones selection when there is none");
   if (a.d < 1 || a.d > 64) throw std::invalid_argument("gram_cols: d must be in [1, 64]");
   if (a.w != nullptr) throw std::invalid_argument("gram_cols: instance weights need the materialized path");
   if (blocks < 1) throw std::invalid_argument("gram_cols: blocks must be >= 1");
-  const int64_t nsup = (a.n + 63) / 64;
+  const int64_t nsup = tile::supersteps(a.n);
   a.spw = (nsup + blocks - 1) / blocks;
   if (a.spw < 1) a.spw = 1;
   a.nsuper = nsup;
   a.P = (int)gram_partial_stride(GRAM_BF16, a.d);
-  const int NT = (a.d + 31) / 32;
+  const int NT = tile::tiles(tile::kTall, a.d);
   const size_t lds = cols_lds(NT);
   if (a.ydt != DT_F64 && a.ydt != DT_F32) throw std::invalid_argument("gram_cols: label must be f32 or f64");
   with_cols_kernel(NT, sdt, a.ydt,

@@ -80,12 +80,10 @@ __device__ __forceinline__ void load8(const void* p, int64_t r0, int64_t n, C v[
 #pragma unroll
       for (int j = 0; j < 4; ++j) v[j] = (C)a[j], v[4 + j] = (C)b[j];
     } else {  // bf16
-      const u32x4 q = *gptr<u32x4>(reinterpret_cast<const uint16_t*>(p) + r0);
+      float x[8];
+      bf16x8_to_f32(*gptr<u32x4>(reinterpret_cast<const uint16_t*>(p) + r0), x);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        v[2 * j] = (C)__uint_as_float(q[j] << 16);
-        v[2 * j + 1] = (C)__uint_as_float(q[j] & 0xffff0000u);
-      }
+      for (int j = 0; j < 8; ++j) v[j] = (C)x[j];
     }
     return;
   }

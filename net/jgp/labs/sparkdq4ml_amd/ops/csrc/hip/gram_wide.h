@@ -4,13 +4,9 @@
 
 #include <cstdint>
 
-namespace dq4ml {
+#include "common.h"  // PackSrc
 
-struct PackSrcW {
-  const void* ptr;
-  int dt;
-  int pad;
-};
+namespace dq4ml {
 
 struct WideArgs {
   const unsigned char* X;     // wide tiled storage, NT = npanels * 8 tiles
@@ -34,7 +30,7 @@ constexpr int kWideZeroBytes = 32768;  // >= the largest panel-relative piece of
 int64_t wide_tiled_bytes(int eb, int d, int64_t n);
 // shift (null: none): per-feature f32 shift s; the amax is that of x - s and the pack stores
 // (x - s) [* inv_scale] (the Gram statistics are un-shifted in f64 afterwards: gram.h stats_unshift)
-void feature_amax(const PackSrcW* srcs_dev, int d, int64_t n, const uint8_t* sel, float* amax, hipStream_t st,
+void feature_amax(const PackSrc* srcs_dev, int d, int64_t n, const uint8_t* sel, float* amax, hipStream_t st,
                   const float* shift = nullptr);
 // the label's augmentation panel [1, y_hi, y_lo] (1 tile, eb's layout) of rows with sel != 0
 // (null: all), split on the device: aux (f64[6]) = [1, s_h, s_l | t, 1/s_h, 1/s_l] -- aux[0:3] is
@@ -46,7 +42,7 @@ int wide_label_part_doubles();
 void wide_label_aug(int eb, const void* y, int ydt, int64_t n, const uint8_t* sel, double* part, double* aux,
                     void* out, hipStream_t st);
 // eb = 16 (bf16) or 8 (fp8 e4m3, values multiplied by inv_scale[f] before conversion)
-void pack_wide(int eb, const PackSrcW* srcs_dev, int d, int64_t n, int nt, const uint8_t* sel, const float* inv_scale,
+void pack_wide(int eb, const PackSrc* srcs_dev, int d, int64_t n, int nt, const uint8_t* sel, const float* inv_scale,
                void* out, hipStream_t st, const float* shift = nullptr);
 // zero the rows with sel[r] == 0 (and rows >= n) of a wide tiled matrix: in -> out (may alias)
 void wide_mask_rows(int eb, const void* in, void* out, int d, int64_t n, const uint8_t* sel, hipStream_t st);

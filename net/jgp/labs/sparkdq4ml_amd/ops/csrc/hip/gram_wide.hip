@@ -27,6 +27,7 @@
 
 #include "common.h"
 #include "gram_wide.h"
+#include "tile_layout.h"
 
 namespace dq4ml {
 
@@ -568,10 +569,10 @@ __global__ __launch_bounds__(256) void gram_wide_reduce_kernel(WideArgs a, const
 
 // ---- packing into the wide tiled layouts ----------------------------------------------------
 // per-feature amax (for fp8 scales): one block per feature
-__global__ __launch_bounds__(256) void amax_kernel(const PackSrcW* __restrict__ srcs, int64_t n,
+__global__ __launch_bounds__(256) void amax_kernel(const PackSrc* __restrict__ srcs, int64_t n,
                                                   const uint8_t* __restrict__ sel, float* __restrict__ amax,
                                                   const float* __restrict__ shift) {
-  const PackSrcW s = srcs[blockIdx.x];
+  const PackSrc s = srcs[blockIdx.x];
   const float sh = shift ? shift[blockIdx.x] : 0.0f;  // amax of the shifted column x - s
   float m = 0.0f;
   for (int64_t r = threadIdx.x; r < n; r += blockDim.x) {
@@ -596,16 +597,15 @@ __global__ __launch_bounds__(256) void amax_kernel(const PackSrcW* __restrict__ 
 // columns -> wide fragment-ordered tiles (EB = 16: bf16, EB = 8: fp8 with 1/scale pre-multiplied).
 // One block-iteration = one (superstep s, tile t) chunk: thread (f, q) vector-loads rows
 // [8q, 8q+8) of feature f (8 threads per feature: coalesced 256-B column runs); in the wide
-// layout that run is lane 32(q & 1) + f's fragment of k-step q >> 1 -> one 16-B (bf16) or 8-B
-// (fp8) store.
+// layouts that is run q of the chunk (tile_layout.h) -> one 16-B (bf16) or 8-B (fp8) store.
 template <int EB>
-__global__ __launch_bounds__(256) void pack_wide_kernel(const PackSrcW* __restrict__ srcs, int d, int64_t n, int NT,
+__global__ __launch_bounds__(256) void pack_wide_kernel(const PackSrc* __restrict__ srcs, int d, int64_t n, int NT,
                                                        int64_t nsup, const uint8_t* __restrict__ sel,
                                                        const float* __restrict__ inv_scale,
                                                        unsigned char* __restrict__ out,
                                                        const float* __restrict__ shift) {
+  constexpr int L = tile::wide_layout(EB);
   const int fl = threadIdx.x >> 3, q = threadIdx.x & 7;
-  const int ki = q >> 1, lane = 32 * (q & 1) + fl;
   const int64_t nchunks = nsup * NT;
   for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
     const int t = (int)(c % NT);
@@ -614,7 +614,7 @@ __global__ __launch_bounds__(256) void pack_wide_kernel(const PackSrcW* __restri
     const int64_t r0 = s * 64 + 8 * q;
     float x[8];
     if (f < d) {
-      const PackSrcW src = srcs[f];
+      const PackSrc src = srcs[f];
       load8_f32(src.ptr, src.dt, r0, n, x);
       if (shift) sub_shift8(x, shift[f], r0, n);
       mask8(sel, r0, n, x);
@@ -622,24 +622,12 @@ __global__ __launch_bounds__(256) void pack_wide_kernel(const PackSrcW* __restri
 #pragma unroll
       for (int j = 0; j < 8; ++j) x[j] = 0.0f;
     }
-    if constexpr (EB == 16) {
-      bf16x8 v;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = (__bf16)x[j];
-      reinterpret_cast<u32x4*>(out)[c * 256 + ki * 64 + lane] = __builtin_bit_cast(u32x4, v);
-    } else {  // saturate to the e4m3 range (the conversion maps overflow to NaN)
+    if constexpr (EB == 8) {  // saturate to the e4m3 range (the conversion maps overflow to NaN)
       const float is = f < d ? inv_scale[f] : 0.0f;
-      float qv[8];
 #pragma unroll
-      for (int j = 0; j < 8; ++j) qv[j] = fminf(fmaxf(x[j] * is, -448.0f), 448.0f);
-      int lo = __builtin_amdgcn_cvt_pk_fp8_f32(qv[0], qv[1], 0, false);
-      lo = __builtin_amdgcn_cvt_pk_fp8_f32(qv[2], qv[3], lo, true);
-      int hi = __builtin_amdgcn_cvt_pk_fp8_f32(qv[4], qv[5], 0, false);
-      hi = __builtin_amdgcn_cvt_pk_fp8_f32(qv[6], qv[7], hi, true);
-      // chunk (s, t) = [2 halves][64 lanes][16 B]; k-step ki -> half ki >> 1, byte 8 * (ki & 1)
-      const int64_t o = c * 2048 + (((ki >> 1) * 64 + lane) << 4) + ((ki & 1) << 3);
-      *reinterpret_cast<u32x2*>(out + o) = u32x2{(unsigned)lo, (unsigned)hi};
+      for (int j = 0; j < 8; ++j) x[j] = fminf(fmaxf(x[j] * is, -448.0f), 448.0f);
     }
+    tile::store_run<L>(out, c, q, fl, x);
   }
 }
 
@@ -729,7 +717,6 @@ __global__ __launch_bounds__(256) void wide_label_pack_kernel(const void* __rest
                                                               const double* __restrict__ aux,
                                                               unsigned char* __restrict__ out) {
   const int fl = threadIdx.x >> 3, q = threadIdx.x & 7;
-  const int ki = q >> 1, lane = 32 * (q & 1) + fl;
   const double t = aux[3], sh = aux[1], ish = aux[4], isl = aux[5];
   for (int64_t s = blockIdx.x; s < nsup; s += gridDim.x) {  // one 64-row superstep per iteration
     const int64_t r0 = s * 64 + 8 * q;
@@ -761,32 +748,20 @@ __global__ __launch_bounds__(256) void wide_label_pack_kernel(const void* __rest
       }
       x[j] = v;
     }
-    if constexpr (EB == 16) {
-      bf16x8 v;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = (__bf16)x[j];
-      reinterpret_cast<u32x4*>(out)[s * 256 + ki * 64 + lane] = __builtin_bit_cast(u32x4, v);
-    } else {
-      int lo = __builtin_amdgcn_cvt_pk_fp8_f32(x[0], x[1], 0, false);
-      lo = __builtin_amdgcn_cvt_pk_fp8_f32(x[2], x[3], lo, true);
-      int hi = __builtin_amdgcn_cvt_pk_fp8_f32(x[4], x[5], 0, false);
-      hi = __builtin_amdgcn_cvt_pk_fp8_f32(x[6], x[7], hi, true);
-      const int64_t o = s * 2048 + (((ki >> 1) * 64 + lane) << 4) + ((ki & 1) << 3);
-      *reinterpret_cast<u32x2*>(out + o) = u32x2{(unsigned)lo, (unsigned)hi};
-    }
+    tile::store_run<tile::wide_layout(EB)>(out, s, q, fl, x);  // NT = 1: chunk = superstep
   }
 }
 
 // Zero the dead rows of a wide fragment-ordered matrix (a DQ selection applied AFTER the pack):
 // one pass over the storage, 16 B per thread, no dequantize / re-pack.  In both layouts a 16-B
-// unit holds 8-row runs of ONE feature: bf16 = rows s*64 + 16ki + 8h + [0, 8) (unit = (s, t, ki,
-// lane)), fp8 = two runs 16 rows apart, k-steps 2kh and 2kh + 1 (unit = (s, t, kh, lane));
-// lane = 32h + feature % 32.
+// fragment (chunk, sub, lane = 32h + feature % 32) holds 8-row runs of ONE feature: one (bf16) or
+// two 16 rows apart (fp8); tile::frag_row names their rows.
 template <int EB>
 __global__ __launch_bounds__(256) void wide_mask_rows_kernel(const u32x4* __restrict__ in, u32x4* __restrict__ out,
                                                             int64_t units, int NT, int64_t n,
                                                             const uint8_t* __restrict__ sel) {
-  constexpr int kUnitsPerChunk = EB == 8 ? 128 : 256;
+  constexpr int L = tile::wide_layout(EB);
+  constexpr int kUnitsPerChunk = tile::chunk_bytes(L) / 16;
   auto run_mask = [&](int64_t r0) -> uint64_t {  // 0x01 per live row byte, rows past n dead
     if (r0 + 8 <= n) return *gptr<uint64_t>(sel + r0);
     uint64_t m = 0;
@@ -798,16 +773,14 @@ __global__ __launch_bounds__(256) void wide_mask_rows_kernel(const u32x4* __rest
     const int64_t c = u / kUnitsPerChunk;
     const int q = (int)(u - c * kUnitsPerChunk);
     const int64_t s = c / NT;
-    const int lane = q & 63, h = lane >> 5;
+    const int h = (q & 63) >> 5, sub = q >> 6;
     u32x4 v = in[u];
     if constexpr (EB == 8) {
-      const int kh = q >> 6;
-      const int64_t base = s * 64 + 32 * kh + 8 * h;
+      const int64_t base = tile::frag_row(L, s, sub, h, 0);  // the second run: 16 rows on
       const uint64_t m0 = run_mask(base) * 0xffull, m1 = run_mask(base + 16) * 0xffull;  // bytes 0x01 -> 0xff
       v[0] &= (unsigned)m0, v[1] &= (unsigned)(m0 >> 32), v[2] &= (unsigned)m1, v[3] &= (unsigned)(m1 >> 32);
     } else {
-      const int ki = q >> 6;
-      const uint64_t m = run_mask(s * 64 + 16 * ki + 8 * h);
+      const uint64_t m = run_mask(tile::frag_row(L, s, sub, h, 0));
 #pragma unroll
       for (int w = 0; w < 4; ++w) {  // dword w = rows 2w, 2w+1
         const unsigned lo = (unsigned)((m >> (16 * w)) & 1) * 0xffffu;
@@ -823,7 +796,7 @@ __global__ __launch_bounds__(256) void wide_mask_rows_kernel(const u32x4* __rest
 
 
 void wide_mask_rows(int eb, const void* in, void* out, int d, int64_t n, const uint8_t* sel, hipStream_t st) {
-  const int NT = ((d + 255) / 256) * 8;
+  const int NT = tile::tiles(tile::wide_layout(eb), d);
   const int64_t units = wide_tiled_bytes(eb, d, n) / 16;
   int64_t g = (units + 255) / 256;
   if (g > 16384) g = 16384;
@@ -837,20 +810,17 @@ void wide_mask_rows(int eb, const void* in, void* out, int d, int64_t n, const u
   DQ_HIP_CHECK(hipGetLastError());
 }
 
-int64_t wide_tiled_bytes(int eb, int d, int64_t n) {
-  const int NT = ((d + 255) / 256) * 8;
-  return ((n + 63) / 64) * NT * 4 * 64 * (int64_t)eb;
-}
+int64_t wide_tiled_bytes(int eb, int d, int64_t n) { return tile::bytes(tile::wide_layout(eb), d, n); }
 
-void feature_amax(const PackSrcW* srcs_dev, int d, int64_t n, const uint8_t* sel, float* amax, hipStream_t st,
+void feature_amax(const PackSrc* srcs_dev, int d, int64_t n, const uint8_t* sel, float* amax, hipStream_t st,
                   const float* shift) {
   hipLaunchKernelGGL(amax_kernel, dim3(d), dim3(256), 0, st, srcs_dev, n, sel, amax, shift);
   DQ_HIP_CHECK(hipGetLastError());
 }
 
-void pack_wide(int eb, const PackSrcW* srcs_dev, int d, int64_t n, int nt, const uint8_t* sel, const float* inv_scale,
+void pack_wide(int eb, const PackSrc* srcs_dev, int d, int64_t n, int nt, const uint8_t* sel, const float* inv_scale,
                void* out, hipStream_t st, const float* shift) {
-  const int64_t nsup = (n + 63) / 64;
+  const int64_t nsup = tile::supersteps(n);
   int64_t g = nsup * nt;
   if (g > 16384) g = 16384;
   if (g < 1) g = 1;
@@ -890,7 +860,7 @@ void wide_label_aug(int eb, const void* y, int ydt, int64_t n, const uint8_t* se
                     void* out, hipStream_t st) {
   if (eb != 8 && eb != 16) throw std::invalid_argument("wide_label_aug: eb must be 8 or 16");
   if (ydt != 0 && ydt != 1) throw std::invalid_argument("wide_label_aug: label must be f64 or f32");
-  const int64_t nsup = (n + 63) / 64;
+  const int64_t nsup = tile::supersteps(n);
   hipLaunchKernelGGL(wide_label_stats_kernel, dim3(kLabelBlocks), dim3(256), 0, st, y, ydt, n, sel, part);
   hipLaunchKernelGGL(wide_label_scales_kernel, dim3(1), dim3(64), 0, st, part, kLabelBlocks, eb, aux);
   int64_t g = nsup < 1 ? 1 : (nsup > 2048 ? 2048 : nsup);  // (grid-stride: ~10 supersteps per block)

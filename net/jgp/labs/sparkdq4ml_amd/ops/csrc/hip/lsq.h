@@ -6,8 +6,9 @@
 
 namespace dq4ml {
 
-// Feature-matrix layouts (the ``tiled`` codes of rowops): 0 plain feature-major [d][ld] of xdt
-// (f64 / f32 / bf16), 1 tall bf16 tiles (TiledBF16), 2 wide bf16 tiles, 3 wide fp8 tiles (TiledWide).
+// Feature-matrix layouts: the codes of tile::Layout (tile_layout.h, which owns the tile formats).
+// 0 plain feature-major [d][ld] of xdt (f64 / f32 / bf16), 1 tall bf16 tiles (TiledBF16), 2 wide
+// bf16 tiles, 3 wide fp8 tiles (TiledWide).
 struct LsqX {
   const void* X;
   int layout;

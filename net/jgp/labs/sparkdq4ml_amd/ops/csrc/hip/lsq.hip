@@ -22,6 +22,7 @@
 
 #include "common.h"
 #include "lsq.h"
+#include "tile_layout.h"
 
 namespace dq4ml {
 
@@ -31,39 +32,7 @@ constexpr int kMarginThreads = 512;
 constexpr int kColThreads = 256;
 constexpr int kPlainFB = 16;  // features per workgroup, plain layout
 
-__host__ __device__ constexpr int64_t chunk_bytes(int L) { return L == 3 ? 2048 : 4096; }
-__host__ __device__ constexpr int units_per_sup(int L) { return L == 3 ? 2 : 4; }
-
-inline int nt_of(int layout, int d) { return layout == 1 ? (d + 31) / 32 : ((d + 255) / 256) * 8; }
 inline int tg_of(int mode) { return mode ? 8 : 16; }
-
-// row of element e of the 16-byte fragment of lane half h in unit `sub` of superstep s
-template <int L>
-__device__ __forceinline__ int64_t frag_row(int64_t s, int sub, int h, int e) {
-  if constexpr (L == 1) return s * 64 + 32 * h + 8 * sub + e;  // tall: k-step i = rows 32h + 8i + j
-  else if constexpr (L == 2) return s * 64 + 16 * sub + 8 * h + e;  // wide bf16: k-step = 16 rows
-  else return s * 64 + 16 * (2 * sub + (e >> 3)) + 8 * h + (e & 7);  // wide fp8: half = 2 k-steps
-}
-
-template <int L>
-__device__ __forceinline__ void unpack(const u32x4 q, float* x) {
-  if constexpr (L == 3) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int v = (int)q[k];
-      x[4 * k + 0] = __builtin_amdgcn_cvt_f32_fp8(v, 0);
-      x[4 * k + 1] = __builtin_amdgcn_cvt_f32_fp8(v, 1);
-      x[4 * k + 2] = __builtin_amdgcn_cvt_f32_fp8(v, 2);
-      x[4 * k + 3] = __builtin_amdgcn_cvt_f32_fp8(v, 3);
-    }
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      x[2 * j] = __uint_as_float(q[j] << 16);
-      x[2 * j + 1] = __uint_as_float(q[j] & 0xffff0000u);
-    }
-  }
-}
 
 __device__ __forceinline__ double block_sum_f64(double s, double* red /* >= 16 doubles */) {
   s = wave_sum_f64(s);
@@ -103,10 +72,10 @@ __global__ __launch_bounds__(kMarginThreads) void lsq_margin_frag(
   extern __shared__ __attribute__((aligned(16))) double lsq_smem[];
   double* red = lsq_smem;                               // 16 doubles
   float* cs = reinterpret_cast<float*>(lsq_smem + 16);  // ntl * 32 floats
-  constexpr int E = L == 3 ? 16 : 8;
-  constexpr int64_t CH = chunk_bytes(L);
-  constexpr int UPS = units_per_sup(L);
-  const int ntl = (d + 31) >> 5;
+  constexpr int E = tile::frag_elems(L);
+  constexpr int64_t CH = tile::chunk_bytes(L);
+  constexpr int UPS = tile::units_per_sup(L);
+  const int ntl = tile::live_tiles(d);
   const double offset = *offp;  // device scalar: the optimizer never syncs to launch a pass
   if constexpr (CLDS) {
     for (int i = threadIdx.x; i < ntl * 32; i += blockDim.x) cs[i] = i < d ? cf[i] : 0.0f;
@@ -118,7 +87,7 @@ __global__ __launch_bounds__(kMarginThreads) void lsq_margin_frag(
   for (int64_t u = (int64_t)blockIdx.x * nw + wave; u < nunits; u += (int64_t)gridDim.x * nw) {
     const int64_t s = u / UPS;
     const int sub = (int)(u % UPS);
-    const unsigned char* p = X + s * NT * CH + ((sub * 64 + lane) << 4);
+    const unsigned char* p = tile::frag_ptr<L>(X, s * NT, sub, lane);
     double acc[E];
 #pragma unroll
     for (int e = 0; e < E; ++e) acc[e] = 0.0;
@@ -135,7 +104,7 @@ __global__ __launch_bounds__(kMarginThreads) void lsq_margin_frag(
         const int f = (t + k) * 32 + fl;
         const float c = CLDS ? cs[f] : (f < d ? cf[f] : 0.0f);
         float x[E];
-        unpack<L>(q[k], x);
+        tile::unpack<L>(q[k], x);
 #pragma unroll
         for (int e = 0; e < E; ++e) a[e] = fmaf(x[e], c, a[e]);
       }
@@ -147,7 +116,7 @@ __global__ __launch_bounds__(kMarginThreads) void lsq_margin_frag(
       const int f = t * 32 + fl;
       const float c = CLDS ? cs[f] : (f < d ? cf[f] : 0.0f);
       float x[E];
-      unpack<L>(q, x);
+      tile::unpack<L>(q, x);
 #pragma unroll
       for (int e = 0; e < E; ++e) acc[e] += (double)(x[e] * c);
     }
@@ -160,7 +129,7 @@ __global__ __launch_bounds__(kMarginThreads) void lsq_margin_frag(
     double m = acc[0];
 #pragma unroll
     for (int e = 1; e < E; ++e) m = fl == e ? acc[e] : m;
-    if (fl < E) row_epilogue(frag_row<L>(s, sub, h, fl), n, m, offset, inv_ystd, y, w, v, loss);
+    if (fl < E) row_epilogue(tile::frag_row(L, s, sub, h, fl), n, m, offset, inv_ystd, y, w, v, loss);
   }
   loss = block_sum_f64(loss, red);
   if (threadIdx.x == 0) lpart[blockIdx.x] = loss;
@@ -247,13 +216,13 @@ template <int L, int MODE, int TG>
 __global__ __launch_bounds__(kColThreads) void lsq_cols_frag(const unsigned char* __restrict__ X, int d, int NT,
                                                             int64_t n, int64_t nsup, int R,
                                                             const double* __restrict__ v, double* __restrict__ part) {
-  constexpr int E = L == 3 ? 16 : 8;
-  constexpr int64_t CH = chunk_bytes(L);
-  constexpr int UPS = units_per_sup(L);
+  constexpr int E = tile::frag_elems(L);
+  constexpr int64_t CH = tile::chunk_bytes(L);
+  constexpr int UPS = tile::units_per_sup(L);
   constexpr int NV = UPS * E;  // 32 rows per lane per superstep
   constexpr int NS = TG * (1 + MODE);
   __shared__ double red[4][NS][32];
-  const int ntl = (d + 31) >> 5;
+  const int ntl = tile::live_tiles(d);
   const int G = (ntl + TG - 1) / TG;
   const int tg = (int)(blockIdx.x % G), rho = (int)(blockIdx.x / G);
   const int64_t s0 = nsup * rho / R, s1 = nsup * (rho + 1) / R;
@@ -269,7 +238,7 @@ __global__ __launch_bounds__(kColThreads) void lsq_cols_frag(const unsigned char
     for (int sub = 0; sub < UPS; ++sub) {
 #pragma unroll
       for (int e0 = 0; e0 < E; e0 += 8) {
-        const int64_t r0 = frag_row<L>(s, sub, h, e0);  // 8 contiguous rows, r0 % 8 == 0
+        const int64_t r0 = tile::frag_row(L, s, sub, h, e0);  // 8 contiguous rows, r0 % 8 == 0
         if (r0 + 8 <= n) {
 #pragma unroll
           for (int j = 0; j < 8; j += 2) {
@@ -283,18 +252,18 @@ __global__ __launch_bounds__(kColThreads) void lsq_cols_frag(const unsigned char
         }
       }
     }
-    const unsigned char* p = X + (s * NT + tg * TG) * CH + (lane << 4);
+    const unsigned char* p = tile::frag_ptr<L>(X, s * NT + tg * TG, 0, lane);
 #pragma unroll
     for (int k = 0; k < TG; ++k) {
       if (k < nt) {
         u32x4 q[UPS];
 #pragma unroll
-        for (int sub = 0; sub < UPS; ++sub) q[sub] = *gptr<u32x4>(p + k * CH + sub * 1024);
+        for (int sub = 0; sub < UPS; ++sub) q[sub] = *gptr<u32x4>(tile::frag_ptr<L>(p, k, sub, 0));
         float a = 0.0f, a2 = 0.0f;
 #pragma unroll
         for (int sub = 0; sub < UPS; ++sub) {
           float x[E];
-          unpack<L>(q[sub], x);
+          tile::unpack<L>(q[sub], x);
 #pragma unroll
           for (int e = 0; e < E; ++e) {
             const float t = vv[sub * E + e] * x[e];
@@ -439,10 +408,10 @@ Split col_split(const LsqX& x, int mode) {
     sp.R = (int)(R < cap ? R : cap);
     sp.ldp = x.d;
   } else {
-    const int ntl = (x.d + 31) / 32;
+    const int ntl = tile::live_tiles(x.d);
     const int tg = tg_of(mode);
     sp.G = (ntl + tg - 1) / tg;
-    const int64_t nsup = (x.n + 63) / 64;
+    const int64_t nsup = tile::supersteps(x.n);
     int64_t R = (4096 + sp.G - 1) / sp.G;
     const int64_t cap = nsup > 1 ? nsup : 1;
     sp.R = (int)(R < cap ? R : cap);
@@ -460,7 +429,7 @@ void check(const LsqX& x) {
   if (x.layout == 0 && x.d > 1 && x.ld % 4 != 0) throw std::invalid_argument("lsq: plain layout needs ld % 4 == 0");
 }
 
-int margin_lds_bytes(const LsqX& x) { return 16 * 8 + ((x.d + 31) / 32) * 32 * 4; }
+int margin_lds_bytes(const LsqX& x) { return 16 * 8 + tile::live_tiles(x.d) * 32 * 4; }
 
 }  // namespace
 
@@ -470,7 +439,7 @@ int lsq_margin_blocks(const LsqX& x) {
     int64_t g = (nq + 255) / 256;
     return (int)(g < 1 ? 1 : (g > 2048 ? 2048 : g));
   }
-  const int64_t nunits = ((x.n + 63) / 64) * (x.layout == 3 ? 2 : 4);
+  const int64_t nunits = tile::supersteps(x.n) * tile::units_per_sup(x.layout);
   const int lds = margin_lds_bytes(x);
   const int per_cu = lds <= 32768 ? 4 : (lds <= 65536 + 128 ? 2 : 1);
   int64_t g = (nunits + 7) / 8;
@@ -505,8 +474,8 @@ void lsq_margin(const LsqX& x, const void* cf, const double* offset, double inv_
   }
   auto Xb = reinterpret_cast<const unsigned char*>(x.X);
   auto c = reinterpret_cast<const float*>(cf);
-  const int NT = nt_of(x.layout, x.d);
-  const int64_t nunits = ((x.n + 63) / 64) * (x.layout == 3 ? 2 : 4);
+  const int NT = tile::tiles(x.layout, x.d);
+  const int64_t nunits = tile::supersteps(x.n) * tile::units_per_sup(x.layout);
   const int lds = margin_lds_bytes(x);
   const bool clds = lds <= 131072;
   const unsigned smem = clds ? lds : 16 * 8;
@@ -538,8 +507,8 @@ void lsq_columns(const LsqX& x, int mode, const double* v, const double* lpart, 
 #undef DQ_LSQ_CP
   } else {
     auto Xb = reinterpret_cast<const unsigned char*>(x.X);
-    const int NT = nt_of(x.layout, x.d);
-    const int64_t nsup = (x.n + 63) / 64;
+    const int NT = tile::tiles(x.layout, x.d);
+    const int64_t nsup = tile::supersteps(x.n);
     const int g = sp.G * sp.R;
 #define DQ_LSQ_CF(LL, MM, TT) \
   hipLaunchKernelGGL((lsq_cols_frag<LL, MM, TT>), dim3(g), dim3(kColThreads), 0, st, Xb, x.d, NT, x.n, nsup, sp.R, v, part)

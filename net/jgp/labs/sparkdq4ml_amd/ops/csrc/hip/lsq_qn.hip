@@ -35,6 +35,7 @@
 #pragma clang fp contract(off)  // the scalar algebra mirrors the host's numpy / torch expressions
 
 #include "qn_ctl.h"  // (after the pragma: its functions take this file's contraction setting)
+#include "tile_layout.h"
 
 namespace dq4ml {
 
@@ -45,34 +46,6 @@ constexpr int kW = kT / kWave;
 constexpr int kMem = 10;
 constexpr int kWolfeCap = 10;  // L-BFGS: bracket and zoom steps of a strong-Wolfe search
 constexpr int kDParts = 4;  // per-block partials of an evaluation: x.(regw x), Σ|l1 x|, dir . g, g . g
-
-
-template <int L>
-__device__ __forceinline__ void unpack(const u32x4 q, float* x) {
-  if constexpr (L == 3) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int v = (int)q[k];
-      x[4 * k + 0] = __builtin_amdgcn_cvt_f32_fp8(v, 0);
-      x[4 * k + 1] = __builtin_amdgcn_cvt_f32_fp8(v, 1);
-      x[4 * k + 2] = __builtin_amdgcn_cvt_f32_fp8(v, 2);
-      x[4 * k + 3] = __builtin_amdgcn_cvt_f32_fp8(v, 3);
-    }
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      x[2 * j] = __uint_as_float(q[j] << 16);
-      x[2 * j + 1] = __uint_as_float(q[j] & 0xffff0000u);
-    }
-  }
-}
-
-// row of element e of the 16-byte fragment of lane half h in unit `sub` of superstep s (lsq.hip)
-template <int L>
-__device__ __forceinline__ int64_t frag_row(int64_t s, int sub, int h, int e) {
-  if constexpr (L == 2) return s * 64 + 16 * sub + 8 * h + e;
-  else return s * 64 + 16 * (2 * sub + (e >> 3)) + 8 * h + (e & 7);
-}
 
 struct Eval {
   double v, adj, dd, gg;
@@ -374,9 +347,9 @@ template <int L, int TPW>
 __device__ __forceinline__ void qn_pass(const QnArgs& a, const Std& S, int mode, double alpha, bool first, double pend,
                                         double offset, double* colacc, double* mrow, float* vrow, double* red,
                                         int b, int B) {
-  constexpr int E = L == 3 ? 16 : 8;
-  constexpr int64_t CH = L == 3 ? 2048 : 4096;
-  constexpr int UPS = L == 3 ? 2 : 4;
+  constexpr int E = tile::frag_elems(L);
+  constexpr int64_t CH = tile::chunk_bytes(L);
+  constexpr int UPS = tile::units_per_sup(L);
   constexpr int NC = 8 * TPW * 32;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6, fl = lane & 31, hf = lane >> 5;
   const bool owlqn = a.owlqn != 0;
@@ -386,7 +359,7 @@ __device__ __forceinline__ void qn_pass(const QnArgs& a, const Std& S, int mode,
   for (int64_t u = b; u < a.nunits; u += B) {
     const int64_t s = u / UPS;
     const int sub = (int)(u % UPS);
-    const unsigned char* p = a.X + s * a.NT * CH + ((sub * 64 + lane) << 4);
+    const unsigned char* p = tile::frag_ptr<L>(a.X, s * a.NT, sub, lane);
     double acc[E];
 #pragma unroll
     for (int e = 0; e < E; ++e) acc[e] = 0.0;
@@ -406,7 +379,7 @@ __device__ __forceinline__ void qn_pass(const QnArgs& a, const Std& S, int mode,
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
         float xv[E];
-        unpack<L>(q[k], xv);
+        tile::unpack<L>(q[k], xv);
 #pragma unroll
         for (int e = 0; e < E; ++e) s8[e] = fmaf(xv[e], c[k], s8[e]);
       }
@@ -426,7 +399,7 @@ __device__ __forceinline__ void qn_pass(const QnArgs& a, const Std& S, int mode,
     __syncthreads();
     if (t < 2 * E) {
       double mm = 0.0;
-      const int64_t r = frag_row<L>(s, sub, t / E, t % E);
+      const int64_t r = tile::frag_row(L, s, sub, t / E, t % E);
       if (!skip)
 #pragma unroll
         for (int i = 0; i < kW; ++i) mm += mrow[i * 2 * E + t];
@@ -470,7 +443,7 @@ __device__ __forceinline__ void qn_pass(const QnArgs& a, const Std& S, int mode,
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
         float xv[E];
-        unpack<L>(q[k], xv);
+        tile::unpack<L>(q[k], xv);
         float sa = 0.0f;
 #pragma unroll
         for (int e = 0; e < E; ++e) sa += vr[e] * xv[e];
@@ -575,7 +548,7 @@ template <int L, int TPW>
 __global__ __launch_bounds__(kT, 1) void lsq_qn_kernel(QnArgs a) {
   unsigned gen = 0;
   auto grid_sync = [&]() { grid_barrier(a.gbar, gen, gridDim.x); };
-  constexpr int E = L == 3 ? 16 : 8;
+  constexpr int E = tile::frag_elems(L);
   constexpr int NC = 8 * TPW * 32;  // coefficient slots (tiles padded to whole wave strides)
   __shared__ double colacc[NC];  // the block's f64 column sums (<= 128 KiB)
   __shared__ double red[kW];
@@ -753,7 +726,7 @@ __global__ __launch_bounds__(kT) void lsq_qn_dp_init_kernel(QnArgs a, int nc) {
 
 template <int L, int TPW>
 __global__ __launch_bounds__(kT, 1) void lsq_qn_dp_pass_kernel(QnArgs a) {
-  constexpr int E = L == 3 ? 16 : 8;
+  constexpr int E = tile::frag_elems(L);
   constexpr int NC = 8 * TPW * 32;
   __shared__ double colacc[NC];
   __shared__ double red[kW];
@@ -883,7 +856,7 @@ const void* pick(int layout, int tpw) {
 }
 
 int tpw_of(int d) {
-  const int ntl = (d + 31) / 32;
+  const int ntl = tile::live_tiles(d);
   const int need = (ntl + 7) / 8;
   return need <= 8 ? 8 : need <= 16 ? 16 : need <= 32 ? 32 : 64;
 }
@@ -921,10 +894,10 @@ QnArgs make_args(const LsqX& x, const double* y, const double* w, const double* 
   QnArgs a{};
   a.X = reinterpret_cast<const unsigned char*>(x.X);
   a.d = d;
-  a.ntl = (d + 31) / 32;
-  a.NT = ((d + 255) / 256) * 8;
+  a.ntl = tile::live_tiles(d);
+  a.NT = tile::tiles(x.layout, d);
   a.n = x.n;
-  a.nunits = ((x.n + 63) / 64) * (x.layout == 3 ? 2 : 4);
+  a.nunits = tile::supersteps(x.n) * tile::units_per_sup(x.layout);
   a.y = y, a.w = w, a.scale = scale, a.shift = shift, a.head = head;
   a.fit_icpt = fit_icpt, a.std_f = std_f, a.owlqn = enet != 0.0 && reg != 0.0;
   a.reg = reg, a.enet = enet, a.tol = tol, a.max_iter = max_iter, a.hist_cap = hist_cap;

@@ -479,7 +479,7 @@ PYBIND11_MODULE(_dq4ml_hip, m) {
     a.n = n;
     a.xdt = DT_F32;
     set_rows(a, y, ydt, 0, 0, sel, partials);
-    gram_cols(a, P<const PackSrcG>(srcs), sdt, blocks, P<double>(out), as_stream(stream));
+    gram_cols(a, P<const PackSrc>(srcs), sdt, blocks, P<double>(out), as_stream(stream));
   });
   m.def("tiled_elems", &tiled_elems);
   m.def("tile_bf16", [](uintptr_t X, int xdt, int64_t ld, int d, int64_t n, uintptr_t out, uintptr_t stream,
@@ -535,7 +535,7 @@ PYBIND11_MODULE(_dq4ml_hip, m) {
   m.attr("WIDE_ZERO_BYTES") = kWideZeroBytes;
   m.def("pack_wide", [](int eb, uintptr_t srcs_dev, int d, int64_t n, int nt, uintptr_t sel, uintptr_t inv_scale,
                         uintptr_t out, uintptr_t stream, uintptr_t shift) {
-    pack_wide(eb, P<const PackSrcW>(srcs_dev), d, n, nt, P<const uint8_t>(sel), P<const float>(inv_scale), P<void>(out),
+    pack_wide(eb, P<const PackSrc>(srcs_dev), d, n, nt, P<const uint8_t>(sel), P<const float>(inv_scale), P<void>(out),
               as_stream(stream), P<const float>(shift));
   });
   m.def("wide_label_part_doubles", &wide_label_part_doubles);
@@ -552,7 +552,7 @@ PYBIND11_MODULE(_dq4ml_hip, m) {
   });
   m.def("feature_amax", [](uintptr_t srcs_dev, int d, int64_t n, uintptr_t sel, uintptr_t amax, uintptr_t stream,
                            uintptr_t shift) {
-    feature_amax(P<const PackSrcW>(srcs_dev), d, n, P<const uint8_t>(sel), P<float>(amax), as_stream(stream),
+    feature_amax(P<const PackSrc>(srcs_dev), d, n, P<const uint8_t>(sel), P<float>(amax), as_stream(stream),
                  P<const float>(shift));
   });
   auto wide_args = [](uintptr_t X, uintptr_t Xaug, uintptr_t zeros, int nt, int npanels, int d, int64_t nsup,

@@ -4,15 +4,10 @@
 
 #include <cstdint>
 
+#include "common.h"  // PackSrc
 #include "huber_qn.h"
 
 namespace dq4ml {
-
-struct PackSrc {
-  const void* ptr;
-  int dt;
-  int pad;
-};
 
 int64_t compact_blocks(int64_t n);
 // counts must hold compact_blocks(n) + 1 int64: exclusive offsets + total at [nb]

@@ -16,6 +16,7 @@
 #include "common.h"
 #include "rowops.h"
 #include "scan_host.h"
+#include "tile_layout.h"
 
 namespace dq4ml {
 
@@ -103,51 +104,23 @@ __global__ __launch_bounds__(256) void pack_kernel(const PackSrc* __restrict__ s
 }
 
 // ---- predict / metrics -----------------------------------------------------------------------
-// element offset of (feature f, row r) in the MFMA-fragment-ordered bf16 layout (gram.h)
-__device__ __forceinline__ int64_t tiled_offset(int f, int64_t r, int NT) {
-  const int64_t s = r >> 6;
-  const int h = (int)((r >> 5) & 1), i = (int)((r >> 3) & 3), j = (int)(r & 7);
-  const int t = f >> 5, lane = 32 * h + (f & 31);
-  return ((((s * NT + t) * 4 + i) * 64 + lane) << 3) + j;
-}
-
-// wide layouts (gram_wide.hip): k-step ki = 16 contiguous rows, 8 B (fp8) / 16 B (bf16) per lane
-__device__ __forceinline__ int64_t wide_offset(int f, int64_t r, int NT) {
-  const int64_t s = r >> 6;
-  const int ki = (int)((r >> 4) & 3), h = (int)((r >> 3) & 1), j = (int)(r & 7);
-  const int t = f >> 5, lane = 32 * h + (f & 31);
-  return ((((s * NT + t) * 4 + ki) * 64 + lane) << 3) + j;  // element index
-}
-
-// fp8 wide image: per (superstep, tile) a [2 halves][64 lanes][16 B] chunk; a lane's 32 bytes are
-// its k-steps 0..3 (8 rows each), halves = k-steps {0,1} / {2,3} (gram_wide.hip)
-__device__ __forceinline__ int64_t wide_offset_fp8(int f, int64_t r, int NT) {
-  const int64_t s = r >> 6;
-  const int ki = (int)((r >> 4) & 3), h = (int)((r >> 3) & 1), j = (int)(r & 7);
-  const int t = f >> 5, lane = 32 * h + (f & 31);
-  return (s * NT + t) * 2048 + (((ki >> 1) * 64 + lane) << 4) + ((ki & 1) << 3) + j;  // byte index
-}
-
-__device__ __forceinline__ float fp8_to_f32(uint8_t v) {
-  return __builtin_amdgcn_cvt_f32_fp8((int)v, 0);
-}
-
+// (the MFMA-fragment tile layouts, codes 1-3: tile_layout.h; for the wide fp8 tiles coef comes
+// pre-multiplied by the per-feature scales)
 __device__ __forceinline__ double predict_row(const void* X, int xdt, int64_t ld, int d, const double* coef,
                                               double b, int64_t r, int tiled) {
   double acc = b;
-  if (tiled == 2 || tiled == 3) {  // wide bf16 / wide fp8 (coef pre-multiplied by the fp8 scales)
-    const int NT = ((d + 255) >> 8) * 8;
+  if (tiled == tile::kWide || tiled == tile::kWideFp8) {
+    const int NT = tile::tiles(tile::kWide, d);
     for (int f = 0; f < d; ++f) {
-      const float x = tiled == 2 ? bf16_bits_to_f32(reinterpret_cast<const uint16_t*>(X)[wide_offset(f, r, NT)])
-                                 : fp8_to_f32(reinterpret_cast<const uint8_t*>(X)[wide_offset_fp8(f, r, NT)]);
+      const float x = tiled == tile::kWide ? tile::load_elem<tile::kWide>(X, f, r, NT)
+                                           : tile::load_elem<tile::kWideFp8>(X, f, r, NT);
       acc += coef[f] * (double)x;
     }
     return acc;
   }
   if (tiled) {
-    const int NT = (d + 31) >> 5;
-    const uint16_t* xb = reinterpret_cast<const uint16_t*>(X);
-    for (int f = 0; f < d; ++f) acc += coef[f] * (double)bf16_bits_to_f32(xb[tiled_offset(f, r, NT)]);
+    const int NT = tile::tiles(tile::kTall, d);
+    for (int f = 0; f < d; ++f) acc += coef[f] * (double)tile::load_elem<tile::kTall>(X, f, r, NT);
     return acc;
   }
   for (int f = 0; f < d; ++f) acc += coef[f] * ld_f64(X, xdt, (int64_t)f * ld + r);
@@ -158,12 +131,12 @@ __device__ __forceinline__ double predict_row(const void* X, int xdt, int64_t ld
 // One block-iteration = one (superstep s, tile t) chunk (64 rows x 32 features, 4 KiB out):
 // thread (f, q) loads rows [8q, 8q+8) of feature f with 16-B vector loads (8 threads per feature
 // -> every wave reads 8 contiguous 256-B column runs) and that run is exactly one lane's
-// fragment of k-step q & 3 for lane half q >> 2 -> one 16-B store, no transpose.
+// fragment (run q of the tall layout, tile_layout.h) -> one 16-B store, no transpose.
 __global__ __launch_bounds__(256) void pack_tiled_kernel(const PackSrc* __restrict__ srcs, int d, int64_t n,
                                                         const uint8_t* __restrict__ sel, int NT, int64_t nsup,
-                                                        uint16_t* __restrict__ out, const float* __restrict__ shift) {
+                                                        unsigned char* __restrict__ out,
+                                                        const float* __restrict__ shift) {
   const int fl = threadIdx.x >> 3, q = threadIdx.x & 7;
-  const int i = q & 3, h = q >> 2;
   const int64_t nchunks = nsup * NT;
   for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
     const int t = (int)(c % NT);
@@ -180,11 +153,7 @@ __global__ __launch_bounds__(256) void pack_tiled_kernel(const PackSrc* __restri
 #pragma unroll
       for (int j = 0; j < 8; ++j) x[j] = 0.0f;
     }
-    bf16x8 v;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = (__bf16)x[j];
-    // chunk c = [4 k-steps][64 lanes][8 bf16]; tall layout: lane 32h + f holds rows 32h + 8i + j
-    reinterpret_cast<u32x4*>(out)[c * 256 + i * 64 + h * 32 + fl] = __builtin_bit_cast(u32x4, v);
+    tile::store_run<tile::kTall>(out, c, q, fl, x);
   }
 }
 
@@ -231,36 +200,10 @@ __global__ __launch_bounds__(256) void metrics_kernel(const void* __restrict__ X
 
 // ---- predict / metrics over the MFMA-fragment layouts (tiled codes 1 tall bf16, 2 wide bf16,
 // 3 wide fp8): block-iteration = one superstep (64 rows).  Thread (f, q) walks the tiles reading
-// its 16-B (8-B fp8) fragment = rows [8q, 8q+8) of feature t*32 + f in every layout and
-// accumulates coef * x (f64) for those 8 rows.  The 8 feature-threads of a wave fold with
+// its 16-B (8-B fp8) run = rows [8q, 8q+8) of feature t*32 + f in every layout (tile::load_run)
+// and accumulates coef * x (f64) for those 8 rows.  The 8 feature-threads of a wave fold with
 // shuffles, the 4 waves through a double-buffered 2 KiB LDS slab (one barrier per superstep),
 // and the next superstep's fragments are loaded before that barrier.
-template <int TILED>
-__device__ __forceinline__ void frag8(const unsigned char* X, int64_t ch, int q, int fl, float x[8]) {
-  if constexpr (TILED == 3) {
-    const int ki = q >> 1, lane = 32 * (q & 1) + fl;
-    const uint64_t v = *gptr<uint64_t>(X + ch * 2048 + (((ki >> 1) * 64 + lane) << 4) + ((ki & 1) << 3));
-    const int lo = (int)(uint32_t)v, hi = (int)(uint32_t)(v >> 32);
-    x[0] = __builtin_amdgcn_cvt_f32_fp8(lo, 0);
-    x[1] = __builtin_amdgcn_cvt_f32_fp8(lo, 1);
-    x[2] = __builtin_amdgcn_cvt_f32_fp8(lo, 2);
-    x[3] = __builtin_amdgcn_cvt_f32_fp8(lo, 3);
-    x[4] = __builtin_amdgcn_cvt_f32_fp8(hi, 0);
-    x[5] = __builtin_amdgcn_cvt_f32_fp8(hi, 1);
-    x[6] = __builtin_amdgcn_cvt_f32_fp8(hi, 2);
-    x[7] = __builtin_amdgcn_cvt_f32_fp8(hi, 3);
-    return;
-  }
-  const int64_t unit = TILED == 1 ? ch * 256 + (q & 3) * 64 + (q >> 2) * 32 + fl
-                                  : ch * 256 + (q >> 1) * 64 + 32 * (q & 1) + fl;
-  const u32x4 v = gptr<u32x4>(X)[unit];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    x[2 * j] = __uint_as_float(v[j] << 16);
-    x[2 * j + 1] = __uint_as_float(v[j] & 0xffff0000u);
-  }
-}
-
 template <int MODE, int YDT, int TILED>  // MODE 0: predictions -> out, 1: the 8 metric sums -> partials
 __global__ __launch_bounds__(256) void tiled_rows_kernel(const unsigned char* __restrict__ X, int tiled, int d,
                                                         int64_t n, const double* __restrict__ coef, double b,
@@ -271,11 +214,11 @@ __global__ __launch_bounds__(256) void tiled_rows_kernel(const unsigned char* __
   __shared__ double wpart[4][8][65];  // per wave: [feature-thread][row] (+1 pad)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int fl = tid >> 3, q = tid & 7;
-  const int NT = TILED == 1 ? (d + 31) >> 5 : ((d + 255) >> 8) * 8;
+  const int NT = tile::tiles(TILED, d);
   // tall layouts (<= 2 tiles): the thread's coefficients live in registers
   double c2[2] = {fl < d ? coef[fl] : 0.0, 32 + fl < d ? coef[32 + fl] : 0.0};
-  const int ntiles = (d + 31) >> 5;
-  const int64_t nsup = (n + 63) >> 6;
+  const int ntiles = tile::live_tiles(d);
+  const int64_t nsup = tile::supersteps(n);
   double m[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   int buf = 0;
   for (int64_t s = blockIdx.x; s < nsup; s += gridDim.x) {
@@ -290,8 +233,8 @@ __global__ __launch_bounds__(256) void tiled_rows_kernel(const unsigned char* __
     double acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if constexpr (TILED == 1) {  // tall: <= 2 tiles, both fragments requested before use
       float x0[8], x1[8];
-      frag8<1>(X, s * NT, q, fl, x0);
-      if (ntiles > 1) frag8<1>(X, s * NT + 1, q, fl, x1);
+      tile::load_run<TILED>(X, s * NT, q, fl, x0);
+      if (ntiles > 1) tile::load_run<TILED>(X, s * NT + 1, q, fl, x1);
 #pragma unroll
       for (int j = 0; j < 8; ++j) acc[j] = c2[0] * (double)x0[j];
       if (ntiles > 1) {
@@ -302,7 +245,7 @@ __global__ __launch_bounds__(256) void tiled_rows_kernel(const unsigned char* __
       for (int t = 0; t < ntiles; ++t) {
         const int f = t * 32 + fl;
         float x[8];
-        frag8<TILED>(X, s * NT + t, q, fl, x);
+        tile::load_run<TILED>(X, s * NT + t, q, fl, x);
         const double c = f < d ? coef[f] : 0.0;
 #pragma unroll
         for (int j = 0; j < 8; ++j) acc[j] += c * (double)x[j];
@@ -400,13 +343,13 @@ void pack_columns(const PackSrc* srcs_dev, int d, int64_t n, void* out, int odt,
 
 void pack_tiled(const PackSrc* srcs_dev, int d, int64_t n, const uint8_t* sel, void* out, hipStream_t st,
                 const float* shift) {
-  const int NT = (d + 31) / 32;
-  const int64_t nsup = (n + 63) / 64;
+  const int NT = tile::tiles(tile::kTall, d);
+  const int64_t nsup = tile::supersteps(n);
   int64_t g = nsup * NT;
   if (g > 16384) g = 16384;
   if (g < 1) g = 1;
   hipLaunchKernelGGL(pack_tiled_kernel, dim3(g), dim3(256), 0, st, srcs_dev, d, n, sel, NT, nsup,
-                     reinterpret_cast<uint16_t*>(out), shift);
+                     reinterpret_cast<unsigned char*>(out), shift);
   DQ_HIP_CHECK(hipGetLastError());
 }
 
@@ -414,7 +357,7 @@ void predict(const void* X, int xdt, int64_t ld, int d, int64_t n, const double*
              hipStream_t st, int tiled) {
   if (n <= 0) return;
   if (tiled) {
-    int64_t g = (n + 63) / 64;
+    int64_t g = tile::supersteps(n);
     if (g > 8192) g = 8192;
     auto xb = reinterpret_cast<const unsigned char*>(X);
     if (tiled == 1) hipLaunchKernelGGL((tiled_rows_kernel<0, DT_F64, 1>), dim3(g), dim3(256), 0, st, xb, tiled, d, n, coef, b, nullptr, 0, nullptr, 0.0, out);
@@ -467,11 +410,10 @@ namespace dq4ml {
 namespace {
 
 __device__ __forceinline__ double load_x(const void* X, int xdt, int64_t ld, int d, int f, int64_t r, int tiled) {
-  if (tiled == 1) return (double)bf16_bits_to_f32(reinterpret_cast<const uint16_t*>(X)[tiled_offset(f, r, (d + 31) >> 5)]);
-  if (tiled == 2)
-    return (double)bf16_bits_to_f32(reinterpret_cast<const uint16_t*>(X)[wide_offset(f, r, ((d + 255) >> 8) * 8)]);
-  if (tiled == 3)
-    return (double)fp8_to_f32(reinterpret_cast<const uint8_t*>(X)[wide_offset_fp8(f, r, ((d + 255) >> 8) * 8)]);
+  if (tiled == tile::kTall) return (double)tile::load_elem<tile::kTall>(X, f, r, tile::tiles(tile::kTall, d));
+  if (tiled == tile::kWide) return (double)tile::load_elem<tile::kWide>(X, f, r, tile::tiles(tile::kWide, d));
+  if (tiled == tile::kWideFp8)
+    return (double)tile::load_elem<tile::kWideFp8>(X, f, r, tile::tiles(tile::kWideFp8, d));
   return ld_f64(X, xdt, (int64_t)f * ld + r);
 }
 

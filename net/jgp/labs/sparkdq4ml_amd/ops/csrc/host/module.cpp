@@ -1,5 +1,6 @@
-// pybind11 bindings of the host runtime library (_dq4ml_host): normal-equation solvers and the
-// CSV scanner.  Device kernels live in the separate gfx950 module (_dq4ml_hip).
+// pybind11 bindings of the host runtime library (_dq4ml_host): normal-equation solvers, the CSV
+// scanner and the tile-format arithmetic the kernels share (tile_layout.h).  Device kernels live
+// in the separate gfx950 module (_dq4ml_hip).
 #include <cstring>
 
 #include <pybind11/numpy.h>
@@ -8,6 +9,7 @@
 
 #include "csv.h"
 #include "solvers.h"
+#include "tile_layout.h"
 #include "wls.h"
 
 namespace py = pybind11;
@@ -104,6 +106,17 @@ PYBIND11_MODULE(_dq4ml_host, m) {
         },
         py::arg("bBar"), py::arg("bbBar"), py::arg("ab"), py::arg("aa"), py::arg("aBar"), py::arg("fit_intercept"),
         py::arg("max_iter"), py::arg("tol"), py::arg("l1") = py::none(), py::arg("memory") = 10);
+
+  // tile_layout.h as the kernels compile it, over numpy arrays (broadcast): what
+  // tests/test_tile_layout_host.py holds against ops/layout.py
+  m.def("tile_elem_offsets", py::vectorize([](int layout, int f, int64_t r, int nt) {
+          return tile::elem_offset(layout, f, r, nt);
+        }), py::arg("layout"), py::arg("feats"), py::arg("rows"), py::arg("nt"));
+  m.def("tile_frag_rows", py::vectorize([](int layout, int64_t s, int sub, int h, int e) {
+          return tile::frag_row(layout, s, sub, h, e);
+        }), py::arg("layout"), py::arg("s"), py::arg("sub"), py::arg("h"), py::arg("e"));
+  m.def("tile_tiles", [](int layout, int d) { return tile::tiles(layout, d); });
+  m.def("tile_bytes", [](int layout, int d, int64_t n) { return tile::bytes(layout, d, n); });
 
   m.def("csv_infer_field", [](const std::string& s) { return csv_infer_field(s.data(), s.size()); });
   m.def("csv_merge_types", &csv_merge_types);

@@ -160,7 +160,7 @@ def _feature_view(X: torch.Tensor, align_elems: int):
 
 # ------------------------------------------------------------------------------------------
 from .layout import (PATCH_CAP, PATCH_INLINE, PATCH_SHARE, SLOT_DWORDS, PackedTiles, PatchedTiles, TiledBF16,  # noqa: E402
-                     TiledWide, gram_layout_size, patched_entries)
+                     TiledWide, gram_layout_size, patched_entries, wide_bytes, wide_tiles)
 from .shift import column_shift  # noqa: E402
 
 FP8_MAX = 448.0
@@ -1333,7 +1333,7 @@ def _pack_desc(h, parts, dev):
     for r in rows:
         if r.numel() != n:
             raise ValueError("pack: columns of different lengths")
-    desc = np.zeros((len(rows), 2), dtype=np.int64)  # PackSrcW {ptr, dt, pad}
+    desc = np.zeros((len(rows), 2), dtype=np.int64)  # PackSrc {ptr, dt, pad}
     for i, r in enumerate(rows):
         desc[i, 0] = r.data_ptr()
         desc[i, 1] = dtype_code(r)
@@ -1929,7 +1929,7 @@ def pcg_ok(o: np.ndarray) -> bool:
 # wide (d > 64) fragment layouts + LDS-tiled MFMA SYRK
 # ------------------------------------------------------------------------------------------
 def _srcw_desc(h, rows, dev):
-    desc = np.zeros((len(rows), 2), dtype=np.int64)  # PackSrcW {ptr, dt, pad}
+    desc = np.zeros((len(rows), 2), dtype=np.int64)  # PackSrc {ptr, dt, pad}
     for i, r in enumerate(rows):
         desc[i, 0] = r.data_ptr()
         desc[i, 1] = dtype_code(r)
@@ -1980,8 +1980,8 @@ def pack_wide(parts: List[torch.Tensor], eb: int, sel: Optional[torch.Tensor] = 
         inv_scale = 1.0 / scales
     elif eb == 8:
         scales = 1.0 / inv_scale
-    nt = nt or ((d + 255) // 256) * 8
-    nbytes = ((n + 63) // 64) * nt * 4 * 64 * eb
+    nt = nt or wide_tiles(d)
+    nbytes = wide_bytes(nt, n, eb)
     if out is not None:
         if out.dtype != torch.uint8 or out.numel() != nbytes or not out.is_contiguous() or out.device != dev:
             raise ValueError(f"pack_wide: out must be a contiguous uint8 tensor of {nbytes} bytes on {dev}")

@@ -20,7 +20,7 @@ from __future__ import annotations
 
 import torch
 
-__all__ = ["TiledBF16", "tiled_offsets", "PackedTiles", "pack_reference", "unpack_reference",
+__all__ = ["TiledBF16", "tiled_offsets", "tall_tiles", "wide_tiles", "wide_bytes", "PackedTiles", "pack_reference", "unpack_reference",
            "PatchedTiles", "patch_reference", "unpatch_reference", "patched_entries", "gram_layout_size"]
 
 
@@ -30,9 +30,27 @@ def gram_layout_size(d: int) -> int:
     return 5 + 2 * d + d * (d + 1) // 2
 
 
+def tall_tiles(d: int) -> int:
+    """32-feature tiles of a superstep in the tall layout (``TiledBF16``): the live ones."""
+    return (d + 31) // 32
+
+
+def wide_tiles(d: int) -> int:
+    """32-feature tiles of a superstep in the wide layouts (``TiledWide``): whole 256-feature panels."""
+    return ((d + 255) // 256) * 8
+
+
+def wide_bytes(nt: int, n: int, eb: int) -> int:
+    """Bytes of a wide tiled buffer of ``n`` rows and tile stride ``nt``: 64 x 32 elements per
+    (superstep, tile) chunk, ``eb // 8`` bytes each."""
+    return ((n + 63) // 64) * nt * 2048 * (eb // 8)
+
+
 def tiled_offsets(feats: torch.Tensor, rows: torch.Tensor, d: int) -> torch.Tensor:
-    """Element offsets of (feature, row) pairs (broadcast) in the tiled layout."""
-    NT = (d + 31) // 32
+    """Element offsets of (feature, row) pairs (broadcast) in the tiled layout.  This function and
+    :func:`wide_offsets` are the specification of the formats; csrc/host/tile_layout.h is the
+    native twin that every kernel-side user takes them from, tested against these."""
+    NT = tall_tiles(d)
     s = rows >> 6
     h = (rows >> 5) & 1
     i = (rows >> 3) & 3
@@ -298,7 +316,7 @@ def wide_offsets(feats: torch.Tensor, rows: torch.Tensor, d: int, eb: int = 16) 
     panels (csrc/hip/gram_wide.hip).  Per (superstep s = 64 rows, 32-feature tile t) one chunk of
     512 elements: bf16 ``[k-step][64 lanes][8]``; fp8 ``[half][64 lanes][16]`` where a lane's 32
     bytes are its 4 k-steps (half = k-step >> 1) — one K=64 block-scaled MFMA operand."""
-    NT = ((d + 255) // 256) * 8
+    NT = wide_tiles(d)
     s = rows >> 6
     ki = (rows >> 4) & 3
     h = (rows >> 3) & 1
@@ -320,7 +338,7 @@ class TiledWide:
 
     @property
     def nt(self):
-        return ((self.d + 255) // 256) * 8
+        return wide_tiles(self.d)
 
     @property
     def shape(self):

@@ -31,6 +31,7 @@ import numpy as np
 import torch
 
 from ..utils.logging import get_logger
+from .layout import tall_tiles
 
 __all__ = ["try_fused_stream", "kernel_source", "raw_layout", "STATS", "ENTRY"]
 
@@ -211,7 +212,7 @@ def _compile(chain, rel, feat_cols, mode):
         layout = raw_layout([(c, sizes[c], nullable[c]) for c in used])
         if not used or layout is None:
             raise dqvm.Unfusable("stream prologue: row-scalar area")
-        NT = (d + 31) // 32
+        NT = tall_tiles(d)
         RING = 3 if 4 * _wave_bytes(NT, 3) <= 160 * 1024 else 2
         ctypes = {c: dqvm._ctype(schema.fields[c].dataType) for c in used}
         src = kernel_source(g, layout, ctypes, yv, NT, RING, {2: 1, 1: 0, 4: 2}[mode], yvalid)
