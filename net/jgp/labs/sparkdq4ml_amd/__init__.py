@@ -13,6 +13,7 @@ from .models.linalg import Vectors, DenseVector, SparseVector, Vector
 from .models.feature import VectorAssembler, Imputer, ImputerModel
 from .models.regression import (LinearRegression, LinearRegressionModel,
                                 LinearRegressionTrainingSummary)
+from .models.clustering import KMeans, KMeansModel, KMeansSummary
 from .models.glm import (GeneralizedLinearRegression, GeneralizedLinearRegressionModel,
                          GeneralizedLinearRegressionSummary, GeneralizedLinearRegressionTrainingSummary)
 from .models.tuning import (ParamGridBuilder, CrossValidator, CrossValidatorModel, TrainValidationSplit,
@@ -29,5 +30,5 @@ __all__ = [
     "ParamGridBuilder", "CrossValidator", "CrossValidatorModel", "TrainValidationSplit",
     "TrainValidationSplitModel", "Imputer", "ImputerModel", "IqrRule", "Window", "WindowSpec",
     "GeneralizedLinearRegression", "GeneralizedLinearRegressionModel", "GeneralizedLinearRegressionSummary",
-    "GeneralizedLinearRegressionTrainingSummary",
+    "GeneralizedLinearRegressionTrainingSummary", "KMeans", "KMeansModel", "KMeansSummary",
 ]

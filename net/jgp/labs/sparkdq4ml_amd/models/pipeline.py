@@ -15,6 +15,7 @@ _CLASS_OF = {
     "LinearRegression": "org.apache.spark.ml.regression.LinearRegression",
     "LinearRegressionModel": "org.apache.spark.ml.regression.LinearRegressionModel",
     "GeneralizedLinearRegression": "org.apache.spark.ml.regression.GeneralizedLinearRegression",
+    "KMeans": "org.apache.spark.ml.clustering.KMeans",
     "Pipeline": "org.apache.spark.ml.Pipeline",
     "PipelineModel": "org.apache.spark.ml.PipelineModel",
 }
@@ -22,6 +23,7 @@ _CLASS_OF = {
 
 def _stage_loader(cls_name: str):
     from .feature import VectorAssembler
+    from .clustering import KMeans
     from .glm import GeneralizedLinearRegression
     from .regression import LinearRegression, LinearRegressionModel
 
@@ -30,6 +32,7 @@ def _stage_loader(cls_name: str):
         "org.apache.spark.ml.regression.LinearRegression": LinearRegression,
         "org.apache.spark.ml.regression.LinearRegressionModel": LinearRegressionModel,
         "org.apache.spark.ml.regression.GeneralizedLinearRegression": GeneralizedLinearRegression,
+        "org.apache.spark.ml.clustering.KMeans": KMeans,
         "org.apache.spark.ml.Pipeline": Pipeline,
         "org.apache.spark.ml.PipelineModel": PipelineModel,
     }[cls_name]

@@ -15,6 +15,7 @@
 #include "gram.h"
 #include "gram_folds.h"
 #include "glm_irls.h"
+#include "kmeans.h"
 #include "quantile.h"
 #include "groupby.h"
 #include "sort.h"
@@ -238,6 +239,30 @@ PYBIND11_MODULE(_dq4ml_hip, m) {
   });
   m.def("glm_step", [](uintptr_t sol, int d, double tol, bool init, uintptr_t beta, uintptr_t state, uintptr_t stream) {
     glm_step(P<const double>(sol), d, tol, init ? 1 : 0, P<double>(beta), P<double>(state), as_stream(stream));
+  });
+  // ---- k-means (K5k): the fused Lloyd pass, the slab reduce and the centre update --------------
+  m.def("kmeans_blocks", &kmeans_blocks);
+  m.def("kmeans_stats_size", [](int k, int d) { return kmeans_stats_size(k, d); });
+  m.def("kmeans_pass", [](uintptr_t X, int64_t ld, int d, int64_t n, int xdt, uintptr_t sel, uintptr_t centers, int k,
+                          uintptr_t state, int mode, uintptr_t partials, uintptr_t assign, uintptr_t cost, int blocks,
+                          uintptr_t stream) {
+    GramArgs a{};
+    a.X = P<const void>(X);
+    a.ld = ld;
+    a.d = d;
+    a.n = n;
+    a.xdt = xdt;
+    a.sel = P<const uint8_t>(sel);
+    a.partials = P<double>(partials);
+    kmeans_pass(a, P<const double>(centers), k, P<const double>(state), mode, P<int32_t>(assign), P<double>(cost),
+                blocks, as_stream(stream));
+  });
+  m.def("kmeans_reduce", [](uintptr_t partials, int blocks, int k, int d, uintptr_t stats, uintptr_t stream) {
+    kmeans_reduce(P<const double>(partials), blocks, k, d, P<double>(stats), as_stream(stream));
+  });
+  m.def("kmeans_update", [](uintptr_t stats, int k, int d, double tol, uintptr_t centers, uintptr_t state,
+                            uintptr_t stream) {
+    kmeans_update(P<const double>(stats), k, d, tol, P<double>(centers), P<double>(state), as_stream(stream));
   });
   m.def("quantile_blocks", &quantile_blocks);
   m.def("quantile_limits", []() { return py::make_tuple(kMaxQuantiles, kMaxQuantCols, kQuantPasses, kQuantBins); });

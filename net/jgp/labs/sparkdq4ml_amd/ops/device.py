@@ -555,6 +555,119 @@ def glm_fit(X, y, w, sel, family: str, link: str, fit_icpt: bool, reg: float, ma
 
 
 # ------------------------------------------------------------------------------------------
+# k-means: the fused Lloyd pass (csrc/hip/kmeans.hip)
+# ------------------------------------------------------------------------------------------
+def _centers_dev(centers, d: int, dev) -> torch.Tensor:
+    """``[k, d]`` centres as the device buffer of the pass: centres (centre-major), then 0.5 |c|^2."""
+    C = np.asarray(centers.detach().cpu().numpy() if torch.is_tensor(centers) else centers, dtype=np.float64)
+    if C.ndim != 2 or C.shape[1] != d or not 2 <= C.shape[0] <= 64:
+        raise ValueError("kmeans_pass: centers must be [k, d] with 2 <= k <= 64")
+    return _h2d(np.concatenate([C.reshape(-1), 0.5 * (C * C).sum(axis=1)]), dev)
+
+
+class _KMeansPlan:
+    """Validated operands of the fused pass for one (X, sel, k): view, codes, grids, slabs."""
+
+    def __init__(self, X, sel, k: int, blocks: Optional[int]):
+        self.h = native.hip()
+        self.k = int(k)
+        self.Xv, self.ld, self.xdt = _staged_features(X, (sel,), "kmeans_pass", "1 <= d <= 64, 2 <= k <= 64 and n >= 1",
+                                                      2 <= self.k <= 64)
+        self.d, self.n = int(X.shape[0]), int(X.shape[1])
+        self.sel = _mask_u8(sel, self.n, "the selection", "kmeans_pass")
+        self.blocks, self.dev = blocks, X.device
+        if blocks is not None and int(blocks) < 1:
+            raise ValueError("kmeans_pass: blocks must be >= 1")
+        self.P = self.k * self.d + self.k + 2
+        self.partials = self.stats = None
+
+    def _nb(self, mode: int) -> int:
+        return _grid(self.blocks, ("kmeans", self.d, self.k, self.n, self.xdt, mode),
+                     lambda: self.h.kmeans_blocks(self.d, self.k, self.n, self.xdt, mode))
+
+    def step(self, cen: torch.Tensor, state: torch.Tensor) -> torch.Tensor:
+        """Enqueue pass + slab reduce; returns this rank's statistics."""
+        nb, st = self._nb(0), _stream()
+        if self.partials is None:
+            self.partials = torch.empty(nb * self.P, dtype=torch.float64, device=self.dev)
+            self.stats = torch.empty(self.P, dtype=torch.float64, device=self.dev)
+        self.h.kmeans_pass(self.Xv.data_ptr(), int(self.ld), self.d, self.n, self.xdt, _ptr(self.sel), cen.data_ptr(),
+                           self.k, state.data_ptr(), 0, self.partials.data_ptr(), 0, 0, nb, st)
+        self.h.kmeans_reduce(self.partials.data_ptr(), nb, self.k, self.d, self.stats.data_ptr(), st)
+        return self.stats
+
+    def assign(self, cen: torch.Tensor, want_cost: bool):
+        idx = torch.empty(self.n, dtype=torch.int32, device=self.dev)
+        cost = torch.empty(self.n, dtype=torch.float64, device=self.dev) if want_cost else None
+        self.h.kmeans_pass(self.Xv.data_ptr(), int(self.ld), self.d, self.n, self.xdt, _ptr(self.sel), cen.data_ptr(),
+                           self.k, 0, 1, 0, idx.data_ptr(), _ptr(cost), self._nb(1), _stream())
+        return idx, cost
+
+
+def kmeans_pass(X, sel, centers, mode: int, blocks: Optional[int] = None, cost: bool = True):
+    """One fused Lloyd pass against ``centers`` ``[k, d]``.  ``mode`` 0 (STEP): the flat f64
+    statistics ``[k d sums, k counts, cost, live rows]``; 1 (ASSIGN): ``(int32 index per row, f64 row
+    cost | None)``, dead rows -1 / 0."""
+    if int(mode) not in (0, 1):
+        raise ValueError("kmeans_pass: mode must be STEP (0) or ASSIGN (1)")
+    k = int(centers.shape[0]) if hasattr(centers, "shape") and len(centers.shape) == 2 else 0
+    plan = _KMeansPlan(X, sel, k, blocks)
+    cen = _centers_dev(centers, plan.d, X.device)
+    if int(mode) == 1:
+        return plan.assign(cen, cost)
+    return plan.step(cen, torch.zeros(4, dtype=torch.float64, device=X.device))
+
+
+def kmeans_update(stats: torch.Tensor, k: int, d: int, tol: float, cen: torch.Tensor, state: torch.Tensor) -> None:
+    """Close a Lloyd iteration on the device (``kmeans_update_kernel``): ``cen`` ``[k d + k]`` and
+    ``state`` ``[iterations, done, cost, max moved^2]`` are updated in place; a no-op once done."""
+    _check_dev(stats, cen, state)
+    k, d = int(k), int(d)
+    if not (1 <= d <= 64 and 2 <= k <= 64):
+        raise ValueError("kmeans_update: needs 1 <= d <= 64 and 2 <= k <= 64")
+    if (any(t.dtype != torch.float64 or not t.is_contiguous() for t in (stats, cen, state))
+            or stats.numel() != k * d + k + 2 or cen.numel() != k * d + k or state.numel() != 4):
+        raise ValueError("kmeans_update: stats [k d + k + 2], centers [k d + k], state [4] must be contiguous f64")
+    native.hip().kmeans_update(stats.data_ptr(), k, d, float(tol), cen.data_ptr(), state.data_ptr(), _stream())
+
+
+class KMeansLoop:
+    """The enqueued Lloyd loop of one fit: device centres and ``state``, no host read inside
+    :meth:`iterate`.  In a data-parallel run the flat statistics are summed over the ranks between
+    the slab reduce and the update."""
+
+    def __init__(self, X, sel, centers, tol: float, blocks: Optional[int] = None):
+        self.plan = _KMeansPlan(X, sel, int(np.asarray(centers).shape[0]), blocks)
+        self.tol = float(tol)
+        self.cen = _centers_dev(centers, self.plan.d, X.device)
+        self.state = torch.zeros(4, dtype=torch.float64, device=X.device)
+
+    def iterate(self, n: int) -> None:
+        for _ in range(int(n)):
+            stats = comm.all_reduce_sum(self.plan.step(self.cen, self.state))
+            kmeans_update(stats, self.plan.k, self.plan.d, self.tol, self.cen, self.state)
+
+
+def kmeans_fit(X, sel, centers, max_iter: int, tol: float, batch: int, blocks: Optional[int] = None) -> dict:
+    """Lloyd iterations on the device from ``centers`` ``[k, d]``, in batches of ``batch`` with one
+    host read of the state after each.  Returns ``centers`` (host ``[k, d]``), ``iterations``,
+    ``done``, ``cost`` (the last iteration's) and ``max_moved2``."""
+    loop = KMeansLoop(X, sel, centers, tol, blocks)
+    left, batch = max(int(max_iter), 0), max(int(batch), 1)
+    st = np.zeros(4)
+    while left > 0:
+        n = min(batch, left)
+        loop.iterate(n)
+        left -= n
+        st = loop.state.cpu().numpy()
+        if st[1] != 0.0:
+            break
+    k, d = loop.plan.k, loop.plan.d
+    return {"centers": loop.cen[:k * d].cpu().numpy().reshape(k, d), "iterations": int(st[0]), "done": st[1] != 0.0,
+            "cost": float(st[2]), "max_moved2": float(st[3])}
+
+
+# ------------------------------------------------------------------------------------------
 # exact quantiles: radix select (csrc/hip/quantile.hip)
 # ------------------------------------------------------------------------------------------
 # (the relational kernels below -- quantiles, groupby, sort, join -- share the key reader of keys.h;
