@@ -14,6 +14,9 @@ from .models.feature import VectorAssembler, Imputer, ImputerModel
 from .models.regression import (LinearRegression, LinearRegressionModel,
                                 LinearRegressionTrainingSummary)
 from .models.clustering import KMeans, KMeansModel, KMeansSummary
+from .models.classification import (LogisticRegression, LogisticRegressionModel,
+                                    LogisticRegressionTrainingSummary)
+from .models.evaluation import MulticlassClassificationEvaluator
 from .models.glm import (GeneralizedLinearRegression, GeneralizedLinearRegressionModel,
                          GeneralizedLinearRegressionSummary, GeneralizedLinearRegressionTrainingSummary)
 from .models.tuning import (ParamGridBuilder, CrossValidator, CrossValidatorModel, TrainValidationSplit,
@@ -31,4 +34,6 @@ __all__ = [
     "TrainValidationSplitModel", "Imputer", "ImputerModel", "IqrRule", "Window", "WindowSpec",
     "GeneralizedLinearRegression", "GeneralizedLinearRegressionModel", "GeneralizedLinearRegressionSummary",
     "GeneralizedLinearRegressionTrainingSummary", "KMeans", "KMeansModel", "KMeansSummary",
+    "LogisticRegression", "LogisticRegressionModel", "LogisticRegressionTrainingSummary",
+    "MulticlassClassificationEvaluator",
 ]

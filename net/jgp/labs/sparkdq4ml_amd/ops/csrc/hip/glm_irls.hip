@@ -86,25 +86,6 @@ __device__ __forceinline__ double glm_project(double mu) {
   }
 }
 
-__device__ __forceinline__ double load_f32_f64(const void* p, int dt, int64_t r) {
-  return dt == DT_F64 ? reinterpret_cast<const double*>(p)[r] : (double)reinterpret_cast<const float*>(p)[r];
-}
-
-// The ragged superstep's tile: features [f0, f0 + 16) x rows [r0, r0 + 64) into xs[f][row] like
-// stage_tile (gram_slab.h), lane = row, zeros for features >= d and rows >= n.
-template <typename TX>
-__device__ __forceinline__ void stage_tile_guarded(const TX* __restrict__ X, int64_t ld, int d, int f0, int64_t r0,
-                                                   int64_t n, int lane, double* xs) {
-  const bool in = r0 + lane < n;
-#pragma unroll
-  for (int fl = 0; fl < 16; ++fl) {
-    const int feat = f0 + fl;
-    double v = 0.0;
-    if (in && feat < d) v = (double)X[(int64_t)feat * ld + r0 + lane];
-    xs[fl * kStageLd + lane] = v;
-  }
-}
-
 // a.nsuper = supersteps (ceil(n / 64)), a.spw = supersteps per wave; a.partials = [gridDim.x][P].
 // LDS: the tall f64 loop's (row scalars + one staged tile per wave), then beta[65].
 template <typename TX, int NT, int FAM, int LINK>

@@ -123,6 +123,9 @@ int gram_plan_blocks(int mode, int d, int64_t n, int xdt, int xmode);
 // later, possibly on another stream
 void gram_tall(int mode, GramArgs a, int xmode, int blocks, double* out, hipStream_t st, bool reduce = true);
 void gram_reduce(int mode, const double* partials, int blocks, int d, double* out, hipStream_t st);
+// out[i] = sum of partials[b][i] over nslab flat slabs of P doubles, in slab order, one thread per
+// statistic: the block-order sum of the kmeans.hip and logreg.hip slabs (defined in kmeans.hip)
+void slab_sum(const double* partials, int nslab, int P, double* out, hipStream_t st);
 // flat statistics of x' = x - s (GramArgs::xshift) -> those of x, in place, in f64:
 //   Σw·x = Σw·x' + s·Σw,  Σw·x·y = Σw·x'·y + s·Σw·y,
 //   Σw·xᵢ·xⱼ = Σw·x'ᵢ·x'ⱼ + sᵢ·Σw·x'ⱼ + sⱼ·Σw·x'ᵢ + sᵢ·sⱼ·Σw

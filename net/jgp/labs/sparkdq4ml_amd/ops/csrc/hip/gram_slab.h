@@ -226,6 +226,11 @@ inline void staged_f64_plan(GramArgs& a, int blocks, const char* who) {
 }
 #endif
 
+// a row operand (label, weight) that is f64 or f32
+__device__ __forceinline__ double load_f32_f64(const void* p, int dt, int64_t r) {
+  return dt == DT_F64 ? reinterpret_cast<const double*>(p)[r] : (double)reinterpret_cast<const float*>(p)[r];
+}
+
 // Cooperative load of features [f0, f0 + 16) x rows [r0, r0 + 64) of a feature-major matrix into a
 // per-wave LDS tile xs[f][row] (f64), zeros for features >= d.  Chunk c = i * 64 + lane.
 template <typename TX>
@@ -251,6 +256,49 @@ __device__ __forceinline__ void stage_tile(const TX* __restrict__ X, int64_t ld,
     double* dst = xs + fl * kStageLd + k * kPer;
 #pragma unroll
     for (int j = 0; j < kPer; j += 2) *reinterpret_cast<f64x2*>(dst + j) = f64x2{(double)v[i][j], (double)v[i][j + 1]};
+  }
+}
+
+// The ragged superstep's tile: features [f0, f0 + 16) x rows [r0, r0 + 64) into xs[f][row] like
+// stage_tile, lane = row, zeros for features >= d and rows >= n.
+template <typename TX>
+__device__ __forceinline__ void stage_tile_guarded(const TX* __restrict__ X, int64_t ld, int d, int f0, int64_t r0,
+                                                   int64_t n, int lane, double* xs) {
+  const bool in = r0 + lane < n;
+#pragma unroll
+  for (int fl = 0; fl < 16; ++fl) {
+    const int feat = f0 + fl;
+    double v = 0.0;
+    if (in && feat < d) v = (double)X[(int64_t)feat * ld + r0 + lane];
+    xs[fl * kStageLd + lane] = v;
+  }
+}
+
+// stage_tile for the kernels short of registers (kmeans.hip, logreg.hip).  f32: stage_tile.  f64:
+// the same chunks in two batches of 8 features, 4 loads in flight per lane instead of 8 -- the 16
+// registers that kmeans.hip's <double, 4, 4, STEP> otherwise spills.
+template <typename TX>
+__device__ __forceinline__ void stage_tile_batched(const TX* __restrict__ X, int64_t ld, int d, int f0, int64_t r0,
+                                                   int lane, double* xs) {
+  if constexpr (sizeof(TX) == 4) {
+    stage_tile<TX>(X, ld, d, f0, r0, lane, xs);
+  } else {
+#pragma unroll 1
+    for (int h = 0; h < 2; ++h) {
+      f64x2 v[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int c = i * 64 + lane;
+        const int feat = f0 + 8 * h + c / 32;
+        const TX* src = X + (int64_t)(feat < d ? feat : 0) * ld + r0 + (c % 32) * 2;
+        v[i] = feat < d ? __builtin_nontemporal_load(reinterpret_cast<const f64x2*>(src)) : f64x2{};
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int c = i * 64 + lane;
+        *reinterpret_cast<f64x2*>(xs + (8 * h + c / 32) * kStageLd + (c % 32) * 2) = v[i];
+      }
+    }
   }
 }
 

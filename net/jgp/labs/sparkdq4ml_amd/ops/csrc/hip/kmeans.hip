@@ -44,7 +44,7 @@
 //
 // Slabs: one partial per block, [k d sums (centre-major), k counts, cost, live rows], folded over
 // the waves in order in LDS (the loop's area, dead by then), reduced over the blocks in block order
-// by kmeans_reduce_kernel (sum_slabs_kernel of rowops.hip walks the columns serially in one block,
+// by slab_sum (gram.h; sum_slabs_kernel of rowops.hip walks the columns serially in one block,
 // which suits 8 columns, not 4162).  Plain launches, no atomics: bit-identical run to run.
 #include "kmeans.h"
 
@@ -79,49 +79,6 @@ __device__ __forceinline__ void km_take(double& b, int& bi, double s, int c) {
   if (s < b || (s == b && c < bi)) {
     b = s;
     bi = c;
-  }
-}
-
-// The ragged superstep's tile: features [f0, f0 + 16) x rows [r0, r0 + 64) into xs[f][row] like
-// stage_tile (gram_slab.h), lane = row, zeros for features >= d and rows >= n.
-template <typename TX>
-__device__ __forceinline__ void km_stage_guarded(const TX* __restrict__ X, int64_t ld, int d, int f0, int64_t r0,
-                                                 int64_t n, int lane, double* xs) {
-  const bool in = r0 + lane < n;
-#pragma unroll
-  for (int fl = 0; fl < 16; ++fl) {
-    const int feat = f0 + fl;
-    double v = 0.0;
-    if (in && feat < d) v = (double)X[(int64_t)feat * ld + r0 + lane];
-    xs[fl * kStageLd + lane] = v;
-  }
-}
-
-// A full superstep's tile.  f32: stage_tile (gram_slab.h).  f64: the same chunks in two batches of
-// 8 features, 4 loads in flight per lane instead of 8 -- the 16 registers that <double, 4, 4, STEP>
-// otherwise spills.
-template <typename TX>
-__device__ __forceinline__ void km_stage_full(const TX* __restrict__ X, int64_t ld, int d, int f0, int64_t r0, int lane,
-                                              double* xs) {
-  if constexpr (sizeof(TX) == 4) {
-    stage_tile<TX>(X, ld, d, f0, r0, lane, xs);
-  } else {
-#pragma unroll 1
-    for (int h = 0; h < 2; ++h) {
-      f64x2 v[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int c = i * 64 + lane;
-        const int feat = f0 + 8 * h + c / 32;
-        const TX* src = X + (int64_t)(feat < d ? feat : 0) * ld + r0 + (c % 32) * 2;
-        v[i] = feat < d ? __builtin_nontemporal_load(reinterpret_cast<const f64x2*>(src)) : f64x2{};
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int c = i * 64 + lane;
-        *reinterpret_cast<f64x2*>(xs + (8 * h + c / 32) * kStageLd + (c % 32) * 2) = v[i];
-      }
-    }
   }
 }
 
@@ -185,8 +142,8 @@ __global__ __launch_bounds__(kBlock) void kmeans_lloyd_f64_kernel(GramArgs a, Km
 #pragma unroll 1
     for (int t = 0; t < NT; ++t) {
       __builtin_amdgcn_wave_barrier();
-      if (s < nfull) km_stage_full<TX>(X, a.ld, d, t * 16, r0, lane, xs);
-      else km_stage_guarded<TX>(X, a.ld, d, t * 16, r0, a.n, lane, xs);
+      if (s < nfull) stage_tile_batched<TX>(X, a.ld, d, t * 16, r0, lane, xs);
+      else stage_tile_guarded<TX>(X, a.ld, d, t * 16, r0, a.n, lane, xs);
       __builtin_amdgcn_wave_barrier();
 #pragma unroll 4
       for (int j = 0; j < 16; ++j) {  // lane = row: one bank per lane
@@ -252,8 +209,8 @@ __global__ __launch_bounds__(kBlock) void kmeans_lloyd_f64_kernel(GramArgs a, Km
         const int t = NT - 1 - tt;
         if (tt > 0) {
           __builtin_amdgcn_wave_barrier();
-          if (s < nfull) km_stage_full<TX>(X, a.ld, d, t * 16, r0, lane, xs);
-          else km_stage_guarded<TX>(X, a.ld, d, t * 16, r0, a.n, lane, xs);
+          if (s < nfull) stage_tile_batched<TX>(X, a.ld, d, t * 16, r0, lane, xs);
+          else stage_tile_guarded<TX>(X, a.ld, d, t * 16, r0, a.n, lane, xs);
           __builtin_amdgcn_wave_barrier();
         }
         const f64x2* src = reinterpret_cast<const f64x2*>(xs + f * kStageLd + 16 * q);
@@ -310,16 +267,6 @@ __global__ __launch_bounds__(kBlock) void kmeans_lloyd_f64_kernel(GramArgs a, Km
     double* out = a.partials + (int64_t)blockIdx.x * P;
     for (int i = threadIdx.x; i < P; i += kBlock) out[i] = red[i];
   }
-}
-
-// fixed-order reduction over the blocks: one thread per statistic, blocks in order
-__global__ __launch_bounds__(256) void kmeans_reduce_kernel(const double* __restrict__ partials, int nslab, int P,
-                                                            double* __restrict__ out) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= P) return;
-  double s = 0.0;
-  for (int b = 0; b < nslab; ++b) s += partials[(int64_t)b * P + i];
-  out[i] = s;
 }
 
 // One block, one thread per centre.
@@ -410,11 +357,25 @@ void kmeans_pass(GramArgs a, const double* centers, int k, const double* state, 
   DQ_HIP_CHECK(hipGetLastError());
 }
 
-void kmeans_reduce(const double* partials, int blocks, int k, int d, double* stats, hipStream_t st) {
-  if (partials == nullptr || stats == nullptr || blocks < 1) throw std::invalid_argument("kmeans_reduce: bad operand");
-  const int P = kmeans_stats_size(k, d);
-  hipLaunchKernelGGL(kmeans_reduce_kernel, dim3((P + 255) / 256), dim3(256), 0, st, partials, blocks, P, stats);
+namespace {
+__global__ __launch_bounds__(256) void slab_sum_kernel(const double* __restrict__ partials, int nslab, int P,
+                                                       double* __restrict__ out) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= P) return;
+  double s = 0.0;
+  for (int b = 0; b < nslab; ++b) s += partials[(int64_t)b * P + i];
+  out[i] = s;
+}
+}  // namespace
+
+void slab_sum(const double* partials, int nslab, int P, double* out, hipStream_t st) {
+  if (partials == nullptr || out == nullptr || nslab < 1 || P < 1) throw std::invalid_argument("slab_sum: bad operand");
+  hipLaunchKernelGGL(slab_sum_kernel, dim3((P + 255) / 256), dim3(256), 0, st, partials, nslab, P, out);
   DQ_HIP_CHECK(hipGetLastError());
+}
+
+void kmeans_reduce(const double* partials, int blocks, int k, int d, double* stats, hipStream_t st) {
+  slab_sum(partials, blocks, kmeans_stats_size(k, d), stats, st);
 }
 
 void kmeans_update(const double* stats, int k, int d, double tol, double* centers, double* state, hipStream_t st) {

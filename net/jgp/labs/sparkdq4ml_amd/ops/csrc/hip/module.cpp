@@ -16,6 +16,7 @@
 #include "gram_folds.h"
 #include "glm_irls.h"
 #include "kmeans.h"
+#include "logreg.h"
 #include "quantile.h"
 #include "groupby.h"
 #include "sort.h"
@@ -263,6 +264,25 @@ PYBIND11_MODULE(_dq4ml_hip, m) {
   m.def("kmeans_update", [](uintptr_t stats, int k, int d, double tol, uintptr_t centers, uintptr_t state,
                             uintptr_t stream) {
     kmeans_update(P<const double>(stats), k, d, tol, P<double>(centers), P<double>(state), as_stream(stream));
+  });
+  // ---- logistic regression (K5l): the fused loss / gradient pass, its PREDICT mode, the slab sum --
+  m.def("logreg_blocks", &logreg_blocks);
+  m.def("logreg_stats_size", [](int K, int d) { return logreg_stats_size(K, d); });
+  m.def("logreg_pass", [](uintptr_t X, int64_t ld, int d, int64_t n, int xdt, uintptr_t y, int ydt, uintptr_t w, int wdt,
+                          uintptr_t sel, uintptr_t coef, int K, int mode, double threshold, uintptr_t partials,
+                          uintptr_t raw, uintptr_t prob, uintptr_t pred, int blocks, uintptr_t stream) {
+    GramArgs a{};
+    a.X = P<const void>(X);
+    a.ld = ld;
+    a.d = d;
+    a.n = n;
+    a.xdt = xdt;
+    set_rows(a, y, ydt, w, wdt, sel, partials);
+    logreg_pass(a, P<const double>(coef), K, mode, threshold, P<double>(raw), P<double>(prob), P<double>(pred), blocks,
+                as_stream(stream));
+  });
+  m.def("slab_sum", [](uintptr_t partials, int nslab, int width, uintptr_t out, uintptr_t stream) {
+    slab_sum(P<const double>(partials), nslab, width, P<double>(out), as_stream(stream));
   });
   m.def("quantile_blocks", &quantile_blocks);
   m.def("quantile_limits", []() { return py::make_tuple(kMaxQuantiles, kMaxQuantCols, kQuantPasses, kQuantBins); });

@@ -668,6 +668,76 @@ def kmeans_fit(X, sel, centers, max_iter: int, tol: float, batch: int, blocks: O
 
 
 # ------------------------------------------------------------------------------------------
+# logistic regression: the fused loss / gradient pass (csrc/hip/logreg.hip)
+# ------------------------------------------------------------------------------------------
+class _LogregPlan:
+    """Validated operands of the fused pass for one (X, y, w, sel, K): view, codes, grids, slabs.
+    ``K``: coefficient rows, 1 for the binomial family.  ``y`` may be None for PREDICT only."""
+
+    def __init__(self, X, y, w, sel, K: int, blocks: Optional[int] = None):
+        self.h = native.hip()
+        self.K = int(K)
+        self.Xv, self.ld, self.xdt = _staged_features(X, (y, w, sel), "logreg_pass", "1 <= d <= 64, 1 <= K <= 64 and n >= 1",
+                                                      1 <= self.K <= 64)
+        self.d, self.n = int(X.shape[0]), int(X.shape[1])
+        self.y = self.w = None
+        if y is not None:
+            self.y, self.w, _ = _prep_rows(y, w, None, self.n)
+        self.sel = _mask_u8(sel, self.n, "the selection", "logreg_pass")
+        self.blocks, self.dev = blocks, X.device
+        if blocks is not None and int(blocks) < 1:
+            raise ValueError("logreg_pass: blocks must be >= 1")
+        self.P = self.K * (self.d + 1) + 4
+        self.partials = self.stats = None
+
+    def _nb(self, mode: int) -> int:
+        return _grid(self.blocks, ("logreg", self.d, self.K, self.n, self.xdt, mode),
+                     lambda: self.h.logreg_blocks(self.d, self.K, self.n, self.xdt, mode))
+
+    def _coef(self, coef) -> torch.Tensor:
+        c = coef if torch.is_tensor(coef) else _coef_dev(coef, self.dev)
+        _check_dev(self.Xv, c)
+        if c.dtype != torch.float64 or not c.is_contiguous() or tuple(c.shape) != (self.K, self.d + 1):
+            raise ValueError("logreg_pass: coef must be contiguous f64 [K, d + 1]")
+        return c
+
+    def grad(self, coef) -> torch.Tensor:
+        """Enqueue pass + slab sum; returns this rank's statistics."""
+        if self.y is None:
+            raise ValueError("logreg_pass: a GRAD pass needs the label")
+        c, nb, st = self._coef(coef), self._nb(0), _stream()
+        if self.partials is None:
+            self.partials = torch.empty(nb * self.P, dtype=torch.float64, device=self.dev)
+            self.stats = torch.empty(self.P, dtype=torch.float64, device=self.dev)
+        self.h.logreg_pass(self.Xv.data_ptr(), int(self.ld), self.d, self.n, self.xdt, self.y.data_ptr(),
+                           dtype_code(self.y), _ptr(self.w), _wdt(self.w), _ptr(self.sel), c.data_ptr(), self.K, 0, 0.5,
+                           self.partials.data_ptr(), 0, 0, 0, nb, st)
+        self.h.slab_sum(self.partials.data_ptr(), nb, self.P, self.stats.data_ptr(), st)
+        return self.stats
+
+    def predict(self, coef, threshold: float):
+        c, classes = self._coef(coef), max(self.K, 2)
+        raw = torch.empty(classes, self.n, dtype=torch.float64, device=self.dev)
+        prob = torch.empty(classes, self.n, dtype=torch.float64, device=self.dev)
+        pred = torch.empty(self.n, dtype=torch.float64, device=self.dev)
+        self.h.logreg_pass(self.Xv.data_ptr(), int(self.ld), self.d, self.n, self.xdt, 0, 0, 0, 0, _ptr(self.sel),
+                           c.data_ptr(), self.K, 1, float(threshold), 0, raw.data_ptr(), prob.data_ptr(),
+                           pred.data_ptr(), self._nb(1), _stream())
+        return raw, prob, pred
+
+
+def logreg_pass(X, y, w, sel, coef, mode: int, blocks: Optional[int] = None, threshold: float = 0.5):
+    """One fused logistic pass against ``coef`` ``[K, d + 1]`` (K = 1: binomial).  ``mode`` 0 (GRAD):
+    the flat f64 statistics ``[K (d + 1) gradient, loss, sum w, live rows, bad labels]``; 1
+    (PREDICT): ``(raw [C, n], prob [C, n], pred [n])`` f64, dead rows NaN / -1."""
+    if int(mode) not in (0, 1):
+        raise ValueError("logreg_pass: mode must be GRAD (0) or PREDICT (1)")
+    K = int(coef.shape[0]) if hasattr(coef, "shape") and len(coef.shape) == 2 else 0
+    plan = _LogregPlan(X, y if int(mode) == 0 else None, w if int(mode) == 0 else None, sel, K, blocks)
+    return plan.grad(coef) if int(mode) == 0 else plan.predict(coef, threshold)
+
+
+# ------------------------------------------------------------------------------------------
 # exact quantiles: radix select (csrc/hip/quantile.hip)
 # ------------------------------------------------------------------------------------------
 # (the relational kernels below -- quantiles, groupby, sort, join -- share the key reader of keys.h;

@@ -11,6 +11,7 @@ Ops:
   K5  ``gram_stats``         WLS sufficient statistics (MFMA Gram) of [X | 1 | y] with weights/mask
   K5i ``glm_pass``           one IRLS pass of a generalized linear model: statistics of (x, z, w')
   K5k ``kmeans_pass``        one Lloyd pass of k-means: nearest centre per row, sums / counts / cost per centre
+  K5l ``logreg_pass``        one logistic loss / gradient evaluation (multinomial softmax or binomial), or raw / prob / pred
   K5q ``quantiles``          exact order statistics of C columns x Q probabilities (radix select)
   K5g ``group_encode`` / ``group_agg``  group ids of key columns, integer-word grouped aggregates
   K5s ``sort_permutation``   stable multi-column radix sort of the live rows (row indices)
@@ -34,7 +35,7 @@ from .window import (window_bounds, window_finish, window_heads, window_limits, 
 from .join import join_key_columns, join_limits, join_mask, join_pairs  # noqa: F401  (K5j: dispatches by device itself)
 
 __all__ = ["selected_indices", "pack_columns", "gram_stats", "predict", "regression_metrics",
-           "gram_layout_size", "glm_pass", "kmeans_pass", "gram_stats_folds", "fold_ids", "fold_thresholds", "fold_seed", "quantiles", "group_encode", "group_encode_columns",
+           "gram_layout_size", "glm_pass", "kmeans_pass", "logreg_pass", "gram_stats_folds", "fold_ids", "fold_thresholds", "fold_seed", "quantiles", "group_encode", "group_encode_columns",
            "group_agg", "group_scale", "group_limits", "sort_permutation", "sort_limits", "window_heads", "window_bounds",
            "window_prefix", "window_minmax", "window_finish", "window_limits", "join_pairs", "join_mask",
            "join_key_columns", "join_limits"]
@@ -195,6 +196,20 @@ def kmeans_pass(X: torch.Tensor, sel: Optional[torch.Tensor], centers, mode: int
     from . import kmeans
 
     return kmeans.lloyd_pass_host(X, sel, centers, mode)
+
+
+def logreg_pass(X: torch.Tensor, y, w, sel, coef, mode: int, blocks: Optional[int] = None, threshold: float = 0.5):
+    """One logistic loss / gradient pass of ``ops/logreg.py`` against ``coef`` ``[K, d + 1]`` (K = 1:
+    binomial): ``mode`` 0 (GRAD) gives the flat f64 statistics ``[K (d + 1) gradient, loss, sum w,
+    live rows, bad labels]``, 1 (PREDICT) ``(raw, prob, pred)``.  Device tensors: the fused pass
+    (d <= 64, K <= 64, f32 / f64 features); host tensors: its fp64 twin."""
+    if _on_gpu(X):
+        from . import device
+
+        return device.logreg_pass(X, y, w, sel, coef, mode, blocks, threshold)
+    from . import logreg
+
+    return logreg.logreg_pass_host(X, y, w, sel, coef, mode, threshold)
 
 
 # ------------------------------------------------------------------------------------------
