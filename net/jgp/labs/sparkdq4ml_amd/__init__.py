@@ -13,7 +13,8 @@ from .models.linalg import Vectors, DenseVector, SparseVector, Vector
 from .models.feature import VectorAssembler, Imputer, ImputerModel
 from .models.regression import (LinearRegression, LinearRegressionModel,
                                 LinearRegressionTrainingSummary)
-from .models.clustering import KMeans, KMeansModel, KMeansSummary
+from .models.clustering import (GaussianMixture, GaussianMixtureModel, GaussianMixtureSummary, KMeans,
+                                KMeansModel, KMeansSummary)
 from .models.classification import (LogisticRegression, LogisticRegressionModel,
                                     LogisticRegressionTrainingSummary)
 from .models.evaluation import MulticlassClassificationEvaluator
@@ -34,6 +35,7 @@ __all__ = [
     "TrainValidationSplitModel", "Imputer", "ImputerModel", "IqrRule", "Window", "WindowSpec",
     "GeneralizedLinearRegression", "GeneralizedLinearRegressionModel", "GeneralizedLinearRegressionSummary",
     "GeneralizedLinearRegressionTrainingSummary", "KMeans", "KMeansModel", "KMeansSummary",
+    "GaussianMixture", "GaussianMixtureModel", "GaussianMixtureSummary",
     "LogisticRegression", "LogisticRegressionModel", "LogisticRegressionTrainingSummary",
     "MulticlassClassificationEvaluator",
 ]

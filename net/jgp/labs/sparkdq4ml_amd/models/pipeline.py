@@ -16,6 +16,7 @@ _CLASS_OF = {
     "LinearRegressionModel": "org.apache.spark.ml.regression.LinearRegressionModel",
     "GeneralizedLinearRegression": "org.apache.spark.ml.regression.GeneralizedLinearRegression",
     "KMeans": "org.apache.spark.ml.clustering.KMeans",
+    "GaussianMixture": "org.apache.spark.ml.clustering.GaussianMixture",
     "LogisticRegression": "org.apache.spark.ml.classification.LogisticRegression",
     "Pipeline": "org.apache.spark.ml.Pipeline",
     "PipelineModel": "org.apache.spark.ml.PipelineModel",
@@ -25,7 +26,7 @@ _CLASS_OF = {
 def _stage_loader(cls_name: str):
     from .feature import VectorAssembler
     from .classification import LogisticRegression
-    from .clustering import KMeans
+    from .clustering import GaussianMixture, KMeans
     from .glm import GeneralizedLinearRegression
     from .regression import LinearRegression, LinearRegressionModel
 
@@ -35,6 +36,7 @@ def _stage_loader(cls_name: str):
         "org.apache.spark.ml.regression.LinearRegressionModel": LinearRegressionModel,
         "org.apache.spark.ml.regression.GeneralizedLinearRegression": GeneralizedLinearRegression,
         "org.apache.spark.ml.clustering.KMeans": KMeans,
+        "org.apache.spark.ml.clustering.GaussianMixture": GaussianMixture,
         "org.apache.spark.ml.classification.LogisticRegression": LogisticRegression,
         "org.apache.spark.ml.Pipeline": Pipeline,
         "org.apache.spark.ml.PipelineModel": PipelineModel,

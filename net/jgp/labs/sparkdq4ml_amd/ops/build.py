@@ -94,7 +94,8 @@ def _torch_lib():
 # them.  (The older kernels keep the flags they were validated and measured with.)  As logreg.hip
 # stands its arithmetic is f64 and the flag changes no instruction; it guards later edits, such as
 # an f32 softmax.
-_FILE_FLAGS = {"logreg.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+_NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+_FILE_FLAGS = {"logreg.hip": _NO_PK_F32, "gmm.hip": _NO_PK_F32}  # (gmm.hip: f64 arithmetic too)
 
 
 def _obj_stale(obj, src, headers):

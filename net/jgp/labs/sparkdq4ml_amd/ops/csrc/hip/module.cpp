@@ -15,6 +15,7 @@
 #include "gram.h"
 #include "gram_folds.h"
 #include "glm_irls.h"
+#include "gmm.h"
 #include "kmeans.h"
 #include "logreg.h"
 #include "quantile.h"
@@ -264,6 +265,27 @@ PYBIND11_MODULE(_dq4ml_hip, m) {
   m.def("kmeans_update", [](uintptr_t stats, int k, int d, double tol, uintptr_t centers, uintptr_t state,
                             uintptr_t stream) {
     kmeans_update(P<const double>(stats), k, d, tol, P<double>(centers), P<double>(state), as_stream(stream));
+  });
+  // ---- Gaussian mixture (K5m): the fused EM pass and the slab reduce ------------------------------
+  m.def("gmm_blocks", &gmm_blocks);
+  m.def("gmm_stats_size", [](int k, int d) { return gmm_stats_size(k, d); });
+  m.def("gmm_params_size", [](int k, int d) { return gmm_params_size(k, d); });
+  m.def("gmm_pass", [](uintptr_t X, int64_t ld, int d, int64_t n, int xdt, uintptr_t sel, uintptr_t params, int k,
+                       int mode, uintptr_t partials, uintptr_t assign, uintptr_t prob, uintptr_t logp, int blocks,
+                       uintptr_t stream) {
+    GramArgs a{};
+    a.X = P<const void>(X);
+    a.ld = ld;
+    a.d = d;
+    a.n = n;
+    a.xdt = xdt;
+    a.sel = P<const uint8_t>(sel);
+    a.partials = P<double>(partials);
+    gmm_pass(a, P<const double>(params), k, mode, P<int32_t>(assign), P<double>(prob), P<double>(logp), blocks,
+             as_stream(stream));
+  });
+  m.def("gmm_reduce", [](uintptr_t partials, int blocks, int k, int d, uintptr_t stats, uintptr_t stream) {
+    gmm_reduce(P<const double>(partials), blocks, k, d, P<double>(stats), as_stream(stream));
   });
   // ---- logistic regression (K5l): the fused loss / gradient pass, its PREDICT mode, the slab sum --
   m.def("logreg_blocks", &logreg_blocks);

@@ -668,6 +668,84 @@ def kmeans_fit(X, sel, centers, max_iter: int, tol: float, batch: int, blocks: O
 
 
 # ------------------------------------------------------------------------------------------
+# Gaussian mixture: the fused EM pass (csrc/hip/gmm.hip)
+# ------------------------------------------------------------------------------------------
+_GMM_NEEDS = "1 <= d <= 32, 2 <= k <= 16 (k <= 8 beyond d = 16) and n >= 1"
+
+
+class _GmmPlan:
+    """Validated operands of the fused pass for one (X, sel, k): view, codes, grids, slabs."""
+
+    def __init__(self, X, sel, k: int, blocks: Optional[int]):
+        from . import gmm
+
+        self.h = native.hip()
+        self.k = int(k)
+        d = int(X.shape[0]) if torch.is_tensor(X) and X.dim() == 2 else 0
+        self.Xv, self.ld, self.xdt = _staged_features(X, (sel,), "gmm_pass", _GMM_NEEDS, gmm.fused_range(d, self.k))
+        self.d, self.n = d, int(X.shape[1])
+        self.sel = _mask_u8(sel, self.n, "the selection", "gmm_pass")
+        self.blocks, self.dev = blocks, X.device
+        if blocks is not None and int(blocks) < 1:
+            raise ValueError("gmm_pass: blocks must be >= 1")
+        self.P = gmm.stats_size(self.k, self.d)
+        self.partials = self.stats = None
+
+    def _nb(self, mode: int) -> int:
+        return _grid(self.blocks, ("gmm", self.d, self.k, self.n, self.xdt, mode),
+                     lambda: self.h.gmm_blocks(self.d, self.k, self.n, self.xdt, mode))
+
+    def params(self, weights, means, covs) -> torch.Tensor:
+        """The device parameter buffer of the pass (built on the host: k eigendecompositions)."""
+        from . import gmm
+
+        w, mu, cov = gmm._check_params(weights, means, covs, self.d)
+        if w.size != self.k:
+            raise ValueError("gmm_pass: the parameters must be weights [k], means [k, d] and covs [k, d, d]")
+        return _h2d(gmm.params_buffer(w, mu, cov), self.dev)
+
+    def step(self, par: torch.Tensor) -> torch.Tensor:
+        """Enqueue pass + slab reduce; returns this rank's statistics."""
+        nb, st = self._nb(0), _stream()
+        if self.partials is None:
+            self.partials = torch.empty(nb * self.P, dtype=torch.float64, device=self.dev)
+            self.stats = torch.empty(self.P, dtype=torch.float64, device=self.dev)
+        self.h.gmm_pass(self.Xv.data_ptr(), int(self.ld), self.d, self.n, self.xdt, _ptr(self.sel), par.data_ptr(),
+                        self.k, 0, self.partials.data_ptr(), 0, 0, 0, nb, st)
+        self.h.gmm_reduce(self.partials.data_ptr(), nb, self.k, self.d, self.stats.data_ptr(), st)
+        return self.stats
+
+    def assign(self, par: torch.Tensor, want_logp: bool):
+        idx = torch.empty(self.n, dtype=torch.int32, device=self.dev)
+        prob = torch.empty(self.k, self.n, dtype=torch.float64, device=self.dev)
+        logp = torch.empty(self.n, dtype=torch.float64, device=self.dev) if want_logp else None
+        self.h.gmm_pass(self.Xv.data_ptr(), int(self.ld), self.d, self.n, self.xdt, _ptr(self.sel), par.data_ptr(),
+                        self.k, 1, 0, idx.data_ptr(), prob.data_ptr(), _ptr(logp), self._nb(1), _stream())
+        return idx, prob, logp
+
+
+def gmm_pass(X, sel, weights, means, covs, mode: int, blocks: Optional[int] = None, logp: bool = True):
+    """One fused EM pass against ``weights`` ``[k]``, ``means`` ``[k, d]``, ``covs`` ``[k, d, d]``.
+    ``mode`` 0 (STEP): the flat f64 statistics ``[k sw, k d sm, k d (d + 1) / 2 S, loglik, live
+    rows]``; 1 (ASSIGN): ``(int32 arg-max component per row, probabilities [k, n], log P | None)``,
+    dead rows -1 / 0 / 0."""
+    if int(mode) not in (0, 1):
+        raise ValueError("gmm_pass: mode must be STEP (0) or ASSIGN (1)")
+    plan = _GmmPlan(X, sel, int(np.asarray(weights).size), blocks)
+    par = plan.params(weights, means, covs)
+    return plan.assign(par, logp) if int(mode) == 1 else plan.step(par)
+
+
+def gmm_fit(X, sel, weights, means, covs, max_iter: int, tol: float, blocks: Optional[int] = None):
+    """EM on the device from the given start: one fused pass per iteration over one plan, the
+    statistics read by the host, whose M-step builds the next parameter buffer (``gmm.em``)."""
+    from . import gmm
+
+    plan = _GmmPlan(X, sel, int(np.asarray(weights).size), blocks)
+    return gmm.em(lambda *p: plan.step(plan.params(*p)), weights, means, covs, max_iter, tol, "fused")
+
+
+# ------------------------------------------------------------------------------------------
 # logistic regression: the fused loss / gradient pass (csrc/hip/logreg.hip)
 # ------------------------------------------------------------------------------------------
 class _LogregPlan:

@@ -11,6 +11,7 @@ Ops:
   K5  ``gram_stats``         WLS sufficient statistics (MFMA Gram) of [X | 1 | y] with weights/mask
   K5i ``glm_pass``           one IRLS pass of a generalized linear model: statistics of (x, z, w')
   K5k ``kmeans_pass``        one Lloyd pass of k-means: nearest centre per row, sums / counts / cost per centre
+  K5m ``gmm_pass``           one EM pass of a Gaussian mixture: k densities per row, responsibility-weighted moments per component
   K5l ``logreg_pass``        one logistic loss / gradient evaluation (multinomial softmax or binomial), or raw / prob / pred
   K5q ``quantiles``          exact order statistics of C columns x Q probabilities (radix select)
   K5g ``group_encode`` / ``group_agg``  group ids of key columns, integer-word grouped aggregates
@@ -35,7 +36,7 @@ from .window import (window_bounds, window_finish, window_heads, window_limits, 
 from .join import join_key_columns, join_limits, join_mask, join_pairs  # noqa: F401  (K5j: dispatches by device itself)
 
 __all__ = ["selected_indices", "pack_columns", "gram_stats", "predict", "regression_metrics",
-           "gram_layout_size", "glm_pass", "kmeans_pass", "logreg_pass", "gram_stats_folds", "fold_ids", "fold_thresholds", "fold_seed", "quantiles", "group_encode", "group_encode_columns",
+           "gram_layout_size", "glm_pass", "kmeans_pass", "gmm_pass", "logreg_pass", "gram_stats_folds", "fold_ids", "fold_thresholds", "fold_seed", "quantiles", "group_encode", "group_encode_columns",
            "group_agg", "group_scale", "group_limits", "sort_permutation", "sort_limits", "window_heads", "window_bounds",
            "window_prefix", "window_minmax", "window_finish", "window_limits", "join_pairs", "join_mask",
            "join_key_columns", "join_limits"]
@@ -196,6 +197,21 @@ def kmeans_pass(X: torch.Tensor, sel: Optional[torch.Tensor], centers, mode: int
     from . import kmeans
 
     return kmeans.lloyd_pass_host(X, sel, centers, mode)
+
+
+def gmm_pass(X: torch.Tensor, sel: Optional[torch.Tensor], weights, means, covs, mode: int, blocks: Optional[int] = None):
+    """One EM pass of ``ops/gmm.py`` against ``weights`` ``[k]``, ``means`` ``[k, d]``, ``covs``
+    ``[k, d, d]``: ``mode`` 0 (STEP) gives the flat f64 statistics ``[k sw, k d sm, k d (d + 1) / 2 S,
+    loglik, live rows]``, 1 (ASSIGN) ``(int32 arg-max component, probabilities [k, n], log P)`` per
+    row.  Device tensors: the fused pass (d <= 32, 2 <= k <= 16, k <= 8 beyond d = 16, f32 / f64
+    features); host tensors: its fp64 twin."""
+    if _on_gpu(X):
+        from . import device
+
+        return device.gmm_pass(X, sel, weights, means, covs, mode, blocks)
+    from . import gmm
+
+    return gmm.em_pass_host(X, sel, weights, means, covs, mode)
 
 
 def logreg_pass(X: torch.Tensor, y, w, sel, coef, mode: int, blocks: Optional[int] = None, threshold: float = 0.5):
