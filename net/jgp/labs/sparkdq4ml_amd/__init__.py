@@ -17,6 +17,8 @@ from .models.clustering import (GaussianMixture, GaussianMixtureModel, GaussianM
                                 KMeansModel, KMeansSummary)
 from .models.classification import (LogisticRegression, LogisticRegressionModel,
                                     LogisticRegressionTrainingSummary)
+from .models.tree import (DecisionTreeClassificationModel, DecisionTreeClassifier, DecisionTreeRegressionModel,
+                          DecisionTreeRegressor)
 from .models.evaluation import MulticlassClassificationEvaluator
 from .models.glm import (GeneralizedLinearRegression, GeneralizedLinearRegressionModel,
                          GeneralizedLinearRegressionSummary, GeneralizedLinearRegressionTrainingSummary)
@@ -37,5 +39,6 @@ __all__ = [
     "GeneralizedLinearRegressionTrainingSummary", "KMeans", "KMeansModel", "KMeansSummary",
     "GaussianMixture", "GaussianMixtureModel", "GaussianMixtureSummary",
     "LogisticRegression", "LogisticRegressionModel", "LogisticRegressionTrainingSummary",
-    "MulticlassClassificationEvaluator",
+    "MulticlassClassificationEvaluator", "DecisionTreeRegressor", "DecisionTreeRegressionModel",
+    "DecisionTreeClassifier", "DecisionTreeClassificationModel",
 ]

@@ -18,6 +18,8 @@ _CLASS_OF = {
     "KMeans": "org.apache.spark.ml.clustering.KMeans",
     "GaussianMixture": "org.apache.spark.ml.clustering.GaussianMixture",
     "LogisticRegression": "org.apache.spark.ml.classification.LogisticRegression",
+    "DecisionTreeRegressor": "org.apache.spark.ml.regression.DecisionTreeRegressor",
+    "DecisionTreeClassifier": "org.apache.spark.ml.classification.DecisionTreeClassifier",
     "Pipeline": "org.apache.spark.ml.Pipeline",
     "PipelineModel": "org.apache.spark.ml.PipelineModel",
 }
@@ -29,6 +31,7 @@ def _stage_loader(cls_name: str):
     from .clustering import GaussianMixture, KMeans
     from .glm import GeneralizedLinearRegression
     from .regression import LinearRegression, LinearRegressionModel
+    from .tree import DecisionTreeClassifier, DecisionTreeRegressor
 
     return {
         "org.apache.spark.ml.feature.VectorAssembler": VectorAssembler,
@@ -38,6 +41,8 @@ def _stage_loader(cls_name: str):
         "org.apache.spark.ml.clustering.KMeans": KMeans,
         "org.apache.spark.ml.clustering.GaussianMixture": GaussianMixture,
         "org.apache.spark.ml.classification.LogisticRegression": LogisticRegression,
+        "org.apache.spark.ml.regression.DecisionTreeRegressor": DecisionTreeRegressor,
+        "org.apache.spark.ml.classification.DecisionTreeClassifier": DecisionTreeClassifier,
         "org.apache.spark.ml.Pipeline": Pipeline,
         "org.apache.spark.ml.PipelineModel": PipelineModel,
     }[cls_name]

@@ -96,6 +96,9 @@ def _torch_lib():
 # an f32 softmax.
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 _FILE_FLAGS = {"logreg.hip": _NO_PK_F32, "gmm.hip": _NO_PK_F32}  # (gmm.hip: f64 arithmetic too)
+# tree.hip: its split search must round every f64 operation as the fp64 twin does (ops/tree.py), so
+# no multiply-add is contracted; its histogram is integer-only.
+_FILE_FLAGS["tree.hip"] = [*_NO_PK_F32, "-ffp-contract=off"]
 
 
 def _obj_stale(obj, src, headers):

@@ -23,6 +23,7 @@
 #include <stdexcept>
 
 #include "common.h"
+#include "fixed_point.h"
 #include "hashtable.h"
 #include "keys.h"
 
@@ -172,13 +173,10 @@ __global__ __launch_bounds__(kGroupThreads) void group_agg_kernel(GroupAggArgs a
             const u64 b = (u64)__double_as_longlong(x);
             const bool finite = (b & ~kSign) < kInfBits;
             const u64 flag = finite ? 0ull : ((b & ~kSign) > kInfBits ? 1ull : ((b & kSign) ? 4ull : 2ull));
-            double tt = finite ? ldexp(x, 32 - a.e[s]) : 0.0;
+            long long c[kSumLimbs];
+            cut_limbs(finite ? x : 0.0, a.e[s], c);
 #pragma unroll
-            for (int k = 0; k < kGroupSumWords - 1; ++k) {
-              const double c = trunc(tt);
-              emit(acc, a.words, on, g[j], w0 + k, GK_ADD, (u64)(long long)c, lane);
-              tt = ldexp(tt - c, 32);
-            }
+            for (int k = 0; k < kSumLimbs; ++k) emit(acc, a.words, on, g[j], w0 + k, GK_ADD, (u64)c[k], lane);
             emit(acc, a.words, on, g[j], w0 + kGroupSumWords - 1, GK_OR, flag, lane);
             break;
           }

@@ -30,6 +30,7 @@
 #include "rowops.h"
 #include "scan_host.h"
 #include "lsq.h"
+#include "tree.h"
 
 namespace py = pybind11;
 using namespace dq4ml;
@@ -286,6 +287,50 @@ PYBIND11_MODULE(_dq4ml_hip, m) {
   });
   m.def("gmm_reduce", [](uintptr_t partials, int blocks, int k, int d, uintptr_t stats, uintptr_t stream) {
     gmm_reduce(P<const double>(partials), blocks, k, d, P<double>(stats), as_stream(stream));
+  });
+  // ---- decision tree (K5t): binning, the level histogram, the split search, routing, the walk -----
+  m.def("tree_blocks", &tree_blocks);
+  m.def("tree_group", [](int kind, int d, int nb, int classes) {
+    const bool ok = d >= 1 && d <= kTreeMaxD && nb >= 1 && nb <= kTreeMaxBins &&
+                    (kind == TREE_REG || (kind == TREE_CLS && classes >= 1 && classes <= kTreeMaxClasses));
+    return ok ? tree_group(kind, d, nb, classes) : 0;
+  });
+  m.def("tree_bin", [](uintptr_t X, int64_t ld, int d, int64_t n, int xdt, uintptr_t sel, uintptr_t thr, uintptr_t nsplit,
+                       int S, int dpad, uintptr_t B, uintptr_t flag, int blocks, uintptr_t stream) {
+    tree_bin(P<const void>(X), ld, d, n, xdt, P<const uint8_t>(sel), P<const double>(thr), P<const int>(nsplit), S, dpad,
+             P<uint8_t>(B), P<int>(flag), blocks, as_stream(stream));
+  });
+  m.def("tree_hist", [](uintptr_t B, uintptr_t node, uintptr_t y, int ydt, int64_t n, int d, int dpad, int nb, int classes,
+                        int e, int g0, int G, int kind, uintptr_t H, int blocks, uintptr_t stream) {
+    TreeHistArgs a{};
+    a.B = P<const uint8_t>(B);
+    a.node = P<const int>(node);
+    a.y = P<const void>(y);
+    a.ydt = ydt;
+    a.n = n;
+    a.d = d, a.dpad = dpad, a.nb = nb, a.classes = classes, a.e = e, a.g0 = g0, a.G = G;
+    tree_hist(a, kind, P<long long>(H), blocks, as_stream(stream));
+  });
+  m.def("tree_split", [](uintptr_t H, uintptr_t nsplit, int open, int d, int nb, int classes, int kind, int impurity, int e,
+                         int64_t min_rows, double min_gain, bool force_leaf, bool child_leaf, uintptr_t rec,
+                         uintptr_t stream) {
+    TreeSplitArgs a{};
+    a.H = P<const long long>(H);
+    a.nsplit = P<const int>(nsplit);
+    a.open = open, a.d = d, a.nb = nb, a.classes = classes, a.kind = kind, a.impurity = impurity, a.e = e;
+    a.min_rows = min_rows;
+    a.min_gain = min_gain;
+    a.force_leaf = force_leaf ? 1 : 0, a.child_leaf = child_leaf ? 1 : 0;
+    tree_split(a, P<double>(rec), as_stream(stream));
+  });
+  m.def("tree_route", [](uintptr_t B, int dpad, int64_t n, uintptr_t tab, int open, uintptr_t node, int blocks,
+                         uintptr_t stream) {
+    tree_route(P<const uint8_t>(B), dpad, n, P<const int>(tab), open, P<int>(node), blocks, as_stream(stream));
+  });
+  m.def("tree_predict", [](uintptr_t X, int64_t ld, int d, int64_t n, int xdt, uintptr_t sel, uintptr_t feat, uintptr_t thr,
+                           uintptr_t left, uintptr_t right, int m_, uintptr_t leaf, int blocks, uintptr_t stream) {
+    tree_predict(P<const void>(X), ld, d, n, xdt, P<const uint8_t>(sel), P<const int>(feat), P<const double>(thr),
+                 P<const int>(left), P<const int>(right), m_, P<int>(leaf), blocks, as_stream(stream));
   });
   // ---- logistic regression (K5l): the fused loss / gradient pass, its PREDICT mode, the slab sum --
   m.def("logreg_blocks", &logreg_blocks);

@@ -820,6 +820,123 @@ def logreg_pass(X, y, w, sel, coef, mode: int, blocks: Optional[int] = None, thr
 # ------------------------------------------------------------------------------------------
 # (the relational kernels below -- quantiles, groupby, sort, join -- share the key reader of keys.h;
 # ops/keys.py is its Python statement)
+# ------------------------------------------------------------------------------------------
+# decision tree: binning, level histogram, split search, routing, prediction walk (csrc/hip/tree.hip)
+# ------------------------------------------------------------------------------------------
+def _tree_grid(h, n: int, blocks: Optional[int]) -> int:
+    if blocks is not None and int(blocks) < 1:
+        raise ValueError("tree: blocks must be >= 1")
+    return _grid(blocks, ("tree", int(n)), lambda: h.tree_blocks(int(n)))
+
+
+def _tree_i32(t, dev, who: str) -> torch.Tensor:
+    t = torch.as_tensor(t)
+    return (t if t.is_cuda else _h2d(np.asarray(t, dtype=np.int32), dev)).to(torch.int32).contiguous()
+
+
+def tree_bin(X, sel, thr, nsplit, blocks: Optional[int] = None):
+    """``(uint8 B [n, dpad], int32 flag [1])``: the bins of feature-major ``X`` against ``thr`` ``[d, S]``
+    (f64, the first ``nsplit[f]`` of a row are that feature's thresholds); the flag is nonzero when a
+    live row holds a NaN."""
+    h = native.hip()
+    Xv, ld, xdt = _staged_features(X, (sel,), "tree_bin", "1 <= d <= 64 and n >= 1")
+    d, n = int(X.shape[0]), int(X.shape[1])
+    T = np.ascontiguousarray(np.asarray(thr, dtype=np.float64)).reshape(d, -1)
+    ns = np.asarray(nsplit, dtype=np.int32).reshape(-1)
+    if ns.shape != (d,) or T.shape[1] < 1 or T.shape[1] > 255 or (ns < 0).any() or (ns > T.shape[1]).any():
+        raise ValueError("tree_bin: thresholds must be [d, S] with 1 <= S <= 255 and 0 <= nsplit <= S")
+    selv = _mask_u8(sel, n, "the selection", "tree_bin")
+    dpad = (d + 3) // 4 * 4
+    B = torch.empty(n, dpad, dtype=torch.uint8, device=X.device)
+    flag = torch.zeros(1, dtype=torch.int32, device=X.device)
+    Td, nsd = _h2d(T, X.device), _h2d(ns, X.device)
+    h.tree_bin(Xv.data_ptr(), int(ld), d, n, xdt, _ptr(selv), Td.data_ptr(), nsd.data_ptr(), int(T.shape[1]), dpad,
+               B.data_ptr(), flag.data_ptr(), _tree_grid(h, n, blocks), _stream())
+    return B, flag
+
+
+def _tree_rows(B, node, d: int, who: str):
+    _check_dev(B, node)
+    n, dpad = int(B.shape[0]), int(B.shape[1])
+    if B.dtype != torch.uint8 or not B.is_contiguous() or dpad != (int(d) + 3) // 4 * 4 or n < 1:
+        raise ValueError(f"{who}: B must be a contiguous uint8 [n, d rounded up to 4] with n >= 1")
+    if node.dtype != torch.int32 or not node.is_contiguous() or node.numel() != n:
+        raise ValueError(f"{who}: node must be a contiguous int32 [n]")
+    return n, dpad
+
+
+def tree_hist(B, node, y, kind: int, nodes: int, d: int, nb: int, classes: int, e: int, blocks: Optional[int] = None):
+    """The int64 histogram ``[nodes, d, nb, W]`` of the rows with ``0 <= node[r] < nodes``, one launch
+    per node group."""
+    h = native.hip()
+    n, dpad = _tree_rows(B, node, d, "tree_hist")
+    _check_dev(B, y)
+    if y.dtype not in (torch.float32, torch.float64) or y.numel() != n or not y.is_contiguous():
+        raise ValueError("tree_hist: labels must be a contiguous f32 / f64 [n]")
+    G = int(h.tree_group(int(kind), int(d), int(nb), int(classes)))
+    if G < 1 or int(nodes) < 1:
+        raise ValueError("tree_hist: needs at least one open node whose cells fit the block's LDS")
+    W = int(classes) if int(kind) == 1 else 9
+    H = torch.zeros(int(nodes), int(d), int(nb), W, dtype=torch.int64, device=B.device)
+    nbk, st = _tree_grid(h, n, blocks), _stream()
+    for g0 in range(0, int(nodes), G):
+        h.tree_hist(B.data_ptr(), node.data_ptr(), y.data_ptr(), dtype_code(y), n, int(d), dpad, int(nb), int(classes),
+                    int(e), g0, min(G, int(nodes) - g0), int(kind), H.data_ptr(), nbk, st)
+    return H
+
+
+def tree_split(H, nsplit, kind: int, impurity: int, e: int, min_rows: int, min_gain: float, force_leaf: bool,
+               child_leaf: bool) -> torch.Tensor:
+    """The f64 node records ``[nodes, 64]`` (csrc/hip/tree.h) of a reduced int64 histogram."""
+    _check_dev(H)
+    if H.dtype != torch.int64 or H.dim() != 4 or not H.is_contiguous():
+        raise ValueError("tree_split: the histogram must be a contiguous int64 [nodes, d, bins, words]")
+    nodes, d, nb, W = (int(v) for v in H.shape)
+    if W != (9 if int(kind) == 0 else W) or not 1 <= W <= 16:
+        raise ValueError("tree_split: 9 words per cell for regression, one per class (<= 16) otherwise")
+    nsd = _tree_i32(nsplit, H.device, "tree_split")
+    if nsd.numel() != d:
+        raise ValueError("tree_split: one split count per feature")
+    rec = torch.empty(nodes, 64, dtype=torch.float64, device=H.device)
+    native.hip().tree_split(H.data_ptr(), nsd.data_ptr(), nodes, d, nb, W, int(kind), int(impurity), int(e), int(min_rows),
+                            float(min_gain), bool(force_leaf), bool(child_leaf), rec.data_ptr(), _stream())
+    return rec
+
+
+def tree_route(B, node, tab, blocks: Optional[int] = None) -> torch.Tensor:
+    """``node`` (updated in place) after a level: ``tab`` ``[nodes, 4]`` = (feature | -1, split bin, left
+    slot, right slot) of every open node; -1 for the rows that end in a leaf."""
+    h = native.hip()
+    n, dpad = _tree_rows(B, node, int(B.shape[1]), "tree_route")
+    t = np.ascontiguousarray(np.asarray(tab, dtype=np.int32)).reshape(-1, 4)
+    if t.shape[0] < 1 or (t[:, 0] >= dpad).any():
+        raise ValueError("tree_route: the table must be [nodes, 4] with every feature inside the rows")
+    td = _h2d(t, B.device)
+    h.tree_route(B.data_ptr(), dpad, n, td.data_ptr(), int(t.shape[0]), node.data_ptr(), _tree_grid(h, n, blocks), _stream())
+    return node
+
+
+def tree_predict(X, sel, feat, thr, left, right, blocks: Optional[int] = None) -> torch.Tensor:
+    """int32 index of the leaf every live row reaches (-1 for dead rows) in the tree ``feat`` (-1:
+    leaf) / ``thr`` / ``left`` / ``right``; ``x <= thr`` goes left."""
+    h = native.hip()
+    Xv, ld, xdt = _staged_features(X, (sel,), "tree_predict", "1 <= d <= 64 and n >= 1")
+    d, n = int(X.shape[0]), int(X.shape[1])
+    f, lo, hi = (np.ascontiguousarray(np.asarray(a, dtype=np.int32)) for a in (feat, left, right))
+    t = np.ascontiguousarray(np.asarray(thr, dtype=np.float64))
+    m = int(f.size)
+    inner = f >= 0
+    if m < 1 or not (lo.size == hi.size == t.size == m) or (f >= d).any() or (
+            inner.any() and ((lo[inner] < 0).any() or (lo[inner] >= m).any() or (hi[inner] < 0).any() or (hi[inner] >= m).any())):
+        raise ValueError("tree_predict: malformed tree")
+    selv = _mask_u8(sel, n, "the selection", "tree_predict")
+    fd, ld_, rd, td = (_h2d(a, X.device) for a in (f, lo, hi, t))
+    leaf = torch.empty(n, dtype=torch.int32, device=X.device)
+    h.tree_predict(Xv.data_ptr(), int(ld), d, n, xdt, _ptr(selv), fd.data_ptr(), td.data_ptr(), ld_.data_ptr(),
+                   rd.data_ptr(), m, leaf.data_ptr(), _tree_grid(h, n, blocks), _stream())
+    return leaf
+
+
 _QUANT_DTYPES = (torch.float64, torch.float32, torch.int32, torch.int64)
 
 

@@ -13,6 +13,7 @@ Ops:
   K5k ``kmeans_pass``        one Lloyd pass of k-means: nearest centre per row, sums / counts / cost per centre
   K5m ``gmm_pass``           one EM pass of a Gaussian mixture: k densities per row, responsibility-weighted moments per component
   K5l ``logreg_pass``        one logistic loss / gradient evaluation (multinomial softmax or binomial), or raw / prob / pred
+  K5t ``tree_bin`` / ``tree_hist`` / ``tree_split`` / ``tree_route`` / ``tree_predict``  the level passes of a decision tree
   K5q ``quantiles``          exact order statistics of C columns x Q probabilities (radix select)
   K5g ``group_encode`` / ``group_agg``  group ids of key columns, integer-word grouped aggregates
   K5s ``sort_permutation``   stable multi-column radix sort of the live rows (row indices)
@@ -36,7 +37,7 @@ from .window import (window_bounds, window_finish, window_heads, window_limits, 
 from .join import join_key_columns, join_limits, join_mask, join_pairs  # noqa: F401  (K5j: dispatches by device itself)
 
 __all__ = ["selected_indices", "pack_columns", "gram_stats", "predict", "regression_metrics",
-           "gram_layout_size", "glm_pass", "kmeans_pass", "gmm_pass", "logreg_pass", "gram_stats_folds", "fold_ids", "fold_thresholds", "fold_seed", "quantiles", "group_encode", "group_encode_columns",
+           "gram_layout_size", "glm_pass", "kmeans_pass", "gmm_pass", "logreg_pass", "tree_bin", "tree_hist", "tree_split", "tree_route", "tree_predict", "gram_stats_folds", "fold_ids", "fold_thresholds", "fold_seed", "quantiles", "group_encode", "group_encode_columns",
            "group_agg", "group_scale", "group_limits", "sort_permutation", "sort_limits", "window_heads", "window_bounds",
            "window_prefix", "window_minmax", "window_finish", "window_limits", "join_pairs", "join_mask",
            "join_key_columns", "join_limits"]
@@ -226,6 +227,52 @@ def logreg_pass(X: torch.Tensor, y, w, sel, coef, mode: int, blocks: Optional[in
     from . import logreg
 
     return logreg.logreg_pass_host(X, y, w, sel, coef, mode, threshold)
+
+
+# ------------------------------------------------------------------------------------------
+# K5t -- the level passes of a decision tree (ops/tree.py): device tensors take csrc/hip/tree.hip,
+# host tensors the fp64 twins
+# ------------------------------------------------------------------------------------------
+def tree_bin(X: torch.Tensor, sel, thr, nsplit, blocks: Optional[int] = None):
+    """``(uint8 bins [n, dpad], NaN flag [1])`` of feature-major ``X`` against ``thr`` ``[d, S]``."""
+    from . import device, tree
+
+    return device.tree_bin(X, sel, thr, nsplit, blocks) if _on_gpu(X) else tree.bin_host(X, sel, thr, nsplit)
+
+
+def tree_hist(B, node, y, kind: int, nodes: int, d: int, nb: int, classes: int, e: int, blocks: Optional[int] = None):
+    """The int64 words ``[nodes, d, nb, W]`` of the rows of the open nodes."""
+    from . import device, tree
+
+    if _on_gpu(B):
+        return device.tree_hist(B, node, y, kind, nodes, d, nb, classes, e, blocks)
+    return tree.hist_host(B, node, y, kind, nodes, d, nb, classes, e)
+
+
+def tree_split(H, nsplit, kind: int, impurity: int, e: int, min_rows: int, min_gain: float, force_leaf: bool,
+               child_leaf: bool):
+    """The node records ``[nodes, 64]`` of a histogram of words (a device tensor for device words)."""
+    from . import device, tree
+
+    if _on_gpu(H):
+        return device.tree_split(H, nsplit, kind, impurity, e, min_rows, min_gain, force_leaf, child_leaf)
+    return tree.split_host(H, nsplit, kind, impurity, e, min_rows, min_gain, force_leaf, child_leaf)
+
+
+def tree_route(B, node, tab, blocks: Optional[int] = None):
+    """The next level's slot of every row from the level's ``[nodes, 4]`` table."""
+    from . import device, tree
+
+    return device.tree_route(B, node, tab, blocks) if _on_gpu(B) else tree.route_host(B, node, tab)
+
+
+def tree_predict(X: torch.Tensor, sel, feat, thr, left, right, blocks: Optional[int] = None):
+    """int32 index of the leaf each live row reaches, -1 for dead rows."""
+    from . import device, tree
+
+    if _on_gpu(X):
+        return device.tree_predict(X, sel, feat, thr, left, right, blocks)
+    return tree.predict_host(X, sel, feat, thr, left, right)
 
 
 # ------------------------------------------------------------------------------------------
