@@ -19,6 +19,8 @@ from .models.classification import (LogisticRegression, LogisticRegressionModel,
                                     LogisticRegressionTrainingSummary)
 from .models.tree import (DecisionTreeClassificationModel, DecisionTreeClassifier, DecisionTreeRegressionModel,
                           DecisionTreeRegressor)
+from .models.forest import (RandomForestClassificationModel, RandomForestClassifier, RandomForestRegressionModel,
+                            RandomForestRegressor)
 from .models.evaluation import MulticlassClassificationEvaluator
 from .models.glm import (GeneralizedLinearRegression, GeneralizedLinearRegressionModel,
                          GeneralizedLinearRegressionSummary, GeneralizedLinearRegressionTrainingSummary)
@@ -40,5 +42,6 @@ __all__ = [
     "GaussianMixture", "GaussianMixtureModel", "GaussianMixtureSummary",
     "LogisticRegression", "LogisticRegressionModel", "LogisticRegressionTrainingSummary",
     "MulticlassClassificationEvaluator", "DecisionTreeRegressor", "DecisionTreeRegressionModel",
-    "DecisionTreeClassifier", "DecisionTreeClassificationModel",
+    "DecisionTreeClassifier", "DecisionTreeClassificationModel", "RandomForestRegressor", "RandomForestRegressionModel",
+    "RandomForestClassifier", "RandomForestClassificationModel",
 ]

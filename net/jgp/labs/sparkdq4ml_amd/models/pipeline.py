@@ -20,6 +20,8 @@ _CLASS_OF = {
     "LogisticRegression": "org.apache.spark.ml.classification.LogisticRegression",
     "DecisionTreeRegressor": "org.apache.spark.ml.regression.DecisionTreeRegressor",
     "DecisionTreeClassifier": "org.apache.spark.ml.classification.DecisionTreeClassifier",
+    "RandomForestRegressor": "org.apache.spark.ml.regression.RandomForestRegressor",
+    "RandomForestClassifier": "org.apache.spark.ml.classification.RandomForestClassifier",
     "Pipeline": "org.apache.spark.ml.Pipeline",
     "PipelineModel": "org.apache.spark.ml.PipelineModel",
 }
@@ -31,6 +33,7 @@ def _stage_loader(cls_name: str):
     from .clustering import GaussianMixture, KMeans
     from .glm import GeneralizedLinearRegression
     from .regression import LinearRegression, LinearRegressionModel
+    from .forest import RandomForestClassifier, RandomForestRegressor
     from .tree import DecisionTreeClassifier, DecisionTreeRegressor
 
     return {
@@ -43,6 +46,8 @@ def _stage_loader(cls_name: str):
         "org.apache.spark.ml.classification.LogisticRegression": LogisticRegression,
         "org.apache.spark.ml.regression.DecisionTreeRegressor": DecisionTreeRegressor,
         "org.apache.spark.ml.classification.DecisionTreeClassifier": DecisionTreeClassifier,
+        "org.apache.spark.ml.regression.RandomForestRegressor": RandomForestRegressor,
+        "org.apache.spark.ml.classification.RandomForestClassifier": RandomForestClassifier,
         "org.apache.spark.ml.Pipeline": Pipeline,
         "org.apache.spark.ml.PipelineModel": PipelineModel,
     }[cls_name]

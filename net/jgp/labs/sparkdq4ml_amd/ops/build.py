@@ -99,6 +99,8 @@ _FILE_FLAGS = {"logreg.hip": _NO_PK_F32, "gmm.hip": _NO_PK_F32}  # (gmm.hip: f64
 # tree.hip: its split search must round every f64 operation as the fp64 twin does (ops/tree.py), so
 # no multiply-add is contracted; its histogram is integer-only.
 _FILE_FLAGS["tree.hip"] = [*_NO_PK_F32, "-ffp-contract=off"]
+# forest.hip: the same two reasons (its prediction sums round as the twin's in ops/forest.py)
+_FILE_FLAGS["forest.hip"] = _FILE_FLAGS["tree.hip"]
 
 
 def _obj_stale(obj, src, headers):

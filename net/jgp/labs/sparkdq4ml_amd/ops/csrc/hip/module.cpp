@@ -31,6 +31,7 @@
 #include "scan_host.h"
 #include "lsq.h"
 #include "tree.h"
+#include "forest.h"
 
 namespace py = pybind11;
 using namespace dq4ml;
@@ -331,6 +332,60 @@ PYBIND11_MODULE(_dq4ml_hip, m) {
                            uintptr_t left, uintptr_t right, int m_, uintptr_t leaf, int blocks, uintptr_t stream) {
     tree_predict(P<const void>(X), ld, d, n, xdt, P<const uint8_t>(sel), P<const int>(feat), P<const double>(thr),
                  P<const int>(left), P<const int>(right), m_, P<int>(leaf), blocks, as_stream(stream));
+  });
+  // ---- random forest (K5r): bagging, the forest histogram, the subset split search, routing, the walk --
+  m.def("forest_group", [](int kind, int m_, int nb, int classes) {
+    const bool ok = m_ >= 1 && m_ <= kTreeMaxD && nb >= 1 && nb <= kTreeMaxBins &&
+                    (kind == TREE_REG || (kind == TREE_CLS && classes >= 1 && classes <= kTreeMaxClasses));
+    return ok ? forest_group(kind, m_, nb, classes) : 0;
+  });
+  m.def("forest_bag", [](int64_t n, int64_t row_offset, uintptr_t sel, uintptr_t seeds, int trees,
+                         const std::vector<uint32_t>& thr, uintptr_t node, int blocks, uintptr_t stream) {
+    if (thr.size() > (size_t)kForestMaxCount) throw std::invalid_argument("forest_bag: at most 15 thresholds");
+    BagRule rule{};
+    rule.k = (int)thr.size();
+    for (size_t j = 0; j < thr.size(); ++j) rule.thr[j] = thr[j];
+    forest_bag(n, row_offset, P<const uint8_t>(sel), P<const uint64_t>(seeds), trees, rule, P<int>(node), blocks,
+               as_stream(stream));
+  });
+  m.def("forest_hist", [](uintptr_t B, uintptr_t node, uintptr_t y, int ydt, uintptr_t mask, int64_t n, int d, int dpad,
+                          int nb, int classes, int m_, int e, int g0, int G, int t0, int t1, int kind, uintptr_t H,
+                          int blocks, uintptr_t stream) {
+    ForestHistArgs a{};
+    a.B = P<const uint8_t>(B);
+    a.node = P<const int>(node);
+    a.y = P<const void>(y);
+    a.mask = P<const uint64_t>(mask);
+    a.ydt = ydt;
+    a.n = n;
+    a.d = d, a.dpad = dpad, a.nb = nb, a.classes = classes, a.m = m_, a.e = e;
+    a.g0 = g0, a.G = G, a.t0 = t0, a.t1 = t1;
+    forest_hist(a, kind, P<long long>(H), blocks, as_stream(stream));
+  });
+  m.def("forest_split", [](uintptr_t H, uintptr_t feats, uintptr_t nsplit, int open, int d, int m_, int nb, int classes,
+                           int kind, int impurity, int e, int64_t min_rows, double min_gain, bool force_leaf,
+                           bool child_leaf, uintptr_t rec, uintptr_t stream) {
+    TreeSplitArgs a{};
+    a.H = P<const long long>(H);
+    a.nsplit = P<const int>(nsplit);
+    a.feats = P<const int>(feats);
+    a.open = open, a.d = d, a.m = m_, a.nb = nb, a.classes = classes, a.kind = kind, a.impurity = impurity, a.e = e;
+    a.min_rows = min_rows;
+    a.min_gain = min_gain;
+    a.force_leaf = force_leaf ? 1 : 0, a.child_leaf = child_leaf ? 1 : 0;
+    if (!a.feats) throw std::invalid_argument("forest_split: null operand");
+    tree_split(a, P<double>(rec), as_stream(stream));
+  });
+  m.def("forest_route", [](uintptr_t B, int dpad, int64_t n, uintptr_t tab, int open, uintptr_t node, int trees,
+                           int blocks, uintptr_t stream) {
+    forest_route(P<const uint8_t>(B), dpad, n, P<const int>(tab), open, P<int>(node), trees, blocks, as_stream(stream));
+  });
+  m.def("forest_predict", [](uintptr_t X, int64_t ld, int d, int64_t n, int xdt, uintptr_t sel, uintptr_t feat,
+                             uintptr_t thr, uintptr_t left, uintptr_t right, int nodes, uintptr_t root, int trees,
+                             uintptr_t val, int C, uintptr_t out, int blocks, uintptr_t stream) {
+    forest_predict(P<const void>(X), ld, d, n, xdt, P<const uint8_t>(sel), P<const int>(feat), P<const double>(thr),
+                   P<const int>(left), P<const int>(right), nodes, P<const int>(root), trees, P<const double>(val), C,
+                   P<double>(out), blocks, as_stream(stream));
   });
   // ---- logistic regression (K5l): the fused loss / gradient pass, its PREDICT mode, the slab sum --
   m.def("logreg_blocks", &logreg_blocks);

@@ -42,9 +42,13 @@ struct TreeHistArgs {
 };
 
 struct TreeSplitArgs {
-  const long long* H;  // [open, d, nb, words]
+  const long long* H;  // [open, d, nb, words]; with feats: [open, m, nb, words]
   const int* nsplit;   // [d] splits of each feature (bins = splits + 1 <= nb)
   int open, d, nb, classes, kind, impurity, e;
+  // A forest's per-node feature subsets (forest.hip): feats[open, m] holds, ascending, the feature
+  // whose cells sit at each position of the node.  nullptr: all d features, position = feature.
+  const int* feats;
+  int m;
   long long min_rows;
   double min_gain;
   int force_leaf;   // the level sits at maxDepth

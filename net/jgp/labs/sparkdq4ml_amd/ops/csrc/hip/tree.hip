@@ -36,6 +36,8 @@
 // tree_split: one block per open node, one wave per feature at a time, lanes over bins.  The bin
 // prefix is an integer wave scan, so left / right words are exact; a fixed-point sum becomes a
 // double by limbs_to_f64 below, the one statement of that conversion (ops/tree.py has its twin).
+// A forest (forest.hip) hands it each node's feature subset: the search then walks the node's m
+// positions, looks the split count up by the real feature and reports that feature.
 // All f64 arithmetic of this file is compiled without contraction, so each operation rounds as
 // the twin's does.
 #include "tree.h"
@@ -218,7 +220,11 @@ __global__ __launch_bounds__(kTreeThreads) void tree_split_kernel(TreeSplitArgs 
   __shared__ Best wbest[kWaves];
   const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
   const int W = tree_words(a.kind, a.classes);
-  const i64* Hn = a.H + (int64_t)blockIdx.x * a.d * a.nb * W;
+  // positions of the node's cells: every feature, or the m features of its subset (ascending, so
+  // the (position, split) order of the search below is the (feature, split) order either way)
+  const int np = a.feats ? a.m : a.d;
+  const int* fs = a.feats ? a.feats + (int64_t)blockIdx.x * a.m : nullptr;
+  const i64* Hn = a.H + (int64_t)blockIdx.x * np * a.nb * W;
   // the node's words: the sum over the bins of feature 0 (every wave, for itself)
   i64 tot[kMaxW];
 #pragma unroll
@@ -240,8 +246,10 @@ __global__ __launch_bounds__(kTreeThreads) void tree_split_kernel(TreeSplitArgs 
   }
   const NodeStats P = node_stats(tot, a);
   Best best{0.0, -1, 0};
-  for (int f = wave; f < a.d; f += kWaves) {
-    const int ns = min(gptr<int>(a.nsplit)[f], a.nb - 1);
+  for (int f = wave; f < np; f += kWaves) {  // f: the position; best.f keeps it until the record is written
+    const int feat = fs ? gptr<int>(fs)[f] : f;
+    if (feat < 0 || feat >= a.d) continue;  // (wave-uniform; never index past nsplit)
+    const int ns = min(gptr<int>(a.nsplit)[feat], a.nb - 1);
     i64 carry[kMaxW];
 #pragma unroll
     for (int k = 0; k < kMaxW; ++k) carry[k] = 0;
@@ -286,7 +294,7 @@ __global__ __launch_bounds__(kTreeThreads) void tree_split_kernel(TreeSplitArgs 
     if (better(wbest[i].gain, wbest[i].f, wbest[i].b, best)) best = wbest[i];
   for (int i = 0; i < kTreeRecord; ++i) out[i] = 0.0;
   const bool found = best.f >= 0;
-  out[0] = found ? (double)best.f : -1.0;
+  out[0] = found ? (double)(fs ? gptr<int>(fs)[best.f] : best.f) : -1.0;
   out[3] = P.imp, out[4] = P.n, out[5] = P.pred;
   out[10] = (a.force_leaf || !found || !(best.gain > 0.0)) ? 1.0 : 0.0;
   if (a.kind == TREE_CLS)
@@ -409,6 +417,7 @@ void tree_split(const TreeSplitArgs& a, double* rec, hipStream_t st) {
     throw std::invalid_argument("tree_split: variance for regression; gini / entropy and 1 <= classes <= 16 otherwise");
   if (a.min_rows < 1) throw std::invalid_argument("tree_split: minInstancesPerNode must be >= 1");
   if (!a.H || !a.nsplit || !rec) throw std::invalid_argument("tree_split: null operand");
+  if (a.feats && (a.m < 1 || a.m > a.d)) throw std::invalid_argument("tree_split: a feature subset needs 1 <= m <= d");
   hipLaunchKernelGGL(tree_split_kernel, dim3((unsigned)a.open), dim3(kTreeThreads), 0, st, a, rec);
   DQ_HIP_CHECK(hipGetLastError());
 }

@@ -937,6 +937,143 @@ def tree_predict(X, sel, feat, thr, left, right, blocks: Optional[int] = None) -
     return leaf
 
 
+# ------------------------------------------------------------------------------------------
+# random forest: bagging, the forest histogram, the subset split search, routing, the forest walk
+# (csrc/hip/forest.hip); a node word is (bag count << 24) | slot, -1 for no slot
+# ------------------------------------------------------------------------------------------
+_FOREST_SLOTS = 1 << 24
+
+
+def _forest_words(B, node, d: int, who: str):
+    _check_dev(B, node)
+    n, dpad = int(B.shape[0]), int(B.shape[1])
+    if B.dtype != torch.uint8 or not B.is_contiguous() or dpad != (int(d) + 3) // 4 * 4 or n < 1:
+        raise ValueError(f"{who}: B must be a contiguous uint8 [n, d rounded up to 4] with n >= 1")
+    if node.dtype != torch.int32 or not node.is_contiguous() or node.dim() != 2 or node.shape[1] != n or not (
+            1 <= node.shape[0] < _FOREST_SLOTS):
+        raise ValueError(f"{who}: node must be a contiguous int32 [trees, n]")
+    return n, dpad, int(node.shape[0])
+
+
+def forest_bag(n: int, row_offset: int, sel, seeds, thr, dev, blocks: Optional[int] = None) -> torch.Tensor:
+    """int32 node words ``[trees, n]``: ``(c << 24) | t`` for the live rows with bag count ``c`` =
+    #{j : fold_hash(seeds[t], row_offset + r) >= thr[j]} >= 1, else -1."""
+    h = native.hip()
+    sd = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64)).reshape(-1)
+    th = np.asarray(thr, dtype=np.uint32).reshape(-1)
+    if int(n) < 1 or int(row_offset) < 0 or not 1 <= sd.size < _FOREST_SLOTS or th.size > 15:
+        raise ValueError("forest_bag: needs n >= 1, row_offset >= 0, 1 <= trees < 2^24 and at most 15 thresholds")
+    selv = _mask_u8(sel, int(n), "the selection", "forest_bag")
+    _check_dev(selv)
+    node = torch.empty(sd.size, int(n), dtype=torch.int32, device=dev)
+    sdd = _h2d(sd.view(np.int64), dev)
+    h.forest_bag(int(n), int(row_offset), _ptr(selv), sdd.data_ptr(), int(sd.size), [int(v) for v in th], node.data_ptr(),
+                 _tree_grid(h, int(n), blocks), _stream())
+    return node
+
+
+def forest_hist(B, node, y, kind: int, d: int, m: int, nb: int, classes: int, e: int, masks, slot_tree,
+                blocks: Optional[int] = None, group: Optional[int] = None) -> torch.Tensor:
+    """The int64 histogram ``[slots, m, nb, W]`` of a level: slot s (tree ``slot_tree[s]``, tree-major)
+    takes ``count x`` the label words of the rows whose word in that tree names it, at the features
+    of ``masks[s]`` (at most m bits below d).  One launch per slot group of at most ``group`` slots
+    (default and maximum: what the block's LDS holds)."""
+    h = native.hip()
+    n, dpad, trees = _forest_words(B, node, d, "forest_hist")
+    _check_dev(B, y)
+    if y.dtype not in (torch.float32, torch.float64) or y.numel() != n or not y.is_contiguous():
+        raise ValueError("forest_hist: labels must be a contiguous f32 / f64 [n]")
+    mk = np.ascontiguousarray(np.asarray(masks, dtype=np.uint64)).reshape(-1)
+    st_ = np.asarray(slot_tree, dtype=np.int64).reshape(-1)
+    slots = int(mk.size)
+    if not 1 <= int(m) <= int(d) <= 64:
+        raise ValueError("forest_hist: needs 1 <= m <= d <= 64")
+    bits = np.array([bin(int(v)).count("1") for v in mk])
+    if not 1 <= slots < _FOREST_SLOTS or st_.size != slots or (bits > int(m)).any() or (
+            int(d) < 64 and (mk >> np.uint64(int(d))).any()):
+        raise ValueError("forest_hist: one mask of at most m features below d, and one tree, per slot")
+    if (st_ < 0).any() or (st_ >= trees).any() or (np.diff(st_) < 0).any():
+        raise ValueError("forest_hist: slots must be numbered tree-major over the trees of node")
+    cap = int(h.forest_group(int(kind), int(m), int(nb), int(classes)))
+    G = cap if group is None else int(group)
+    if cap < 1 or not 1 <= G <= cap:
+        raise ValueError("forest_hist: needs a slot group of at least one slot that fits the block's LDS")
+    W = int(classes) if int(kind) == 1 else 9
+    H = torch.zeros(slots, int(m), int(nb), W, dtype=torch.int64, device=B.device)
+    mkd = _h2d(mk.view(np.int64), B.device)
+    nbk, st = _tree_grid(h, n, blocks), _stream()
+    for g0 in range(0, slots, G):
+        g = min(G, slots - g0)
+        h.forest_hist(B.data_ptr(), node.data_ptr(), y.data_ptr(), dtype_code(y), mkd.data_ptr(), n, int(d), dpad, int(nb),
+                      int(classes), int(m), int(e), g0, g, int(st_[g0]), int(st_[g0 + g - 1]), int(kind), H.data_ptr(), nbk, st)
+    return H
+
+
+def forest_split(H, feats, nsplit, kind: int, impurity: int, e: int, min_rows: int, min_gain: float, force_leaf: bool,
+                 child_leaf: bool) -> torch.Tensor:
+    """The f64 node records ``[slots, 64]`` of a reduced forest histogram ``[slots, m, nb, W]``; ``feats``
+    ``[slots, m]`` are each slot's features, ascending, and a record names the real feature."""
+    _check_dev(H)
+    if H.dtype != torch.int64 or H.dim() != 4 or not H.is_contiguous():
+        raise ValueError("forest_split: the histogram must be a contiguous int64 [slots, m, bins, words]")
+    slots, m, nb, W = (int(v) for v in H.shape)
+    if W != (9 if int(kind) == 0 else W) or not 1 <= W <= 16:
+        raise ValueError("forest_split: 9 words per cell for regression, one per class (<= 16) otherwise")
+    ns = np.asarray(nsplit, dtype=np.int32).reshape(-1)
+    fs = np.ascontiguousarray(np.asarray(feats, dtype=np.int32))
+    d = int(ns.size)
+    if fs.shape != (slots, m) or (fs < 0).any() or (fs >= d).any() or (np.diff(fs, axis=1) <= 0).any():
+        raise ValueError("forest_split: feats must be [slots, m] ascending feature indices below d")
+    nsd, fsd = _h2d(ns, H.device), _h2d(fs, H.device)
+    rec = torch.empty(slots, 64, dtype=torch.float64, device=H.device)
+    native.hip().forest_split(H.data_ptr(), fsd.data_ptr(), nsd.data_ptr(), slots, d, m, nb, W, int(kind), int(impurity),
+                              int(e), int(min_rows), float(min_gain), bool(force_leaf), bool(child_leaf), rec.data_ptr(),
+                              _stream())
+    return rec
+
+
+def forest_route(B, node, tab, blocks: Optional[int] = None) -> torch.Tensor:
+    """``node`` ``[trees, n]`` (updated in place) after a level: every word moves through ``tab``
+    ``[slots, 4]`` = (feature | -1, split bin, left slot, right slot) and keeps its count bits; -1
+    for the rows that end in a leaf."""
+    h = native.hip()
+    n, dpad, trees = _forest_words(B, node, int(B.shape[1]), "forest_route")
+    t = np.ascontiguousarray(np.asarray(tab, dtype=np.int32)).reshape(-1, 4)
+    if not 1 <= t.shape[0] < _FOREST_SLOTS or (t[:, 0] >= dpad).any() or (t[:, 2:] >= _FOREST_SLOTS).any():
+        raise ValueError("forest_route: the table must be [slots, 4] with every feature inside the rows and slots < 2^24")
+    td = _h2d(t, B.device)
+    h.forest_route(B.data_ptr(), dpad, n, td.data_ptr(), int(t.shape[0]), node.data_ptr(), trees, _tree_grid(h, n, blocks),
+                   _stream())
+    return node
+
+
+def forest_predict(X, sel, feat, thr, left, right, root, val, blocks: Optional[int] = None) -> torch.Tensor:
+    """f64 ``[C, n]``: per row the sum over the trees, in tree order, of ``val[leaf, :]`` (NaN for dead
+    rows).  The trees are concatenated in ``feat`` (-1: leaf) / ``thr`` / ``left`` / ``right``, ``root[t]``
+    the root of tree t, ``val`` ``[nodes, C]`` with C <= 16."""
+    h = native.hip()
+    Xv, ld, xdt = _staged_features(X, (sel,), "forest_predict", "1 <= d <= 64 and n >= 1")
+    d, n = int(X.shape[0]), int(X.shape[1])
+    f, lo, hi, rt = (np.ascontiguousarray(np.asarray(a, dtype=np.int32)).reshape(-1) for a in (feat, left, right, root))
+    t = np.ascontiguousarray(np.asarray(thr, dtype=np.float64)).reshape(-1)
+    v = np.ascontiguousarray(np.asarray(val, dtype=np.float64))
+    nodes = int(f.size)
+    inner = f >= 0
+    if nodes < 1 or not (lo.size == hi.size == t.size == nodes) or (f >= d).any() or not 1 <= rt.size < _FOREST_SLOTS or (
+            rt < 0).any() or (rt >= nodes).any() or (inner.any() and (
+                (lo[inner] < 0).any() or (lo[inner] >= nodes).any() or (hi[inner] < 0).any() or (hi[inner] >= nodes).any())):
+        raise ValueError("forest_predict: malformed forest")
+    if v.ndim != 2 or v.shape[0] != nodes or not 1 <= v.shape[1] <= 16:
+        raise ValueError("forest_predict: values must be [nodes, C] with 1 <= C <= 16")
+    selv = _mask_u8(sel, n, "the selection", "forest_predict")
+    fd, ld_, rd, rtd, td, vd = (_h2d(a, X.device) for a in (f, lo, hi, rt, t, v))
+    out = torch.empty(int(v.shape[1]), n, dtype=torch.float64, device=X.device)
+    h.forest_predict(Xv.data_ptr(), int(ld), d, n, xdt, _ptr(selv), fd.data_ptr(), td.data_ptr(), ld_.data_ptr(),
+                     rd.data_ptr(), nodes, rtd.data_ptr(), int(rt.size), vd.data_ptr(), int(v.shape[1]), out.data_ptr(),
+                     _tree_grid(h, n, blocks), _stream())
+    return out
+
+
 _QUANT_DTYPES = (torch.float64, torch.float32, torch.int32, torch.int64)
 
 

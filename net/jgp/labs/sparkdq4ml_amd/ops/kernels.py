@@ -14,6 +14,7 @@ Ops:
   K5m ``gmm_pass``           one EM pass of a Gaussian mixture: k densities per row, responsibility-weighted moments per component
   K5l ``logreg_pass``        one logistic loss / gradient evaluation (multinomial softmax or binomial), or raw / prob / pred
   K5t ``tree_bin`` / ``tree_hist`` / ``tree_split`` / ``tree_route`` / ``tree_predict``  the level passes of a decision tree
+  K5r ``forest_bag`` / ``forest_hist`` / ``forest_split`` / ``forest_route`` / ``forest_predict``  the level passes of a random forest
   K5q ``quantiles``          exact order statistics of C columns x Q probabilities (radix select)
   K5g ``group_encode`` / ``group_agg``  group ids of key columns, integer-word grouped aggregates
   K5s ``sort_permutation``   stable multi-column radix sort of the live rows (row indices)
@@ -37,7 +38,7 @@ from .window import (window_bounds, window_finish, window_heads, window_limits, 
 from .join import join_key_columns, join_limits, join_mask, join_pairs  # noqa: F401  (K5j: dispatches by device itself)
 
 __all__ = ["selected_indices", "pack_columns", "gram_stats", "predict", "regression_metrics",
-           "gram_layout_size", "glm_pass", "kmeans_pass", "gmm_pass", "logreg_pass", "tree_bin", "tree_hist", "tree_split", "tree_route", "tree_predict", "gram_stats_folds", "fold_ids", "fold_thresholds", "fold_seed", "quantiles", "group_encode", "group_encode_columns",
+           "gram_layout_size", "glm_pass", "kmeans_pass", "gmm_pass", "logreg_pass", "tree_bin", "tree_hist", "tree_split", "tree_route", "tree_predict", "forest_bag", "forest_hist", "forest_split", "forest_route", "forest_predict", "gram_stats_folds", "fold_ids", "fold_thresholds", "fold_seed", "quantiles", "group_encode", "group_encode_columns",
            "group_agg", "group_scale", "group_limits", "sort_permutation", "sort_limits", "window_heads", "window_bounds",
            "window_prefix", "window_minmax", "window_finish", "window_limits", "join_pairs", "join_mask",
            "join_key_columns", "join_limits"]
@@ -273,6 +274,56 @@ def tree_predict(X: torch.Tensor, sel, feat, thr, left, right, blocks: Optional[
     if _on_gpu(X):
         return device.tree_predict(X, sel, feat, thr, left, right, blocks)
     return tree.predict_host(X, sel, feat, thr, left, right)
+
+
+# ------------------------------------------------------------------------------------------
+# K5r -- the level passes of a random forest (ops/forest.py): device tensors take
+# csrc/hip/forest.hip, host tensors the twins
+# ------------------------------------------------------------------------------------------
+def forest_bag(n: int, row_offset: int, sel, seeds, thr, device=None, blocks: Optional[int] = None):
+    """int32 node words ``[trees, n]`` of the bagged roots: ``(count << 24) | tree`` or -1."""
+    from . import device as _device, forest
+
+    dev = torch.device(device) if device is not None else torch.device("cpu")
+    if dev.type == "cuda":
+        return _device.forest_bag(n, row_offset, sel, seeds, thr, dev, blocks)
+    return forest.bag_host(n, row_offset, sel, seeds, thr)
+
+
+def forest_hist(B, node, y, kind: int, d: int, m: int, nb: int, classes: int, e: int, masks, slot_tree,
+                blocks: Optional[int] = None, group: Optional[int] = None):
+    """The int64 words ``[slots, m, nb, W]`` of the open slots of all trees."""
+    from . import device, forest
+
+    if _on_gpu(B):
+        return device.forest_hist(B, node, y, kind, d, m, nb, classes, e, masks, slot_tree, blocks, group)
+    return forest.hist_host(B, node, y, kind, d, m, nb, classes, e, masks)
+
+
+def forest_split(H, feats, nsplit, kind: int, impurity: int, e: int, min_rows: int, min_gain: float, force_leaf: bool,
+                 child_leaf: bool):
+    """The node records ``[slots, 64]`` of a forest histogram over the per-slot features ``feats``."""
+    from . import device, forest
+
+    if _on_gpu(H):
+        return device.forest_split(H, feats, nsplit, kind, impurity, e, min_rows, min_gain, force_leaf, child_leaf)
+    return forest.split_host(H, feats, nsplit, kind, impurity, e, min_rows, min_gain, force_leaf, child_leaf)
+
+
+def forest_route(B, node, tab, blocks: Optional[int] = None):
+    """The next level's word of every (tree, row) from the level's ``[slots, 4]`` table."""
+    from . import device, forest
+
+    return device.forest_route(B, node, tab, blocks) if _on_gpu(B) else forest.route_host(B, node, tab)
+
+
+def forest_predict(X: torch.Tensor, sel, feat, thr, left, right, root, val, blocks: Optional[int] = None):
+    """f64 ``[C, n]`` sums of the trees' leaf values, NaN for dead rows."""
+    from . import device, forest
+
+    if _on_gpu(X):
+        return device.forest_predict(X, sel, feat, thr, left, right, root, val, blocks)
+    return forest.predict_host(X, sel, feat, thr, left, right, root, val)
 
 
 # ------------------------------------------------------------------------------------------
