@@ -16,7 +16,8 @@ from .models.regression import (LinearRegression, LinearRegressionModel,
 from .models.clustering import (GaussianMixture, GaussianMixtureModel, GaussianMixtureSummary, KMeans,
                                 KMeansModel, KMeansSummary)
 from .models.classification import (LogisticRegression, LogisticRegressionModel,
-                                    LogisticRegressionTrainingSummary)
+                                    LogisticRegressionTrainingSummary, MultilayerPerceptronClassificationModel,
+                                    MultilayerPerceptronClassifier)
 from .models.tree import (DecisionTreeClassificationModel, DecisionTreeClassifier, DecisionTreeRegressionModel,
                           DecisionTreeRegressor)
 from .models.forest import (RandomForestClassificationModel, RandomForestClassifier, RandomForestRegressionModel,
@@ -44,4 +45,5 @@ __all__ = [
     "MulticlassClassificationEvaluator", "DecisionTreeRegressor", "DecisionTreeRegressionModel",
     "DecisionTreeClassifier", "DecisionTreeClassificationModel", "RandomForestRegressor", "RandomForestRegressionModel",
     "RandomForestClassifier", "RandomForestClassificationModel",
+    "MultilayerPerceptronClassifier", "MultilayerPerceptronClassificationModel",
 ]

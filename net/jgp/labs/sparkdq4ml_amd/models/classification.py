@@ -1,4 +1,5 @@
-"""``org.apache.spark.ml.classification.LogisticRegression`` (Spark 2.4 semantics).
+"""``org.apache.spark.ml.classification.LogisticRegression`` and ``MultilayerPerceptronClassifier``
+(Spark 2.4 semantics).
 
 The loss / gradient evaluations, the routes and the fit are ``ops/logreg.py``'s: on the device, for
 dense f32 / f64 features with d <= 64 and at most 64 classes, one evaluation is one launch of
@@ -10,6 +11,14 @@ Not implemented, each raising an error that says so: ``thresholds``, bound const
 (``lowerBoundsOnCoefficients`` ...), persistence of the fitted model, the binary summary's ROC / PR
 curves and ``areaUnderROC``, sparse vectors in the local ``predict*`` methods (vector columns are
 dense).  ``aggregationDepth`` is accepted and ignored.
+
+``MultilayerPerceptronClassifier``: the evaluations, the routes and the fit are ``ops/mlp.py``'s: on
+the device, for one or two hidden layers with d <= 64 and widths and classes <= 32, one evaluation
+is one launch of ``csrc/hip/mlp.hip`` under Breeze's L-BFGS; other shapes take the torch composite
+and the CPU engine the fp64 twin.  Not implemented, each raising an error that says so:
+``solver="gd"``, sparse vectors, persistence of the fitted model, ``rawPredictionCol`` and
+``probabilityCol`` (Spark 3's).  ``blockSize`` is accepted and ignored: the objective is the plain
+mean over the live rows, Spark's value whenever every block is full.  ``stepSize`` belongs to ``gd``.
 """
 from __future__ import annotations
 
@@ -19,6 +28,7 @@ import numpy as np
 import torch
 
 from ..ops import logreg as L
+from ..ops import mlp as M
 from ..sql.dataframe import DataFrame
 from ..sql.expressions import Alias, ColRef, EvalContext, Expr
 from ..sql.plan import Project
@@ -30,7 +40,8 @@ from .linalg import DenseMatrix, DenseVector, SparseVector
 from .param import Param, Params, param_accessors
 from .regression import _JavaFloat, _JavaInt
 
-__all__ = ["LogisticRegression", "LogisticRegressionModel", "LogisticRegressionTrainingSummary"]
+__all__ = ["LogisticRegression", "LogisticRegressionModel", "LogisticRegressionTrainingSummary",
+           "MultilayerPerceptronClassifier", "MultilayerPerceptronClassificationModel"]
 
 _OUT_OF_SCOPE_PARAMS = ("thresholds", "lowerBoundsOnCoefficients", "upperBoundsOnCoefficients",
                         "lowerBoundsOnIntercepts", "upperBoundsOnIntercepts")
@@ -359,3 +370,185 @@ class LogisticRegressionTrainingSummary(LogisticRegressionSummary):
     def route(self) -> str:
         """Which route of ``ops/logreg.py`` ran the evaluations (engine diagnostic, not Spark's)."""
         return self._res.route
+
+
+# ---- MultilayerPerceptronClassifier ------------------------------------------------------------------
+_MLP_OUT_OF_SCOPE_PARAMS = ("rawPredictionCol", "probabilityCol")
+
+
+def _mlp_not_implemented(what: str) -> NotImplementedError:
+    return NotImplementedError(f"MultilayerPerceptronClassifier: {what} is not implemented")
+
+
+def _mlp_layers(v) -> list:
+    return [int(x) for x in v]
+
+
+def _mlp_vector(v) -> np.ndarray:
+    if isinstance(v, SparseVector):
+        raise _mlp_not_implemented("sparse vectors")
+    return np.array(v.toArray() if isinstance(v, DenseVector) else v, dtype=np.float64).reshape(-1)
+
+
+class _MLPParams(Params):
+    _params = {
+        "featuresCol": Param("featuresCol", "features column name", "features"),
+        "labelCol": Param("labelCol", "label column name", "label"),
+        "predictionCol": Param("predictionCol", "prediction column name", "prediction"),
+        "layers": Param("layers", "Sizes of layers from input layer to output layer. E.g., Array(780, 100, 10) means "
+                                  "780 inputs, one hidden layer with 100 neurons and output layer of 10 neurons.", None,
+                        lambda v: len(v) >= 2 and all(x > 0 for x in v), converter=_mlp_layers),
+        "blockSize": Param("blockSize", "Block size for stacking input data in matrices; accepted and ignored", 128,
+                           lambda v: v > 0, converter=int),
+        "solver": Param("solver", "The solver algorithm for optimization. Supported options: l-bfgs, gd.", "l-bfgs",
+                        lambda v: v in ("l-bfgs", "gd")),
+        "maxIter": Param("maxIter", "maximum number of iterations (>= 0)", 100, lambda v: v >= 0, converter=int),
+        "tol": Param("tol", "the convergence tolerance for iterative algorithms (>= 0)", 1e-6, lambda v: v >= 0,
+                     converter=float),
+        "seed": Param("seed", "random seed", -763139545, converter=int),
+        "stepSize": Param("stepSize", "Step size to be used for each iteration of optimization (> 0); solver gd only", 0.03,
+                          lambda v: v > 0, converter=float),
+        "initialWeights": Param("initialWeights", "The initial weights of the model", None, converter=_mlp_vector),
+    }
+
+    def set(self, name, value):
+        if name in _MLP_OUT_OF_SCOPE_PARAMS:
+            raise _mlp_not_implemented(name)
+        return super().set(name, value)
+
+    _set = set
+
+
+for _name in _MLP_OUT_OF_SCOPE_PARAMS:
+    setattr(_MLPParams, "set" + _name[0].upper() + _name[1:], (lambda n: lambda self, v: self.set(n, v))(_name))
+
+
+@param_accessors
+class MultilayerPerceptronClassifier(_MLPParams):
+    uid_prefix = "mlpc"
+
+    def __init__(self, uid=None, **kw):
+        super().__init__(uid)
+        for k, v in kw.items():
+            if v is not None or k in _MLP_OUT_OF_SCOPE_PARAMS:
+                self.set(k, v)
+
+    def fit(self, dataset: DataFrame, params=None) -> "MultilayerPerceptronClassificationModel":
+        est = self.copy(params) if params else self
+        return est._train(dataset)
+
+    # persistence (params only, DefaultParamsWriter layout) -----------------------------------
+    def write(self):
+        from .persistence import ParamsWriter
+
+        return ParamsWriter(self, "org.apache.spark.ml.classification.MultilayerPerceptronClassifier")
+
+    def save(self, path):
+        self.write().save(path)
+
+    @classmethod
+    def load(cls, path):
+        from .persistence import load_params_only
+
+        return load_params_only(cls, path)
+
+    def _train(self, df: DataFrame) -> "MultilayerPerceptronClassificationModel":
+        g = self.getOrDefault
+        layers, init = g("layers"), g("initialWeights")
+        if layers is None:
+            raise ValueError("MultilayerPerceptronClassifier: layers must be set")
+        if g("solver") == "gd":
+            raise _mlp_not_implemented('solver="gd"')
+        if init is not None and init.size != M.weight_count(layers):
+            raise ValueError(f"MultilayerPerceptronClassifier: initialWeights must have length {M.weight_count(layers)} "
+                             f"for layers {layers}, found {init.size}")
+        tbl, Xv, y, _, sel = _operands(self, df, True)
+        with tracing.span("mlp"):
+            res = M.fit(Xv, y, sel, layers, g("maxIter"), g("tol"), g("seed"), init)
+        tracing.add_rows("mlp", tbl.nrows)
+        model = MultilayerPerceptronClassificationModel(self.uid, layers, res.weights)
+        self.copyValues(model)
+        model._route, model._objective_history = res.route, res.objective_history
+        return model
+
+
+class MlpPredictExpr(Expr):
+    """The prediction column of a model's PREDICT pass."""
+
+    def __init__(self, features: str, layers: list, weights: np.ndarray):
+        self.features, self.layers, self.weights = features, layers, weights
+
+    def children(self):
+        return [ColRef(self.features)]
+
+    def data_type(self, schema):
+        return DoubleType()
+
+    def sql_name(self):
+        return "prediction"
+
+    def eval(self, ctx: EvalContext) -> ColumnData:
+        X = ctx.table.column(self.features)
+        with tracing.span("mlp_predict"):
+            pred = M.predict(_dense_features(X), X.valid, self.weights, self.layers)
+        return ColumnData(DoubleType(), pred, X.valid, checks=list(X.checks))
+
+
+@param_accessors
+class MultilayerPerceptronClassificationModel(_MLPParams):
+    """A Spark 2.4 ``PredictionModel``: the prediction column only."""
+    uid_prefix = "mlpc"
+
+    def __init__(self, uid: Optional[str], layers, weights):
+        super().__init__(uid)
+        self._layers = _mlp_layers(layers)
+        self._weights = _mlp_vector(weights)
+        if self._weights.size != M.weight_count(self._layers):
+            raise ValueError(f"MultilayerPerceptronClassificationModel: weights must have length "
+                             f"{M.weight_count(self._layers)} for layers {self._layers}")
+        self._route, self._objective_history = None, []
+
+    @property
+    def layers(self):
+        return list(self._layers)
+
+    @property
+    def weights(self):
+        return DenseVector(self._weights)
+
+    @property
+    def numFeatures(self):
+        return _JavaInt(self._layers[0])
+
+    @property
+    def route(self) -> Optional[str]:
+        """Which route of ``ops/mlp.py`` ran the fit's evaluations (engine diagnostic, not Spark's)."""
+        return self._route
+
+    def predict(self, features) -> float:
+        v = _mlp_vector(features)
+        return _JavaFloat(float(M.mlp_pass_host(v.reshape(-1, 1), None, None, self._weights, self._layers, M.PREDICT)[0]))
+
+    def transform(self, df: DataFrame) -> DataFrame:
+        fc, pc = self.getOrDefault("featuresCol"), self.getOrDefault("predictionCol")
+        ColRef(fc).data_type(df.schema)
+        exprs = [ColRef(n) for n in df.columns if n != pc] + [Alias(MlpPredictExpr(fc, self._layers, self._weights), pc)]
+        return DataFrame(Project(df._plan, exprs), df.sparkSession)
+
+    # persistence: out of scope ---------------------------------------------------------------
+    def write(self):
+        raise _mlp_not_implemented("persistence of the fitted model")
+
+    def save(self, path):
+        self.write()
+
+    @classmethod
+    def read(cls):
+        raise _mlp_not_implemented("persistence of the fitted model")
+
+    @classmethod
+    def load(cls, path):
+        cls.read()
+
+    def __repr__(self):
+        return f"MultilayerPerceptronClassificationModel: uid = {self.uid}, layers = {self._layers}"

@@ -18,6 +18,7 @@
 #include "gmm.h"
 #include "kmeans.h"
 #include "logreg.h"
+#include "mlp.h"
 #include "quantile.h"
 #include "groupby.h"
 #include "sort.h"
@@ -402,6 +403,24 @@ PYBIND11_MODULE(_dq4ml_hip, m) {
     set_rows(a, y, ydt, w, wdt, sel, partials);
     logreg_pass(a, P<const double>(coef), K, mode, threshold, P<double>(raw), P<double>(prob), P<double>(pred), blocks,
                 as_stream(stream));
+  });
+  // ---- multilayer perceptron (K5p): the fused forward / backward pass and its PREDICT mode ---------
+  m.def("mlp_blocks", [](const std::vector<int>& layers, int64_t n, int xdt, int mode) {
+    return mlp_blocks(layers.data(), (int)layers.size(), n, xdt, mode);
+  });
+  m.def("mlp_stats_size", [](const std::vector<int>& layers) { return mlp_stats_size(layers.data(), (int)layers.size()); });
+  m.def("mlp_pass", [](uintptr_t X, int64_t ld, int d, int64_t n, int xdt, uintptr_t y, int ydt, uintptr_t sel,
+                       uintptr_t weights, const std::vector<int>& layers, int mode, uintptr_t partials, uintptr_t pred,
+                       int blocks, uintptr_t stream) {
+    GramArgs a{};
+    a.X = P<const void>(X);
+    a.ld = ld;
+    a.d = d;
+    a.n = n;
+    a.xdt = xdt;
+    set_rows(a, y, ydt, 0, 0, sel, partials);
+    mlp_pass(a, P<const double>(weights), layers.data(), (int)layers.size(), mode, P<double>(pred), blocks,
+             as_stream(stream));
   });
   m.def("slab_sum", [](uintptr_t partials, int nslab, int width, uintptr_t out, uintptr_t stream) {
     slab_sum(P<const double>(partials), nslab, width, P<double>(out), as_stream(stream));

@@ -816,6 +816,76 @@ def logreg_pass(X, y, w, sel, coef, mode: int, blocks: Optional[int] = None, thr
 
 
 # ------------------------------------------------------------------------------------------
+# multilayer perceptron: the fused forward / backward pass (csrc/hip/mlp.hip)
+# ------------------------------------------------------------------------------------------
+class _MlpPlan:
+    """Validated operands of the fused pass for one (X, y, sel, layers): view, codes, grids, slabs.
+    ``y`` may be None for PREDICT only."""
+
+    def __init__(self, X, y, sel, layers, blocks: Optional[int] = None):
+        from . import mlp
+
+        self.h = native.hip()
+        self.layers = [int(v) for v in layers]
+        d = int(X.shape[0]) if torch.is_tensor(X) and X.dim() == 2 else 0
+        self.Xv, self.ld, self.xdt = _staged_features(
+            X, (y, sel), "mlp_pass", "layers = [d, one or two hidden widths, K] with d = X.shape[0] <= 64, hidden "
+            "widths <= 32, 2 <= K <= 32, and n >= 1", mlp.fused_range(self.layers) and self.layers[0] == d)
+        self.d, self.n = d, int(X.shape[1])
+        self.y = None
+        if y is not None:
+            self.y, _, _ = _prep_rows(y, None, None, self.n)
+        self.sel = _mask_u8(sel, self.n, "the selection", "mlp_pass")
+        self.blocks, self.dev = blocks, X.device
+        if blocks is not None and int(blocks) < 1:
+            raise ValueError("mlp_pass: blocks must be >= 1")
+        self.P = mlp.weight_count(self.layers)
+        self.partials = self.stats = None
+
+    def _nb(self, mode: int) -> int:
+        return _grid(self.blocks, ("mlp", tuple(self.layers), self.n, self.xdt, mode),
+                     lambda: self.h.mlp_blocks(self.layers, self.n, self.xdt, mode))
+
+    def _weights(self, weights) -> torch.Tensor:
+        w = weights if torch.is_tensor(weights) else _coef_dev(weights, self.dev)
+        _check_dev(self.Xv, w)
+        if w.dtype != torch.float64 or not w.is_contiguous() or w.dim() != 1 or w.numel() != self.P:
+            raise ValueError(f"mlp_pass: weights must be contiguous f64 of length {self.P}")
+        return w
+
+    def grad(self, weights) -> torch.Tensor:
+        """Enqueue pass + slab sum; returns this rank's statistics."""
+        if self.y is None:
+            raise ValueError("mlp_pass: a GRAD pass needs the label")
+        w, nb, st = self._weights(weights), self._nb(0), _stream()
+        if self.partials is None:
+            self.partials = torch.empty(nb * (self.P + 3), dtype=torch.float64, device=self.dev)
+            self.stats = torch.empty(self.P + 3, dtype=torch.float64, device=self.dev)
+        self.h.mlp_pass(self.Xv.data_ptr(), int(self.ld), self.d, self.n, self.xdt, self.y.data_ptr(),
+                        dtype_code(self.y), _ptr(self.sel), w.data_ptr(), self.layers, 0, self.partials.data_ptr(), 0,
+                        nb, st)
+        self.h.slab_sum(self.partials.data_ptr(), nb, self.P + 3, self.stats.data_ptr(), st)
+        return self.stats
+
+    def predict(self, weights) -> torch.Tensor:
+        w = self._weights(weights)
+        pred = torch.empty(self.n, dtype=torch.float64, device=self.dev)
+        self.h.mlp_pass(self.Xv.data_ptr(), int(self.ld), self.d, self.n, self.xdt, 0, 0, _ptr(self.sel), w.data_ptr(),
+                        self.layers, 1, 0, pred.data_ptr(), self._nb(1), _stream())
+        return pred
+
+
+def mlp_pass(X, y, sel, weights, layers, mode: int, blocks: Optional[int] = None):
+    """One fused perceptron pass against the flat ``weights`` of ``layers``.  ``mode`` 0 (GRAD): the
+    flat f64 statistics ``[P gradient, loss, live rows, bad labels]``; 1 (PREDICT): ``pred [n]`` f64,
+    dead rows -1."""
+    if int(mode) not in (0, 1):
+        raise ValueError("mlp_pass: mode must be GRAD (0) or PREDICT (1)")
+    plan = _MlpPlan(X, y if int(mode) == 0 else None, sel, layers, blocks)
+    return plan.grad(weights) if int(mode) == 0 else plan.predict(weights)
+
+
+# ------------------------------------------------------------------------------------------
 # exact quantiles: radix select (csrc/hip/quantile.hip)
 # ------------------------------------------------------------------------------------------
 # (the relational kernels below -- quantiles, groupby, sort, join -- share the key reader of keys.h;

@@ -13,6 +13,7 @@ Ops:
   K5k ``kmeans_pass``        one Lloyd pass of k-means: nearest centre per row, sums / counts / cost per centre
   K5m ``gmm_pass``           one EM pass of a Gaussian mixture: k densities per row, responsibility-weighted moments per component
   K5l ``logreg_pass``        one logistic loss / gradient evaluation (multinomial softmax or binomial), or raw / prob / pred
+  K5p ``mlp_pass``           one loss / gradient evaluation of a small dense network (sigmoid hidden layers, softmax on top), or pred
   K5t ``tree_bin`` / ``tree_hist`` / ``tree_split`` / ``tree_route`` / ``tree_predict``  the level passes of a decision tree
   K5r ``forest_bag`` / ``forest_hist`` / ``forest_split`` / ``forest_route`` / ``forest_predict``  the level passes of a random forest
   K5q ``quantiles``          exact order statistics of C columns x Q probabilities (radix select)
@@ -38,7 +39,7 @@ from .window import (window_bounds, window_finish, window_heads, window_limits, 
 from .join import join_key_columns, join_limits, join_mask, join_pairs  # noqa: F401  (K5j: dispatches by device itself)
 
 __all__ = ["selected_indices", "pack_columns", "gram_stats", "predict", "regression_metrics",
-           "gram_layout_size", "glm_pass", "kmeans_pass", "gmm_pass", "logreg_pass", "tree_bin", "tree_hist", "tree_split", "tree_route", "tree_predict", "forest_bag", "forest_hist", "forest_split", "forest_route", "forest_predict", "gram_stats_folds", "fold_ids", "fold_thresholds", "fold_seed", "quantiles", "group_encode", "group_encode_columns",
+           "gram_layout_size", "glm_pass", "kmeans_pass", "gmm_pass", "logreg_pass", "mlp_pass", "tree_bin", "tree_hist", "tree_split", "tree_route", "tree_predict", "forest_bag", "forest_hist", "forest_split", "forest_route", "forest_predict", "gram_stats_folds", "fold_ids", "fold_thresholds", "fold_seed", "quantiles", "group_encode", "group_encode_columns",
            "group_agg", "group_scale", "group_limits", "sort_permutation", "sort_limits", "window_heads", "window_bounds",
            "window_prefix", "window_minmax", "window_finish", "window_limits", "join_pairs", "join_mask",
            "join_key_columns", "join_limits"]
@@ -228,6 +229,20 @@ def logreg_pass(X: torch.Tensor, y, w, sel, coef, mode: int, blocks: Optional[in
     from . import logreg
 
     return logreg.logreg_pass_host(X, y, w, sel, coef, mode, threshold)
+
+
+def mlp_pass(X: torch.Tensor, y, sel, weights, layers, mode: int, blocks: Optional[int] = None):
+    """One multilayer-perceptron pass of ``ops/mlp.py`` against the flat ``weights`` (Spark's layout)
+    of ``layers``: ``mode`` 0 (GRAD) gives the flat f64 statistics ``[P gradient, loss, live rows, bad
+    labels]``, 1 (PREDICT) ``pred [n]``.  Device tensors: the fused pass (one or two hidden layers,
+    d <= 64, widths and K <= 32, f32 / f64 features); host tensors: its fp64 twin."""
+    if _on_gpu(X):
+        from . import device
+
+        return device.mlp_pass(X, y, sel, weights, layers, mode, blocks)
+    from . import mlp
+
+    return mlp.mlp_pass_host(X, y, sel, weights, layers, mode)
 
 
 # ------------------------------------------------------------------------------------------
