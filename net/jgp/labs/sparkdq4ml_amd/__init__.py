@@ -22,6 +22,7 @@ from .models.tree import (DecisionTreeClassificationModel, DecisionTreeClassifie
                           DecisionTreeRegressor)
 from .models.forest import (RandomForestClassificationModel, RandomForestClassifier, RandomForestRegressionModel,
                             RandomForestRegressor)
+from .models.recommendation import ALS, ALSModel
 from .models.evaluation import MulticlassClassificationEvaluator
 from .models.glm import (GeneralizedLinearRegression, GeneralizedLinearRegressionModel,
                          GeneralizedLinearRegressionSummary, GeneralizedLinearRegressionTrainingSummary)
@@ -45,5 +46,5 @@ __all__ = [
     "MulticlassClassificationEvaluator", "DecisionTreeRegressor", "DecisionTreeRegressionModel",
     "DecisionTreeClassifier", "DecisionTreeClassificationModel", "RandomForestRegressor", "RandomForestRegressionModel",
     "RandomForestClassifier", "RandomForestClassificationModel",
-    "MultilayerPerceptronClassifier", "MultilayerPerceptronClassificationModel",
+    "MultilayerPerceptronClassifier", "MultilayerPerceptronClassificationModel", "ALS", "ALSModel",
 ]

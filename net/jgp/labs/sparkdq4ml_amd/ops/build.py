@@ -95,7 +95,8 @@ def _torch_lib():
 # stands its arithmetic is f64 and the flag changes no instruction; it guards later edits, such as
 # an f32 softmax.
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-_FILE_FLAGS = {"logreg.hip": _NO_PK_F32, "gmm.hip": _NO_PK_F32, "mlp.hip": _NO_PK_F32}  # (gmm.hip, mlp.hip: f64 arithmetic too)
+_FILE_FLAGS = {"logreg.hip": _NO_PK_F32, "gmm.hip": _NO_PK_F32, "mlp.hip": _NO_PK_F32,  # (gmm.hip, mlp.hip, als.hip:
+               "als.hip": _NO_PK_F32}                                                    # f64 arithmetic too)
 # tree.hip: its split search must round every f64 operation as the fp64 twin does (ops/tree.py), so
 # no multiply-add is contracted; its histogram is integer-only.
 _FILE_FLAGS["tree.hip"] = [*_NO_PK_F32, "-ffp-contract=off"]

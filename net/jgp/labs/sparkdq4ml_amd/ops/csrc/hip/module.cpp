@@ -9,6 +9,7 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include "als.h"
 #include "common.h"
 #include "csv_scan.h"
 #include "dqvm.h"
@@ -421,6 +422,31 @@ PYBIND11_MODULE(_dq4ml_hip, m) {
     set_rows(a, y, ydt, 0, 0, sel, partials);
     mlp_pass(a, P<const double>(weights), layers.data(), (int)layers.size(), mode, P<double>(pred), blocks,
              as_stream(stream));
+  });
+  // ---- alternating least squares (K5a): the chunk table, the fused half-step, the prediction pass ---
+  m.def("als_limits", []() { return py::make_tuple(kAlsMinRank, kAlsMaxRank, kAlsChunk); });
+  m.def("als_system_size", &als_system_size);
+  m.def("als_blocks", &als_blocks);
+  m.def("als_chunk_counts", [](uintptr_t offsets, int64_t D, int chunk, uintptr_t cstart, uintptr_t stream) {
+    als_chunk_counts(P<const int64_t>(offsets), D, chunk, P<int64_t>(cstart), as_stream(stream));
+  });
+  m.def("als_chunk_fill", [](uintptr_t cstart, int64_t D, uintptr_t chunk_dst, uintptr_t stream) {
+    als_chunk_fill(P<const int64_t>(cstart), D, P<int>(chunk_dst), as_stream(stream));
+  });
+  m.def("als_half_step", [](uintptr_t offsets, uintptr_t src, uintptr_t rating, uintptr_t cstart, uintptr_t chunk_dst,
+                            uintptr_t slab_of, uintptr_t long_dst, int64_t D, int64_t nchunks, int64_t nlong, int chunk,
+                            uintptr_t src_f, uintptr_t dst_f, int fdt, int64_t S, int rank, double reg, uintptr_t slab,
+                            uintptr_t status, uintptr_t presolve, int blocks, uintptr_t stream) {
+    AlsTable t{P<const int64_t>(offsets), P<const int>(src),          P<const double>(rating), P<const int64_t>(cstart),
+               P<const int>(chunk_dst),   P<const int64_t>(slab_of),  P<const int>(long_dst),  D,
+               nchunks,                   nlong,                      chunk};
+    als_half_step(t, P<const void>(src_f), P<void>(dst_f), fdt, S, rank, reg, P<double>(slab), P<unsigned>(status),
+                  P<double>(presolve), blocks, as_stream(stream));
+  });
+  m.def("als_predict", [](uintptr_t u, uintptr_t v, uintptr_t sel, int64_t n, uintptr_t U, uintptr_t V, int fdt, int rank,
+                          uintptr_t out, uintptr_t stream) {
+    als_predict(P<const int>(u), P<const int>(v), P<const uint8_t>(sel), n, P<const void>(U), P<const void>(V), fdt, rank,
+                P<double>(out), as_stream(stream));
   });
   m.def("slab_sum", [](uintptr_t partials, int nslab, int width, uintptr_t out, uintptr_t stream) {
     slab_sum(P<const double>(partials), nslab, width, P<double>(out), as_stream(stream));

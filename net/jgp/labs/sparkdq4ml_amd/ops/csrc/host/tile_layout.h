@@ -114,6 +114,18 @@ static_assert(elem_offset(kWide, 5, frag_row(kWide, 2, 3, 1, 7), 8) * 2 == frag_
 static_assert(elem_offset(kWideFp8, 5, frag_row(kWideFp8, 2, 1, 1, 15), 8) == frag_byte(kWideFp8, 16, 1, 37) + 15,
               "fp8 inverse");
 
+// ---- the f64 fragments of v_mfma_f64_16x16x4f64 ------------------------------------------------
+// One step multiplies a 16 x 4 A by a 4 x 16 B into a 16 x 16 D.  Lane l holds A[i][k] and B[k][j]
+// with i = j = f64_col(l) and k = f64_k(l), and D[f64_acc_row(reg, l)][f64_col(l)] in accumulator
+// register reg = 0..3.  For a symmetric product Y^T Y (k = the contracted row of Y) one register,
+// Y[k][16 t + f64_col(l)], is both the A operand of tile row t and the B operand of tile column t.
+constexpr int kF64Tile = 16;  // rows and columns of a D tile
+constexpr int kF64K = 4;      // contracted entries per step
+DQ_TL_FN int f64_col(int lane) { return lane & 15; }
+DQ_TL_FN int f64_k(int lane) { return lane >> 4; }
+DQ_TL_FN int f64_acc_row(int reg, int lane) { return 4 * reg + (lane >> 4); }
+static_assert(f64_col(63) == 15 && f64_k(63) == kF64K - 1 && f64_acc_row(3, 63) == kF64Tile - 1, "f64 fragment");
+
 #if defined(__HIPCC__)
 // ---- device side: fragments and runs as f32 -------------------------------------------------
 __device__ __forceinline__ void fp8x8_to_f32(unsigned lo, unsigned hi, float x[8]) {

@@ -886,6 +886,138 @@ def mlp_pass(X, y, sel, weights, layers, mode: int, blocks: Optional[int] = None
 
 
 # ------------------------------------------------------------------------------------------
+# alternating least squares: the fused half-step (csrc/hip/als.hip)
+# ------------------------------------------------------------------------------------------
+class _AlsSide:
+    """Validated segment table of one side with its chunk table and slab.  Built once (the
+    validation and the chunk count read the device); a half-step then only launches."""
+
+    def __init__(self, h, seg, rank: int, chunk: int):
+        off, src, rating = seg.offsets, seg.src, seg.rating
+        _check_dev(off, src, rating)
+        D, S, nnz = int(seg.D), int(seg.S), int(src.numel())
+        if (off.dtype != torch.int64 or src.dtype != torch.int32 or rating.dtype != torch.float64 or off.dim() != 1
+                or int(off.numel()) != D + 1 or src.dim() != 1 or tuple(rating.shape) != (nnz,)
+                or not (off.is_contiguous() and src.is_contiguous() and rating.is_contiguous())):
+            raise ValueError("als_half_step: offsets int64 [D + 1], src int32 [nnz], rating f64 [nnz], all contiguous")
+        if D < 1 or S < 1 or max(D, S, nnz) >= 1 << 31:
+            raise ValueError("als_half_step: between 1 and 2^31 - 1 destinations and sources, fewer than 2^31 ratings")
+        steps = off[1:] - off[:-1]
+        if int(off[0]) != 0 or int(off[-1]) != nnz or bool((steps < 0).any()):
+            raise ValueError("als_half_step: offsets must rise from 0 to the number of ratings")
+        if nnz and (int(src.min()) < 0 or int(src.max()) >= S):
+            raise ValueError("als_half_step: a source index lies outside [0, S)")
+        self.seg, self.D, self.S, self.chunk = seg, D, S, int(chunk)
+        dev, st = off.device, _stream()
+        self.cstart = torch.empty(D + 1, dtype=torch.int64, device=dev)
+        h.als_chunk_counts(off.data_ptr(), D, self.chunk, self.cstart.data_ptr(), st)
+        h.scan_counts(self.cstart.data_ptr(), D, st)
+        nch = self.cstart[1:] - self.cstart[:-1]
+        long = nch > 1
+        lrows = torch.where(long, nch, torch.zeros_like(nch))
+        self.slab_of = torch.where(long, torch.cumsum(lrows, 0) - lrows, torch.full_like(nch, -1)).contiguous()
+        self.long_dst = torch.nonzero(long).flatten().to(torch.int32).contiguous()
+        self.nchunks, self.nlong, rows = int(self.cstart[D]), int(self.long_dst.numel()), int(lrows.sum())
+        self.chunk_dst = torch.empty(self.nchunks, dtype=torch.int32, device=dev)
+        h.als_chunk_fill(self.cstart.data_ptr(), D, self.chunk_dst.data_ptr(), st)
+        self.slab = torch.empty(rows * h.als_system_size(rank), dtype=torch.float64, device=dev) if rows else None
+
+
+class _AlsPlan:
+    """The operands of a fit's half-steps: both sides' tables, the status words, the grids.
+    ``by_item`` solves the items from the users, ``by_user`` the users from the items (either may
+    be None for a single half-step)."""
+
+    def __init__(self, by_item, by_user, rank: int, reg: float, dtype, chunk: Optional[int] = None,
+                 blocks: Optional[int] = None):
+        from . import als
+
+        self.h = native.hip()
+        self.rank, self.reg = int(rank), float(reg)
+        if not als.RANK_MIN <= self.rank <= als.RANK_MAX:
+            raise ValueError(f"als_half_step: the device pass takes {als.RANK_MIN} <= rank <= {als.RANK_MAX}, got {self.rank}")
+        if dtype not in (torch.float32, torch.float64):
+            raise TypeError("als_half_step: factors must be f32 or f64")
+        if not self.reg >= 0.0:
+            raise ValueError("als_half_step: regParam must be >= 0")
+        self.chunk = als.CHUNK if chunk is None else int(chunk)
+        if self.chunk < 64 or self.chunk % 64:
+            raise ValueError("als_half_step: chunk must be a positive multiple of 64")
+        if blocks is not None and int(blocks) < 1:
+            raise ValueError("als_half_step: blocks must be >= 1")
+        self.dtype, self.fdt, self.blocks = dtype, _DT[dtype], blocks
+        self.sides = [None if s is None else _AlsSide(self.h, s, self.rank, self.chunk) for s in (by_item, by_user)]
+        self.dev = next(s for s in self.sides if s is not None).seg.offsets.device
+        self.status = torch.zeros(2, dtype=torch.int32, device=self.dev)
+
+    def _factors(self, t, rows: int) -> torch.Tensor:
+        _check_dev(self.status, t)
+        if t.dtype != self.dtype or not t.is_contiguous() or tuple(t.shape) != (rows, self.rank):
+            raise ValueError(f"als_half_step: factors must be contiguous {self.dtype} [{rows}, {self.rank}]")
+        return t
+
+    def half(self, which: int, Y: torch.Tensor, X: torch.Tensor, presolve: Optional[torch.Tensor] = None) -> None:
+        """Enqueue side ``which`` (0: items from users, 1: users from items): X from Y."""
+        s = self.sides[which]
+        Y, X = self._factors(Y, s.S), self._factors(X, s.D)
+        nb = _grid(self.blocks, ("als", self.rank, self.fdt, s.nchunks),
+                   lambda: self.h.als_blocks(self.rank, self.fdt, s.nchunks))
+        seg = s.seg
+        self.h.als_half_step(seg.offsets.data_ptr(), seg.src.data_ptr(), seg.rating.data_ptr(), s.cstart.data_ptr(),
+                             s.chunk_dst.data_ptr(), s.slab_of.data_ptr(), s.long_dst.data_ptr(), s.D, s.nchunks, s.nlong,
+                             s.chunk, Y.data_ptr(), X.data_ptr(), self.fdt, s.S, self.rank, self.reg, _ptr(s.slab),
+                             self.status.data_ptr(), _ptr(presolve), nb, _stream())
+
+    def run(self, U0: np.ndarray, V0: np.ndarray, iters: int):
+        """All iterations enqueued, then the one host read: ``(U, V, failed systems)``."""
+        U, V = (torch.from_numpy(np.ascontiguousarray(a)).to(self.dtype).to(self.dev) for a in (U0, V0))
+        for _ in range(int(iters)):
+            self.half(0, U, V)
+            self.half(1, V, U)
+        st = self.status.cpu()
+        if int(st[1]):
+            raise RuntimeError(f"als_half_step: {int(st[1])} source indices outside the factor table")
+        return U.cpu().numpy(), V.cpu().numpy(), int(st[0])
+
+
+def als_half_step(offsets, src, rating, Y, reg: float, chunk: Optional[int] = None, blocks: Optional[int] = None,
+                  presolve: bool = False):
+    """One fused half-step: ``(X [D, rank] of Y's dtype, status int32 [2] = [failed systems, bad source
+    indices])``, and with ``presolve`` every destination's ``[als.system_size]`` sums before the ridge."""
+    from . import als
+
+    if not torch.is_tensor(Y) or Y.dim() != 2:
+        raise ValueError("als_half_step: source factors must be a [S, rank] tensor")
+    D, rank = int(offsets.numel()) - 1, int(Y.shape[1])
+    plan = _AlsPlan(None, als.Segments(offsets, src, rating, D, int(Y.shape[0])), rank, reg, Y.dtype, chunk, blocks)
+    X = torch.empty(D, rank, dtype=Y.dtype, device=Y.device)
+    pre = torch.zeros(D, als.system_size(rank), dtype=torch.float64, device=Y.device) if presolve else None
+    plan.half(1, Y, X, pre)
+    return (X, plan.status, pre) if presolve else (X, plan.status)
+
+
+def als_predict(u, v, sel, U, V) -> torch.Tensor:
+    """f64 ``[n]``: the dot product of rows ``u[i]`` of U and ``v[i]`` of V, NaN for a dead row or -1."""
+    _check_dev(u, v, sel, U, V)
+    n = int(u.numel())
+    if (u.dtype != torch.int32 or v.dtype != torch.int32 or u.dim() != 1 or tuple(v.shape) != (n,)
+            or not (u.is_contiguous() and v.is_contiguous())):
+        raise ValueError("als_predict: the indices must be contiguous int32 [n]")
+    if (U.dim() != 2 or V.dim() != 2 or U.dtype != V.dtype or U.dtype not in (torch.float32, torch.float64)
+            or U.shape[1] != V.shape[1] or not (U.is_contiguous() and V.is_contiguous())):
+        raise ValueError("als_predict: the factors must be contiguous f32 / f64 [*, rank] of one dtype and rank")
+    if not 1 <= int(U.shape[1]) <= 64:
+        raise ValueError("als_predict: rank must be in [1, 64]")
+    if n and (int(u.max()) >= U.shape[0] or int(v.max()) >= V.shape[0] or int(u.min()) < -1 or int(v.min()) < -1):
+        raise ValueError("als_predict: an index lies outside its factor table")
+    sel = _mask_u8(sel, n, "the selection", "als_predict")
+    out = torch.empty(n, dtype=torch.float64, device=u.device)
+    native.hip().als_predict(u.data_ptr(), v.data_ptr(), _ptr(sel), n, U.data_ptr(), V.data_ptr(), _DT[U.dtype],
+                             int(U.shape[1]), out.data_ptr(), _stream())
+    return out
+
+
+# ------------------------------------------------------------------------------------------
 # exact quantiles: radix select (csrc/hip/quantile.hip)
 # ------------------------------------------------------------------------------------------
 # (the relational kernels below -- quantiles, groupby, sort, join -- share the key reader of keys.h;

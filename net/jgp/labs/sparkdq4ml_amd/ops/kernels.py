@@ -14,7 +14,8 @@ Ops:
   K5m ``gmm_pass``           one EM pass of a Gaussian mixture: k densities per row, responsibility-weighted moments per component
   K5l ``logreg_pass``        one logistic loss / gradient evaluation (multinomial softmax or binomial), or raw / prob / pred
   K5p ``mlp_pass``           one loss / gradient evaluation of a small dense network (sigmoid hidden layers, softmax on top), or pred
-  K5t ``tree_bin`` / ``tree_hist`` / ``tree_split`` / ``tree_route`` / ``tree_predict``  the level passes of a decision tree
+  K5a ``als_half_step`` / ``als_predict``  one ALS half-step over a segment table (gather, normal equations, Cholesky), the prediction dot products
+  K5t ``tree_bin`` /``tree_hist`` / ``tree_split`` / ``tree_route`` / ``tree_predict``  the level passes of a decision tree
   K5r ``forest_bag`` / ``forest_hist`` / ``forest_split`` / ``forest_route`` / ``forest_predict``  the level passes of a random forest
   K5q ``quantiles``          exact order statistics of C columns x Q probabilities (radix select)
   K5g ``group_encode`` / ``group_agg``  group ids of key columns, integer-word grouped aggregates
@@ -39,7 +40,7 @@ from .window import (window_bounds, window_finish, window_heads, window_limits, 
 from .join import join_key_columns, join_limits, join_mask, join_pairs  # noqa: F401  (K5j: dispatches by device itself)
 
 __all__ = ["selected_indices", "pack_columns", "gram_stats", "predict", "regression_metrics",
-           "gram_layout_size", "glm_pass", "kmeans_pass", "gmm_pass", "logreg_pass", "mlp_pass", "tree_bin", "tree_hist", "tree_split", "tree_route", "tree_predict", "forest_bag", "forest_hist", "forest_split", "forest_route", "forest_predict", "gram_stats_folds", "fold_ids", "fold_thresholds", "fold_seed", "quantiles", "group_encode", "group_encode_columns",
+           "gram_layout_size", "glm_pass", "kmeans_pass", "gmm_pass", "logreg_pass", "mlp_pass", "als_half_step", "als_predict", "tree_bin", "tree_hist", "tree_split", "tree_route", "tree_predict", "forest_bag", "forest_hist", "forest_split", "forest_route", "forest_predict", "gram_stats_folds", "fold_ids", "fold_thresholds", "fold_seed", "quantiles", "group_encode", "group_encode_columns",
            "group_agg", "group_scale", "group_limits", "sort_permutation", "sort_limits", "window_heads", "window_bounds",
            "window_prefix", "window_minmax", "window_finish", "window_limits", "join_pairs", "join_mask",
            "join_key_columns", "join_limits"]
@@ -243,6 +244,36 @@ def mlp_pass(X: torch.Tensor, y, sel, weights, layers, mode: int, blocks: Option
     from . import mlp
 
     return mlp.mlp_pass_host(X, y, sel, weights, layers, mode)
+
+
+def als_half_step(offsets, src, rating, Y: torch.Tensor, reg: float, chunk: Optional[int] = None,
+                  blocks: Optional[int] = None, presolve: bool = False):
+    """One ALS half-step of ``ops/als.py`` over a segment table (``offsets [D + 1]`` int64, ``src
+    [nnz]`` int32, ``rating [nnz]`` f64) from the source factors ``Y [S, rank]`` (f32 / f64):
+    ``(X [D, rank] of Y's dtype, status [2] = [failed systems, bad source indices])``, and with
+    ``presolve`` also the ``[D, system_size]`` sums that enter the solves.  Device tensors: the fused
+    pass (1 <= rank <= 64); host tensors: its fp64 twin."""
+    if _on_gpu(Y):
+        from . import device
+
+        return device.als_half_step(offsets, src, rating, Y, reg, chunk, blocks, presolve)
+    from . import als
+
+    out = als.als_half_step_host(offsets, src, rating, Y, reg, Y.numpy().dtype, presolve)
+    res = (torch.from_numpy(out[0]), torch.tensor([out[1], 0], dtype=torch.int32))
+    return res + (torch.from_numpy(out[2]),) if presolve else res
+
+
+def als_predict(u: torch.Tensor, v: torch.Tensor, sel, U: torch.Tensor, V: torch.Tensor) -> torch.Tensor:
+    """f64 ``[n]``: the dot product of rows ``u[i]`` of U and ``v[i]`` of V (int32 indices, -1 for an
+    id the fit did not see), NaN for a dead row or an index -1."""
+    if _on_gpu(u):
+        from . import device
+
+        return device.als_predict(u, v, sel, U, V)
+    from . import als
+
+    return als.predict_host(u, v, sel, U, V)
 
 
 # ------------------------------------------------------------------------------------------
